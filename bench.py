@@ -27,6 +27,8 @@ graph's iterations/s (the workload that shards).
 operator sequence, timed on this host at 8 threads and at the
 container's CPU quota (rank 0, N = 1 only); the scalar C port of the checker is reported beside it.
 Exactly --steps steps are timed (default 1000: 80 ms of C3 steps).
+`--dump-outputs DIR`: the poses and patches the last timed step wrote, as DIR/poses.npy and DIR/patches.npy (float32); the
+inputs depend on --workload and --seed only, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -53,7 +55,12 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--probe-ipc", action="store_true", help="internal: child process of an N > 1 run (see ipc_probe)")
     ap.add_argument("--no-large", action="store_true", help="skip the 2.1M-edge sharded workload reported beside the headline")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses.npy, patches.npy, float32) into DIR")
+    args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    return args
 
 
 def ipc_probe(world, local, timeout=240.0):
@@ -243,6 +250,13 @@ def main():
         return steps, el
 
     steps, elapsed = timed(ba_iter, args.warmup, args.steps)
+    dumped = None
+    if args.dump_outputs:
+        # the buffers the last timed step wrote, copied before the blocks below step on from them (N > 1: every rank's own
+        # disparities merged, a collective of all ranks)
+        last = (args.warmup + steps) & 1
+        dumped = {"poses": P[last].cpu().numpy(),
+                  "patches": (X[last] if world == 1 else eng.gather_patches(X[last])).cpu().numpy()}
     # the spread of that number: the same K steps five more times (each block between its own fences; `value` stays the first)
     blocks = [1e3 * el / st_ for st_, el in (timed(ba_iter, 0, args.steps) for _ in range(5))]
     xrates = None
@@ -584,6 +598,11 @@ def main():
         out["roofline"] = roofline
         if cpu_baseline is not None:
             out["cpu_baseline"] = cpu_baseline
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, np.float32))
+            out["dump_outputs"] = {name: list(a.shape) for name, a in dumped.items()}
         print(json.dumps(out), flush=True)
     if world > 1:
         for e in engines.values():

@@ -2,6 +2,7 @@
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from batrack_amd.backend.ba import BA_rgbd_droid
@@ -9,6 +10,17 @@ from batrack_amd.backend.lietorch import SE3
 from batrack_amd.plan import Plan, Stepper
 
 DEV = "cuda:0"
+
+# Processes that may hold the GPU at one time.  The sharded tests start one process per rank, all on cuda:0, beside the pytest
+# process that holds it already; a shared GPU machine admits 6 (BT_TEST_GPU_PROCESSES sets another budget).
+GPU_PROCESSES = int(os.environ.get("BT_TEST_GPU_PROCESSES", "6"))
+
+
+def require_ranks_on_one_gpu(world):
+    """Skip, before any work, a test whose `world` ranks would open cuda:0 in more processes than the budget allows."""
+    if world + 1 > GPU_PROCESSES:
+        pytest.skip(f"needs {world} ranks on one GPU beside the test process ({world + 1} processes with the GPU open); "
+                    f"this machine admits {GPU_PROCESSES}")
 
 # Precision of the per-edge maths of the process under test (DESIGN.md §4): graphs that take k_tile — every graph a real
 # window produces, every fixture — run float64 per edge; BT_FORCE prec=f32 or a forced k_stream / k_edge2 (the mixed-precision

@@ -78,6 +78,8 @@ def run(seeds, world, big=False):
 
 @pytest.mark.parametrize("world,first", [(2, 7100), (4, 7200), (8, 7300)])
 def test_random_graphs_sharded_vs_oracle(world, first):
+    from gpu_util import require_ranks_on_one_gpu
+    require_ranks_on_one_gpu(world)
     lines = run(range(first, first + 16), world)
     bad = [l for l in lines if not l.startswith("ok")]
     assert len(lines) >= 16 and not bad, bad

@@ -91,6 +91,8 @@ def _worker(rank, world, port, out, shape, fixedp, exchange="rccl", per_track_lm
                                                          [("band", 1, 2), ("shibuya", 9, 2), ("band", 1, 4), ("few", 1, 4)]] +
                          [("band", 1, 8, "ipc"), ("shibuya_full", 35, 8, "ipc"), ("shibuya_full", 35, 8, "rccl")])    # BASELINE.json configs[3]: eight ranks
 def test_sharded_step_equals_oracle_and_single_gpu(shape, fixedp, world, exchange):
+    from gpu_util import require_ranks_on_one_gpu
+    require_ranks_on_one_gpu(world)
     import oracle
     from batrack_amd.plan import Plan, Stepper
     g, d = _inputs(shape=shape)

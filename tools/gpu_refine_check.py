@@ -1,5 +1,6 @@
 import sys, os
-sys.path[:0] = ['/root/repo', '/root/repo/tests']
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 import numpy as np, torch, oracle
 from batrack_amd import graphgen
 from gpu_util import HipProblem, rel, update_err

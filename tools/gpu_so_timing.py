@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path[:0]=["/root/repo"]
+sys.path[:0]=[os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 import numpy as np, torch
 from batrack_amd import graphgen
 from batrack_amd.plan import Plan, Stepper
