@@ -768,6 +768,18 @@ int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
         *data = pl->trk_of_patch.data();
         return (int64_t)pl->trk_of_patch.size();
     }
+    if (std::strcmp(name, "ws_layout") == 0) {                // byte offsets in the workspace: sys, zero_bytes, status, total (int64)
+        const int64_t v[4] = {(int64_t)pl->ws.sys, (int64_t)pl->ws.zero_bytes, (int64_t)pl->ws.status, (int64_t)pl->ws.total};
+        pl->dev_readback.assign(8, 0);
+        std::memcpy(pl->dev_readback.data(), v, sizeof(v));
+        *data = pl->dev_readback.data();
+        return 4;
+    }
+    if (std::strcmp(name, "solver_mode") == 0) {              // 0 .. 3 (ba_kernels.hpp: solver_mode), -1 for a host-only plan
+        pl->dev_readback.assign(1, pl->dev_base ? (int32_t)solver_mode(pl->dev) : -1);
+        *data = pl->dev_readback.data();
+        return 1;
+    }
     if (std::strcmp(name, "trk_off") == 0) {                  // sharded: distinct tracks in front of the rank's range (one element)
         pl->dev_readback.assign(1, (int32_t)pl->trk_off);
         *data = pl->dev_readback.data();
@@ -817,7 +829,10 @@ int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
 
 int bt_ba_workspace_init(const bt_plan *pl, void *ws, void *stream) {
     if (!pl || !ws) return BT_EINVAL;
-    return hipMemsetAsync(static_cast<char *>(ws) + pl->ws.sys, 0, pl->ws.zero_bytes, static_cast<hipStream_t>(stream)) == hipSuccess
+    char *w = static_cast<char *>(ws);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the accumulators, and the status block: kernels read its flags (the refinement's, the dense solver's) before they write them
+    return hipMemsetAsync(w + pl->ws.sys, 0, pl->ws.zero_bytes, st) == hipSuccess && hipMemsetAsync(w + pl->ws.status, 0, kStatusBytes, st) == hipSuccess
                ? BT_OK : BT_EHIP;
 }
 

@@ -912,7 +912,7 @@ __device__ __forceinline__ int4 uniform4(const int4 v) {
 
 template <typename T, bool PROF>
 __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
-    if (a.status[kRefineDone] != 0) return;
+    if (sizeof(T) == 4 && a.status[kRefineDone] != 0) return;       // (the double factor solves once: no refinement, no flag)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int flags[2];
     const int tid = threadIdx.x, nth = blockDim.x, wave = tid >> 6, lane = tid & 63;

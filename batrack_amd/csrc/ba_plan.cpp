@@ -108,7 +108,7 @@ static void layout_workspace(bt_plan *pl) {
     w.zvec = off;     off = align_up(off + D * sizeof(float), 256);
     w.dx = off;       off = align_up(off + D * sizeof(float) + 64, 256);
     w.dx0 = off;      off = align_up(off + D * sizeof(float) + 64, 256);     // first solution of a refined solve (float32-factor systems)
-    w.status = off;   off = align_up(off + 1024, 256);
+    w.status = off;   off = align_up(off + kStatusBytes, 256);
     w.spart = off;
     if (pl->sp_ok) off = align_up(off + (size_t)I.tiles * sp_tile_doubles(pl->max_rows16, pl->max_tile_pairs) * sizeof(double), 256);
     w.esave = off;                                                 // k_etile -> k_etile_upd: the tiles' E, [tile][max_rows16][1 << et_lgts]

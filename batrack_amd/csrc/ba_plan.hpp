@@ -123,9 +123,14 @@ struct PlanDev {
     const int32_t *lvl_meta;   // [nlev][kMaxLevelCols][8]: col, diag pos, #sub-blocks, first rest triple, #rest triples, dp first, #dp, 0  (col = -1: unused)
 };
 
+// Bytes of the status block at WsLayout::status: int 0 the solver status, 1 the exchange time-out, 4.. profiling counters, 200 / 201
+// the dense solver's flags, 210 the refinement's flag (ba_kernels.hip, ba_dense.hip).  Cleared by bt_ba_workspace_init.
+constexpr size_t kStatusBytes = 1024;
+
 // Byte offsets of the regions inside the caller's workspace.
 struct WsLayout {
-    size_t sys, pairacc, zero_bytes;   // [sys, sys+zero_bytes) is cleared every reduce
+    size_t sys, pairacc, zero_bytes;   // [sys, sys+zero_bytes): the accumulators; zero after bt_ba_workspace_init and after every completed
+                                       // step (the kernels that consume them clear them; the reduce does not)
     size_t packed, pairgeo, qw, lfac, linv, zvec, dx, dx0, status, spart, esave, total;
     size_t priv;                       // inside the cleared region: [kPrivY][D] then [kPrivP][pairs][kPairAccStride] doubles; 0 = none
 };

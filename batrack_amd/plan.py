@@ -14,7 +14,7 @@ from . import _lib
 
 _USE_CTYPES = os.environ.get("BT_PY_BINDING", "") == "ctypes"      # measurement only: the ctypes route for every step
 
-_NP_TYPES = {"slot_lab": np.uint16, "slot_lp": np.uint8, "act_bits": np.uint32, "slot_code": np.uint16, "tile_la": np.uint8, "tile_sinfo": np.uint32, "tile_cut8": np.uint16, "tile_cut16": np.uint16, "pm_lb": np.uint8, "pm_la": np.uint8}
+_NP_TYPES = {"ws_layout": np.int64, "slot_lab": np.uint16, "slot_lp": np.uint8, "act_bits": np.uint32, "slot_code": np.uint16, "tile_la": np.uint8, "tile_sinfo": np.uint32, "tile_cut8": np.uint16, "tile_cut16": np.uint16, "pm_lb": np.uint8, "pm_la": np.uint8}
 PLAN_ARRAYS = ("kx", "trk_of_patch", "trk_loc", "pair_i", "pair_j", "tile_trk0", "tile_ntrk", "tile_ncam",
                "tile_cam0", "tile_slot0", "tile_nslot", "tile_erow0", "tile_cams", "slot_edge", "slot_pair",
                "slot_lab", "col_ptr", "row_idx", "upd_ptr", "upd", "blk_col", "upd_next", "perm", "blk_src",
@@ -225,6 +225,18 @@ class Plan:
         """8 | 6 | 4: float64 per edge, mixed (float64 reprojection and residual, float32 Jacobians: k_stream / k_edge2), float32
         (bt_plan_edge_precision)."""
         return self._lib.bt_plan_edge_precision(self._h)
+
+    @property
+    def ws_layout(self):
+        """{"sys", "zero_bytes", "status", "total"}: byte offsets in the workspace of the accumulators, their length (zero after
+        bt_ba_workspace_init and after every completed step), the 1024-byte status block, and the workspace's size."""
+        return dict(zip(("sys", "zero_bytes", "status", "total"), (int(v) for v in self.array("ws_layout"))))
+
+    @property
+    def solver_mode(self):
+        """0 | 1 | 2 | 3: the reduced-system solver of this plan's steps — block-sparse factor in LDS as double, in LDS as float
+        (refined), in the workspace as float (refined), dense in the workspace as double; -1 for a host-only plan."""
+        return int(self.array("solver_mode")[0])
 
     @property
     def built_on_device(self):

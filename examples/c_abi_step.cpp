@@ -2,12 +2,14 @@
 // Reads a problem written by tests/test_gpu_c_example.py (raw little-endian arrays), runs one pose+structure step through
 // bt_plan_create / bt_ba_workspace_init / bt_ba_step, writes the updated poses and patches back.
 //   hipcc --offload-arch=gfx950 -Iinclude examples/c_abi_step.cpp -Lbatrack_amd/lib -lbatrack_ba -Wl,-rpath,$PWD/batrack_amd/lib -o c_abi_step
-//   ./c_abi_step problem.bin result.bin
+//   ./c_abi_step problem.bin result.bin [--poison]
+// --poison fills the workspace with 0xFF bytes before bt_ba_workspace_init (a reused allocation holds anything: init is enough).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "batrack_ba.h"
@@ -26,7 +28,8 @@ static T *to_device(const std::vector<T> &v) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) { std::fprintf(stderr, "usage: %s problem.bin result.bin\n", argv[0]); return 1; }
+    const bool poison = argc == 4 && std::strcmp(argv[3], "--poison") == 0;
+    if (argc != 3 && !poison) { std::fprintf(stderr, "usage: %s problem.bin result.bin [--poison]\n", argv[0]); return 1; }
     std::FILE *f = std::fopen(argv[1], "rb");
     if (!f) return 1;
     int64_t hdr[4];                                            // E, n_buf, p_tot, fixedp
@@ -51,6 +54,7 @@ int main(int argc, char **argv) {
     HIP_OK(hipMalloc(&ws, bt_plan_workspace_bytes(plan)));
     hipStream_t st;
     HIP_OK(hipStreamCreate(&st));
+    if (poison) HIP_OK(hipMemset(ws, 0xFF, bt_plan_workspace_bytes(plan)));
     BT_CHECK(bt_ba_workspace_init(plan, ws, st));
 
     bt_ba_args a = {};

@@ -153,6 +153,13 @@ size_t bt_plan_workspace_bytes(const bt_plan *plan);
  * count, or -1 for an unknown name.  Element type is int32 unless noted in
  * DESIGN.md ("slot_lab" is uint16). */
 int64_t bt_plan_array(const bt_plan *plan, const char *name, const void **data);
+/* Two more names of bt_plan_array, read-only (tests / tooling, not the step path):
+ *   "ws_layout"    4 int64: byte offsets in the workspace of the accumulators (sys), their length (zero_bytes: zero
+ *                  after bt_ba_workspace_init and after every completed step), the status block (status, 1024 bytes),
+ *                  and the workspace's size (total = bt_plan_workspace_bytes)
+ *   "solver_mode"  1 int32: the reduced-system solver of the plan's steps, 0 = block-sparse factor in LDS as double,
+ *                  1 = in LDS as float (refined), 2 = in the workspace as float (refined), 3 = dense in the workspace
+ *                  as double (more than 255 free poses, or a filled-in system priced cheaper dense); -1 host-only plan */
 
 typedef struct {
     const float *poses;        /* [n_buf,7] tx ty tz qx qy qz qw                      */
@@ -175,10 +182,12 @@ typedef struct {
                                   A sharded plan (own_lo / own_hi) reads the entries of its own tracks from the same full array */
 } bt_ba_args;
 
-/* Clears the accumulators ([S | y] and the per-pair sums) inside `workspace`.  Call once
- * after allocating a workspace (or pass zero-filled memory), and again only if a
- * bt_ba_reduce was not followed by its bt_ba_solve_update: every completed step leaves the
- * accumulators clear for the next one (the kernels that consume them reset them). */
+/* Clears the accumulators ([S | y] and the per-pair sums) and the status block (the solver status,
+ * the exchange status, the solvers' internal flags) inside `workspace`; the rest of it may hold
+ * anything.  Call once after allocating a workspace (or pass zero-filled memory), and again only if
+ * a bt_ba_reduce was not followed by its bt_ba_solve_update, or to clear BT_XCHG_TIMEOUT: every
+ * completed step leaves the accumulators clear for the next one (the kernels that consume them
+ * reset them).  Right after it, bt_ba_status and bt_ba_xchg_status read 0. */
 int bt_ba_workspace_init(const bt_plan *plan, void *workspace, void *stream);
 
 /* One BA_rgbd_droid call, all phases, enqueued on `stream`. */

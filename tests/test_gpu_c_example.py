@@ -1,5 +1,6 @@
 """-m gpu: the C ABI from a plain HIP host program (examples/c_abi_step.cpp: no Python, no torch in the process): compiled
-here with hipcc against include/batrack_ba.h and libbatrack_ba.so, run on a generated problem, compared with the oracle."""
+here with hipcc against include/batrack_ba.h and libbatrack_ba.so, run on a generated problem (from a fresh workspace and from one
+filled with 0xFF bytes before bt_ba_workspace_init), compared with the oracle."""
 import os
 import shutil
 import struct
@@ -33,16 +34,18 @@ def test_plain_c_program_steps_through_the_abi(tmp_path):
             f.write(np.ascontiguousarray(a, np.int64).tobytes())
         for a in (g.poses, g.patches, g.mono_disp, g.intrinsics, g.targets3, g.weights_pose):
             f.write(f32(a).tobytes())
-    res = str(tmp_path / "result.bin")
-    r = subprocess.run([exe, prob, res], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "Jacobian kernel 0" in r.stdout and "solver status 0" in r.stdout, r.stdout
-    raw = open(res, "rb").read()
-    status = struct.unpack("<i", raw[:4])[0]
-    out = np.frombuffer(raw[4:], np.float32)
-    poses_out, patches_out = out[:7 * N].reshape(N, 7), out[7 * N:].reshape(P, 3)
     d = lambda a: f32(a).astype(np.float64)
     ref = oracle.ba_step(d(g.poses), d(g.patches), d(g.mono_disp), d(g.intrinsics), d(g.targets3), d(g.weights_pose), g.ii, g.jj, g.kk,
                          np.asarray(g.bounds, np.float64), fixedp=1)
     rel = lambda a, b: np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b)
-    assert status == 0 and rel(poses_out, ref["poses_out"]) < 5e-6 and rel(patches_out, ref["patches_out"]) < 5e-6
+    # a fresh allocation, and one filled with 0xFF bytes before bt_ba_workspace_init (what a reused allocation may hold): init is enough
+    for extra in ([], ["--poison"]):
+        res = str(tmp_path / "result.bin")
+        r = subprocess.run([exe, prob, res] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (extra, r.stdout + r.stderr)
+        assert "Jacobian kernel 0" in r.stdout and "solver status 0" in r.stdout, (extra, r.stdout)
+        raw = open(res, "rb").read()
+        status = struct.unpack("<i", raw[:4])[0]
+        out = np.frombuffer(raw[4:], np.float32)
+        poses_out, patches_out = out[:7 * N].reshape(N, 7), out[7 * N:].reshape(P, 3)
+        assert status == 0 and rel(poses_out, ref["poses_out"]) < 5e-6 and rel(patches_out, ref["patches_out"]) < 5e-6, extra

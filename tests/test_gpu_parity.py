@@ -522,22 +522,9 @@ def test_track_seen_by_many_cameras_vs_oracle(n_hubs):
     the float64 gates.  MANY of them stay in tiles of 38+ cameras (large local E blocks, the Schur product spread over many 16x16
     tiles, the depth back-substitution's long camera lists), whose E does not fit LDS as double: float32 per edge, the gates of the
     reference's own precision."""
-    g = graphgen.make_graph(48, 8, 4, seed=21)
-    rng = np.random.default_rng(5)
-    ii, jj, kk = [g.ii], [g.jj], [g.kk]
-    hub_tracks = (3, 100, 200) if n_hubs == 3 else tuple(range(2, 2 + 4 * n_hubs, 4))
-    for k in hub_tracks:                                      # hub tracks: their source frame to 40 other frames
-        tgt = rng.choice(48, size=40, replace=False)
-        ii.append(np.full(40, k // 8)); jj.append(tgt); kk.append(np.full(40, k))
-    ii, jj, kk = (np.concatenate(a).astype(np.int64) for a in (ii, jj, kk))
-    gt = g.patches.copy(); gt[:, 2] = g.disp_gt
-    u, v, _ = graphgen.reproject(g.poses_gt, gt, g.intrinsics, ii, jj, kk)
-    E = len(kk)
-    t3 = np.stack([u + rng.normal(0, 0.5, E), v + rng.normal(0, 0.5, E), g.disp_gt[kk]], 1)
-    w = rng.uniform(0.3, 1.0, (E, 2))
-    f = lambda a: np.asarray(a, np.float32).astype(np.float64)
-    d = dict(poses=f(g.poses), patches=f(g.patches), mono=f(g.mono_disp), intrinsics=f(g.intrinsics),
-             targets3=f(t3), weights=f(w), weights_pose=f(w), ii=ii, jj=jj, kk=kk, bounds=np.asarray(g.bounds))
+    from edge_problems import hub_graph
+    d, hub_tracks = hub_graph(n_hubs)
+    kk = d["kk"]
     ref = oracle.ba_step(d["poses"], d["patches"], d["mono"], d["intrinsics"], d["targets3"], d["weights_pose"],
                          d["ii"], d["jj"], d["kk"], d["bounds"], fixedp=1, want_system=True)
     o = HipProblem(d).raw_step("weights_pose", 1)

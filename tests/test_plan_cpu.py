@@ -187,14 +187,12 @@ def test_plan_limits():
     assert Plan(ii, jj, kk, 2049, 2049, 1, upload=False).n == 2048
     # fewer than 256 poses whose factor does not fit LDS as double: a long thin band stays block-sparse (float32 factor, refined); a graph
     # with long-range edges fills in and is priced cheaper DENSE (ba_plan.cpp, tools/gpu_solver_choice.py) — perm the identity, every block
-    rng = np.random.default_rng(5)
-    N, M, K = 120, 64, 8                                  # (a tile of 64 tracks per frame: the band is as wide as a track's span)
-    kk = np.repeat(np.arange(N * M, dtype=np.int64), K); ii = kk // M
-    jb = np.clip(ii + np.tile(np.arange(K, dtype=np.int64) - 3, N * M), 0, N - 1)
-    band = Plan(ii, jb, kk, N, N * M, 1, upload=False)
+    from edge_problems import band_120
+    ii, jb, kk, N, P = band_120(filled=False)
+    band = Plan(ii, jb, kk, N, P, 1, upload=False)
     assert band.n == N - 1 and band.nnz_blocks < (N - 1) * N // 2 // 4 and band.updates > 0
-    jf = np.where(rng.random(ii.size) < 0.3, rng.integers(0, N, ii.size), jb)
-    filled = Plan(ii, jf, kk, N, N * M, 1, upload=False)
+    ii, jf, kk, N, P = band_120(filled=True)
+    filled = Plan(ii, jf, kk, N, P, 1, upload=False)
     assert filled.n == N - 1 and filled.nnz_blocks == (N - 1) * N // 2 and filled.updates == 0
     assert np.array_equal(filled.array("perm"), np.arange(N - 1))
     ii, jj, kk = _chain_edges(2050)
@@ -535,3 +533,16 @@ def test_ranks_of_a_sharded_solve_agree_on_the_pattern_of_an_irregular_graph(wor
     # one plan for the whole list may couple more (its tiles' cameras pairwise), never less
     full = Plan(ii, jj, kk, N, N * M, 2, upload=False)
     assert full.nnz_blocks >= ref.nnz_blocks
+
+
+def test_workspace_layout_accessor():
+    """bt_plan_array("ws_layout") / ("solver_mode"): the accumulators first, the status block behind every other region, the total equal
+    to bt_plan_workspace_bytes; a host-only plan has no solver mode."""
+    from edge_problems import band_120
+    for ii, jj, kk, n_buf, p_tot in (_chain_edges(12) + (12, 12), band_120(False), band_120(True), _chain_edges(300) + (300, 300)):
+        pl = Plan(ii, jj, kk, n_buf, p_tot, 1, upload=False)
+        lay, D = pl.ws_layout, 6 * pl.n
+        assert lay["sys"] == 0 and lay["zero_bytes"] >= 8 * (D * D + D) and lay["zero_bytes"] % 256 == 0
+        assert lay["status"] % 256 == 0 and lay["status"] >= lay["zero_bytes"] and lay["status"] + 1024 <= lay["total"]
+        assert lay["total"] == pl.workspace_bytes
+        assert pl.solver_mode == -1
