@@ -17,8 +17,9 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 BT_OK, BT_EINVAL, BT_ENOMEM, BT_EHIP, BT_EUNSUPPORTED = 0, -1, -2, -3, -4
 ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "HIP runtime error",
-          BT_EUNSUPPORTED: "unsupported graph (n > 2048 free poses, or a track "
-                           "whose edges name more than one source frame: ii must equal ix[kk])"}
+          BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
+                           "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
+                           "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 

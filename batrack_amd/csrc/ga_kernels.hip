@@ -35,6 +35,15 @@ __device__ __forceinline__ float block_sum(float v, float *red) {          // bl
     return t;                                                              // valid in thread 0
 }
 
+// Cell and weight of the scale grid at image coordinate x: c = x / (size - 1) * (g - 1), its floor and fraction (F.grid_sample,
+// align_corners=True).  c in float64: in float32 a grid 1024 cells wide places a track up to 3e-5 of a cell off (the ulp of
+// 512), and between cells an O(1) apart the sample carries that.
+__device__ __forceinline__ void ga_cell(float x, int64_t size, int g, int &i0, float &w) {
+    const double c = (double)x / (double)(size - 1) * (double)(g - 1), f = floor(c);
+    i0 = (int)f;
+    w = (float)(c - f);
+}
+
 __global__ __launch_bounds__(256) void k_ga_scale(bt_ga_args a, float *mono_scaled, double *losses) {
     __shared__ float red[16];
     __shared__ float s_mean;
@@ -59,10 +68,10 @@ __global__ __launch_bounds__(256) void k_ga_scale(bt_ga_args a, float *mono_scal
         const size_t e = ((size_t)t * N + n) * S + s;
         const float x = a.trajs_2d[2 * e], y = a.trajs_2d[2 * e + 1];
         // F.grid_sample(align_corners=True, zeros padding) of exp(grid / 10) at (x / (W-1), y / (H-1))
-        const float gx = x / (float)(a.W - 1) * (float)(gw - 1), gy = y / (float)(a.H - 1) * (float)(gh - 1);
-        const float fx0 = floorf(gx), fy0 = floorf(gy);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx = gx - fx0, wy = gy - fy0;
+        int x0, y0;
+        float wx, wy;
+        ga_cell(x, a.W, gw, x0, wx);
+        ga_cell(y, a.H, gh, y0, wy);
         float fs = 0.0f;
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
@@ -174,9 +183,10 @@ __device__ __forceinline__ f2 ga_pair_loss(const GaOwn &o, const GaPartner &q) {
     return r;
 }
 
+// The two pairwise kernels declare no static LDS: the staged tracks take all of it at N = BT_GA_MAX_TRACKS (163,840 B, the
+// gfx950 limit per workgroup, static + dynamic), so their final reductions reuse the start of the staging area after a barrier.
 __global__ __launch_bounds__(kGaStrip) void k_ga_pairwise(bt_ga_args a, const float *mono_scaled, double *losses) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ float red[16];
     const int T = (int)a.T, N = (int)a.N, S = (int)a.S, mid = S / 2, M = (N + 1) >> 1;
     const int qi = blockIdx.x / S, s = blockIdx.x % S;
     const int i = (int)a.query[qi];
@@ -215,7 +225,8 @@ __global__ __launch_bounds__(kGaStrip) void k_ga_pairwise(bt_ga_args a, const fl
             acc += r.x + r.y;
         }
     }
-    const float bs = block_sum(acc, red);
+    __syncthreads();                                           // every partner read is done: the records may be overwritten
+    const float bs = block_sum(acc, sm);
     if (threadIdx.x == 0) atomicAdd(&losses[1], (double)bs / ((double)a.Q * S * N * N));
 }
 
@@ -344,7 +355,6 @@ __device__ __forceinline__ float ga_rol1(float x) {
 #endif
 __global__ __launch_bounds__(kGaStrip, BT_GA_BWD_WAVES) void k_ga_bwd_pairwise(bt_ga_args a, const float *mono_scaled, float w_rg, float *g_ms, float *g_intr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    __shared__ float red[16];
     const int T = (int)a.T, N = (int)a.N, S = (int)a.S, mid = S / 2, M = (N + 1) >> 1, Mb = (M + 63) >> 6, Mp = Mb << 6;
     const int qi = blockIdx.x / S, s = blockIdx.x % S;
     const int i = (int)a.query[qi];
@@ -435,8 +445,9 @@ __global__ __launch_bounds__(kGaStrip, BT_GA_BWD_WAVES) void k_ga_bwd_pairwise(b
         // (refine_intrinsics: RefineNet.intrinsics is K * K_scale for every frame, refine_net.py:131-136): dX/dfx = -X / fx,
         // dX/dcx = -D / fx, dY/dfy = -Y / fy, dY/dcy = -D / fy   (the factor -c is in v already)
         const size_t js = (size_t)jraw, jmc = (size_t)(jm < 0 ? 0 : (jm > T - 1 ? T - 1 : jm));
+        __syncthreads();                                       // every record read (emit) is done: the records may be overwritten
         for (int k = 0; k < 8; ++k) {
-            const float tsum = block_sum(v[k], red);
+            const float tsum = block_sum(v[k], sm);
             if (threadIdx.x == 0) atomicAdd(&g_intr[4 * (k < 4 ? js : jmc) + (k & 3)], tsum / (k < 4 ? Ks : Km)[k & 1]);
         }
     }
@@ -458,11 +469,10 @@ __global__ __launch_bounds__(256) void k_ga_bwd_grid(bt_ga_args a, const float *
         const size_t e = ((size_t)t * N + n) * S + s;
         const float g = g_ms[e] * ga_disp(a.trajs_disp_mono, e, half);
         if (g == 0.0f) continue;
-        const float x = a.trajs_2d[2 * e], y = a.trajs_2d[2 * e + 1];
-        const float gx = x / (float)(a.W - 1) * (float)(gw - 1), gy = y / (float)(a.H - 1) * (float)(gh - 1);
-        const float fx0 = floorf(gx), fy0 = floorf(gy);
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const float wx = gx - fx0, wy = gy - fy0;
+        int x0, y0;
+        float wx, wy;
+        ga_cell(a.trajs_2d[2 * e], a.W, gw, x0, wx);
+        ga_cell(a.trajs_2d[2 * e + 1], a.H, gh, y0, wy);
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -621,6 +631,24 @@ __global__ __launch_bounds__(256) void k_ga_bwd_pts3d(bt_ga_args a, const float 
         }
     }
 }
+
+// ------------------------------------------------------------------ host side: the rigidity term's size limit
+constexpr size_t kGaLdsMax = 160 * 1024;                         // gfx950: LDS per workgroup, static + dynamic
+
+// dynamic LDS of the two pairwise kernels: every super-track (forward), blocks of 64 super-tracks (backward)
+inline size_t ga_fwd_lds(int64_t N) { return (size_t)((N + 1) / 2) * kGaRec * sizeof(float4); }
+inline size_t ga_bwd_lds(int64_t N) { return (size_t)(((N + 1) / 2 + 63) / 64 * 64) * kGaRec * sizeof(float4); }
+
+// Checked before anything is enqueued.  BT_EUNSUPPORTED for N > BT_GA_MAX_TRACKS, and where the kernel's static LDS (its code
+// object's group_segment_fixed_size: 0 for these kernels) plus `dyn` would exceed a workgroup's; BT_EHIP when HIP cannot report
+// or raise the limit.
+inline int ga_pairwise_ready(const void *kernel, int64_t N, size_t dyn, LdsLimit &lim) {
+    if (N > BT_GA_MAX_TRACKS) return BT_EUNSUPPORTED;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) return BT_EHIP;
+    if (dyn + fa.sharedSizeBytes > kGaLdsMax) return BT_EUNSUPPORTED;
+    return lim.ensure(kernel, dyn) ? BT_OK : BT_EHIP;
+}
 }  // namespace bt
 
 extern "C" int bt_ga_backward_total(const bt_ga_args *a, const float *mono_scaled, const bt_ga_weights *w, float *g_mono_scaled,
@@ -631,7 +659,13 @@ extern "C" int bt_ga_backward_total(const bt_ga_args *a, const float *mono_scale
         !a->query || !a->trajs_scales || !a->frame_scales || !a->frame_shifts) return BT_EINVAL;
     if ((w->pts3d != 0.0f || w->cam_smooth != 0.0f) && !a->pose) return BT_EINVAL;
     if (w->smooth_mode < BT_GA_SMOOTH_L1 || w->smooth_mode > BT_GA_SMOOTH_HUBER) return BT_EINVAL;
-    if (a->T * a->S > 0x7fffffff || a->T * a->N * a->S > ((int64_t)1 << 40) || a->gh * a->gw > 12 * 1024) return BT_EUNSUPPORTED;
+    if (a->T * a->S > 0x7fffffff || a->T * a->N * a->S > ((int64_t)1 << 40) || a->gh * a->gw > BT_GA_MAX_GRID_CELLS) return BT_EUNSUPPORTED;
+    const size_t lds = bt::ga_bwd_lds(a->N);
+    if (w->rigid != 0.0f) {
+        static bt::LdsLimit lds_limit;
+        const int rc = bt::ga_pairwise_ready(reinterpret_cast<const void *>(&bt::k_ga_bwd_pairwise), a->N, lds, lds_limit);
+        if (rc != BT_OK) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t tns = (size_t)(a->T * a->N * a->S);
     if (hipMemsetAsync(g_mono_scaled, 0, tns * sizeof(float), st) != hipSuccess ||
@@ -642,12 +676,10 @@ extern "C" int bt_ga_backward_total(const bt_ga_args *a, const float *mono_scale
     const dim3 qs((unsigned)(a->Q * a->S)), ts((unsigned)(a->T * a->S));
     hipLaunchKernelGGL(bt::k_ga_bwd_spatial, qs, dim3(256), 0, st, *a, mono_scaled, w->spatial, g_mono_scaled, grad_trajs_scales);
     if (w->rigid != 0.0f) {
-        const size_t M = (size_t)(a->N + 1) / 2, Mb = (M + 63) / 64, lds = Mb * 64 * bt::kGaRec * sizeof(float4);
-        if (lds > 160 * 1024) return BT_EUNSUPPORTED;             // N <= 4096 tracks per frame
-        static bt::LdsLimit lds_limit;
-        if (!lds_limit.ensure(reinterpret_cast<const void *>(&bt::k_ga_bwd_pairwise), lds)) return BT_EHIP;
+        const size_t Mb = (size_t)((a->N + 1) / 2 + 63) / 64;
         hipLaunchKernelGGL(bt::k_ga_bwd_pairwise, dim3((unsigned)(a->Q * a->S), (unsigned)((Mb + bt::kGaStrip / 64 - 1) / (bt::kGaStrip / 64))), dim3(bt::kGaStrip),
                            lds, st, *a, mono_scaled, w->rigid, g_mono_scaled, grad_intrinsics);
+        if (hipGetLastError() != hipSuccess) return BT_EHIP;     // before anything else is enqueued: no total without its rigidity term
     }
     if (w->pts3d != 0.0f)
         hipLaunchKernelGGL(bt::k_ga_bwd_pts3d, ts, dim3(256), 0, st, *a, mono_scaled, w->pts3d, g_mono_scaled, grad_pose, grad_intrinsics);
@@ -732,24 +764,27 @@ extern "C" int bt_ga_forward(const bt_ga_args *a, float *mono_scaled_out, double
     if (!a->trajs_2d || !a->trajs_disp || !a->trajs_disp_mono || !a->trajs_vis || !a->trajs_static || !a->jj || !a->intrinsics ||
         !a->pose || !a->query || !a->trajs_scales || !a->frame_scales || !a->frame_shifts) return BT_EINVAL;
     if (a->T * a->S > 0x7fffffff || a->T * a->N * a->S > ((int64_t)1 << 40)) return BT_EUNSUPPORTED;
+    const int mode = (which >> 8) & 3;
+    if ((which & 8) && mode > BT_GA_SMOOTH_HUBER) return BT_EINVAL;
+    const size_t M = (size_t)(a->N + 1) / 2, lds = bt::ga_fwd_lds(a->N);
+    if (which & 2) {
+        static bt::LdsLimit lds_limit;
+        const int rc = bt::ga_pairwise_ready(reinterpret_cast<const void *>(&bt::k_ga_pairwise), a->N, lds, lds_limit);
+        if (rc != BT_OK) return rc;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(losses, 0, 5 * sizeof(double), st) != hipSuccess) return BT_EHIP;
     hipLaunchKernelGGL(bt::k_ga_scale, dim3((unsigned)(a->T * a->S)), dim3(256), 0, st, *a, mono_scaled_out, losses);
     if (which & 2) {
-        const size_t M = (size_t)(a->N + 1) / 2, lds = M * bt::kGaRec * sizeof(float4);
-        if ((M + 63) / 64 * 64 * bt::kGaRec * sizeof(float4) > 160 * 1024) return BT_EUNSUPPORTED;      // N <= 4096 tracks per frame (the backward's staging: blocks of 64 track pairs)
-        static bt::LdsLimit lds_limit;
-        if (!lds_limit.ensure(reinterpret_cast<const void *>(&bt::k_ga_pairwise), lds)) return BT_EHIP;
         hipLaunchKernelGGL(bt::k_ga_pairwise, dim3((unsigned)(a->Q * a->S), (unsigned)((M + bt::kGaStrip - 1) / bt::kGaStrip)), dim3(bt::kGaStrip),
                            lds, st, *a, mono_scaled_out, losses);
+        if (hipGetLastError() != hipSuccess) return BT_EHIP;     // before anything else is enqueued: no loss without its rigidity term
     }
     if (which & 4) {
         const size_t total = (size_t)(a->T * a->N * a->S);
         hipLaunchKernelGGL(bt::k_ga_pts3d, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *a, mono_scaled_out, losses);
     }
     if (which & 8) {
-        const int mode = (which >> 8) & 3;
-        if (mode > BT_GA_SMOOTH_HUBER) return BT_EINVAL;
         hipLaunchKernelGGL(bt::k_ga_smooth<false>, dim3(1), dim3(256), 0, st, *a, mode, losses, 0.0f, 0.0f, (float *)nullptr, (float *)nullptr);
     }
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;

@@ -39,6 +39,15 @@ typedef struct {
                                       float16 (BASELINE.json configs[4]); everything else stays float32 */
 } bt_ga_args;
 
+/* Size limits, checked before anything is enqueued (a refused call leaves every output buffer untouched):
+ *   N <= BT_GA_MAX_TRACKS whenever the inter-frame term is computed (bt_ga_forward: `which` bit 1; bt_ga_backward_total:
+ *   weights->rigid != 0), else BT_EUNSUPPORTED — its kernels stage the points of all N tracks of a (query frame, slot) in LDS,
+ *   and at 4096 tracks they fill the 160 KiB a workgroup has;
+ *   gh * gw <= BT_GA_MAX_GRID_CELLS in bt_ga_backward_total, else BT_EUNSUPPORTED (a frame's grid is summed in LDS).
+ * A scale grid with gh = 1 or gw = 1 has no neighbours in that direction: that half of the smoothness term is 0. */
+#define BT_GA_MAX_TRACKS 4096
+#define BT_GA_MAX_GRID_CELLS (12 * 1024)
+
 /* mono_scaled_out [T,N,S] float32 = get_frame_scaled_depth(); losses[5] (device, float64) = spatial huber term,
  * inter_frame_loss, pts_3d_loss, cam_smooth_vec_loss (refine_net.py:356-360), scale_grid_smoothness_loss (:362-392) — each
  * the reference's mean.  `which` selects: bit 0 spatial (always computes mono_scaled_out), bit 1 inter-frame, bit 2 3-D

@@ -129,7 +129,10 @@ def scale_grid_smoothness_loss(frame_scales_, mode="l2"):
     dh, dv = s[:, :, :-1] - s[:, :, 1:], s[:, :-1, :] - s[:, 1:, :]
     f = {"l2": lambda x: x * x, "l1": lambda x: x.abs(),
          "huber": lambda x: torch.where(x.abs() < 1.0, 0.5 * x * x, x.abs() - 0.5)}[mode]
-    return f(dh).mean() + f(dv).mean()
+    # a grid one cell wide or high has no neighbours in that direction: that half is 0 (torch's mean of nothing would be nan;
+    # include/batrack_ga.h states 0)
+    mean = lambda x: x.mean() if x.numel() else torch.zeros((), dtype=x.dtype)
+    return mean(f(dh)) + mean(f(dv))
 
 
 def full_total_and_grads(d, weights, smooth_mode="l1", refine_intrinsics=False, K=None, K_scale=20.0,

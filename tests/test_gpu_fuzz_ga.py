@@ -1,5 +1,6 @@
 """Random shapes through the dense global-alignment losses and their gradients: frames, tracks per frame
-(odd, tiny, not a multiple of anything the kernels block by), window spans, query-frame subsets, the loss mix — against the float64
+(odd, tiny, not a multiple of anything the kernels block by), window spans, query-frame subsets, the loss mix, scale-grid shapes,
+track positions off the image — against the float64
 numpy statement of the losses and the torch autograd of it (oracle/ga_losses.py, oracle/ga_torch.py).
 
 As a script: python tests/test_gpu_fuzz_ga.py [first_seed] [count]"""
@@ -27,7 +28,12 @@ def check(seed):
     d = G.make_case(T, N, S, seed=seed)
     nq = int(rng.integers(1, T + 1))
     d["grid_query_frames"] = np.sort(rng.choice(T, nq, replace=bool(rng.random() < 0.2))).astype(np.int64)
-    desc = f"seed {seed}: T={T} N={N} S={S} alpha={alpha} query frames {d['grid_query_frames'].tolist()}"
+    # scale grids of any shape (one cell wide or high included), track positions off the image and on its edges
+    gh, gw = int(rng.choice([1, 2, 3, 4, 6])), int(rng.choice([1, 2, 4, 5, 9]))
+    outside = float(rng.choice([0.0, 0.1, 0.3]))
+    d = G.move_outside(G.regrid(d, gh, gw, seed=seed), outside, seed=seed)
+    desc = (f"seed {seed}: T={T} N={N} S={S} alpha={alpha} query frames {d['grid_query_frames'].tolist()} grid {gh}x{gw} "
+            f"off-image fraction {outside}")
     net = G.build(d)
     l = net.losses().cpu().numpy()[:3]
     ms = ga.frame_scaled_depth(d)

@@ -52,6 +52,40 @@ def make_case(T, N, S, seed):
     return {k: (np.asarray(v, np.float32).astype(np.float64) if np.asarray(v).dtype == np.float64 and np.ndim(v) > 0 else v) for k, v in d.items()}
 
 
+def regrid(d, gh, gw, seed, spread=1.0):
+    """Replace the scale grid of a make_case case by a [T,gh,gw] one, raw values spread * N(0, 1) (spread 6: neighbouring
+    cells differ by more than 1 after exp(g / 10), both branches of the huber smoothness term)."""
+    g = np.random.default_rng(seed).standard_normal((len(d["pose"]), gh, gw)) * spread
+    return dict(d, frame_scales_=g.astype(np.float32).astype(np.float64))
+
+
+def move_outside(d, frac, seed):
+    """Move a fraction `frac` of a make_case case's track positions off the image (zero padding of the scale grid) or onto
+    its edges: x < 0, y < 0, x > W-1, y > H-1, x = W-1, y = H-1, and the cell boundaries of the scale grid."""
+    rng = np.random.default_rng(seed)
+    H, W = int(d["H"]), int(d["W"])
+    gh, gw = d["frame_scales_"].shape[1:]
+    xy = d["trajs_2d"].copy()
+    sel = rng.random(xy.shape[:-1]) < frac
+    k = int(sel.sum())
+    kind = rng.integers(0, 6, k)
+    x, y = xy[sel][:, 0].copy(), xy[sel][:, 1].copy()
+    far = lambda n, hi: rng.uniform(1.0, 0.6 * hi, n)
+    x = np.where(kind == 0, -far(k, W), x)                                     # left of the image
+    y = np.where(kind == 1, -far(k, H), y)                                     # above
+    x = np.where(kind == 2, (W - 1) + far(k, W), x)                            # right
+    y = np.where(kind == 3, (H - 1) + far(k, H), y)                            # below
+    on_edge = rng.random(k) < 0.5
+    x = np.where((kind == 4) & on_edge, W - 1, x)                              # exactly on the last column / row
+    y = np.where((kind == 4) & ~on_edge, H - 1, y)
+    cx = rng.integers(0, gw, k) * (W - 1) / max(gw - 1, 1)                     # a cell boundary of the grid (x / (W-1) * (gw-1) whole)
+    cy = rng.integers(0, gh, k) * (H - 1) / max(gh - 1, 1)
+    x = np.where(kind == 5, cx, x)
+    y = np.where(kind == 5, cy, y)
+    xy[sel] = np.stack([x, y], -1)
+    return dict(d, trajs_2d=xy.astype(np.float32).astype(np.float64))
+
+
 # (the pairwise kernels walk the tracks two by two: odd N, an odd number of such pairs — 301 -> 151 — and a handful of tracks)
 @pytest.mark.parametrize("T,N,S", [(12, 300, 7), (6, 520, 5), (5, 301, 5), (4, 7, 3), (4, 2, 3), (3, 1030, 3)])
 def test_larger_cases_vs_oracle(T, N, S):

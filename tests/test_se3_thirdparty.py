@@ -102,6 +102,34 @@ def test_log_matches_scipy(impl):
 
 
 @pytest.mark.parametrize("impl", IMPLS)
+def test_log_up_to_pi_matches_scipy(impl):
+    """Angles from 3 rad up to pi, and quaternions with w < 0 (angles past pi, which Log folds back below pi): the rotation of
+    Log(X) is scipy's, |phi| <= pi, and scipy's exponential of the whole tangent gives X back.  Below pi - 1e-4 phi is
+    scipy's rotation vector itself.  The branch |w| < 1e-6 (so3.h:115-151) takes the angle as exactly pi: it is off by
+    |w| there (pi - 1e-7 below)."""
+    f = impl()
+    n = 64
+    ang = np.concatenate([RNG.uniform(3.0, np.pi - 1e-4, n - 8), [np.pi - 1e-4, np.pi - 1e-5, np.pi - 1e-7, np.pi, np.pi, 4.0, 5.5, 2 * np.pi - 1e-3]])
+    ax = RNG.standard_normal((n, 3))
+    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    q = np.concatenate([ax * np.sin(ang / 2)[:, None], np.cos(ang / 2)[:, None]], 1)   # w < 0 for the angles past pi
+    t = RNG.standard_normal((n, 3))
+    X = np.concatenate([t, q], 1)
+    got = f["log"](X)
+    w = np.abs(q[:, 3])
+    slack = np.where(w < 1e-6, 2 * w, 0.0) + f["log_tol"]
+    R = Rotation.from_quat(q)
+    assert (np.abs(Rotation.from_rotvec(got[:, 3:]).as_matrix() - R.as_matrix()).max((1, 2)) <= slack).all()
+    assert np.linalg.norm(got[:, 3:], axis=1).max() <= np.pi * (1 + 1e-15)
+    below = np.minimum(ang, 2 * np.pi - ang) < np.pi - 1e-4 + 1e-12
+    assert np.abs(got[below, 3:] - R[below].as_rotvec()).max() < f["log_tol"]
+    M = np.tile(np.eye(4), (n, 1, 1))
+    M[:, :3, :3], M[:, :3, 3] = R.as_matrix(), t
+    back = np.stack([sp_expm(hat(v)) for v in got])
+    assert (np.abs(back - M).max((1, 2)) <= slack * (1 + np.abs(t).max(1)) + 1e-9).all()
+
+
+@pytest.mark.parametrize("impl", IMPLS)
 def test_compose_inverse_and_action_match_scipy(impl):
     f = impl()
     X, Y = f["exp"](tangents()), f["exp"](tangents())
