@@ -789,3 +789,76 @@ extern "C" int bt_ga_forward(const bt_ga_args *a, float *mono_scaled_out, double
     }
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }
+
+// ------------------------------------------------------------------ the stage's output: RefineNet.scaled_dmaps (refine_net.py:408-416)
+// One workgroup per map row (t, y): the two grid rows the row lies between, exponentiated once into LDS, and the row's y weight
+// once; then per pixel the x weight, PyTorch's upsample_bilinear2d lerp (x first, then y) and d / (s + shift d).  8 bytes per
+// pixel; float4 loads and stores when W % 4 == 0 (every row then starts on 16 bytes).
+namespace bt {
+__device__ __forceinline__ void up_src(int i, float scale, int g, int &i0, int &i1, float &l) {   // align_corners=True
+    const float src = scale * (float)i;
+    i0 = (int)src;
+    i1 = i0 + (i0 < g - 1 ? 1 : 0);
+    l = src - (float)i0;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ga_scaled_dmaps(const float *dmaps, const float *fs, const float *shifts, float *out,
+                                                         int H, int W, int gh, int gw, float sh, float sw) {
+    extern __shared__ float e[];                                  // [2][gw]: exp(grid / 10) of grid rows y0, y1
+    const int row = blockIdx.x, t = row / H, y = row - t * H;
+    int y0, y1;
+    float ly;
+    up_src(y, sh, gh, y0, y1, ly);
+    const float ly0 = 1.0f - ly;
+    const float *g = fs + (size_t)t * gh * gw;
+    for (int j = threadIdx.x; j < gw; j += blockDim.x) {
+        e[j] = expf(g[(size_t)y0 * gw + j] / 10.0f);
+        e[gw + j] = expf(g[(size_t)y1 * gw + j] / 10.0f);
+    }
+    __syncthreads();
+    const float shift = shifts[t];
+    const size_t base = (size_t)row * W;
+    auto px = [&](int x, float d) {
+        int x0, x1;
+        float lx;
+        up_src(x, sw, gw, x0, x1, lx);
+        const float lx0 = 1.0f - lx;
+        const float s = ly0 * (lx0 * e[x0] + lx * e[x1]) + ly * (lx0 * e[gw + x0] + lx * e[gw + x1]);
+        return d / (s + shift * d);
+    };
+    if (VEC) {
+        const float4 *src = reinterpret_cast<const float4 *>(dmaps + base);
+        float4 *dst = reinterpret_cast<float4 *>(out + base);
+        for (int i = threadIdx.x; i < W / 4; i += blockDim.x) {
+            const float4 d = src[i];
+            dst[i] = make_float4(px(4 * i, d.x), px(4 * i + 1, d.y), px(4 * i + 2, d.z), px(4 * i + 3, d.w));
+        }
+    } else {
+        for (int x = threadIdx.x; x < W; x += blockDim.x) out[base + x] = px(x, dmaps[base + x]);
+    }
+}
+}  // namespace bt
+
+extern "C" int bt_ga_scaled_dmaps(const float *dmaps, const float *frame_scales, const float *frame_shifts, float *out,
+                                  int64_t T, int64_t gh, int64_t gw, int64_t H, int64_t W, void *stream) {
+    if (!dmaps || !frame_scales || !frame_shifts || !out || T < 1 || gh < 1 || gw < 1 || H < 1 || W < 1) return BT_EINVAL;
+    if (T * H > 0x7fffffffll || W > 0x7fffffffll || gh > 0x7fffffffll || gw > BT_GA_MAX_GRID_W || (double)T * (double)H * (double)W > 9e18)
+        return BT_EUNSUPPORTED;
+    const size_t lds = 2 * (size_t)gw * sizeof(float);
+    const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(dmaps) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const void *k = vec ? reinterpret_cast<const void *>(&bt::k_ga_scaled_dmaps<true>) : reinterpret_cast<const void *>(&bt::k_ga_scaled_dmaps<false>);
+    static bt::LdsLimit lds_vec, lds_scalar;
+    if (!(vec ? lds_vec : lds_scalar).ensure(k, lds)) return BT_EHIP;
+    // the scales of PyTorch's area_pixel_compute_scale (align_corners=True), float32
+    const float sh = H > 1 ? (float)(gh - 1) / (float)(H - 1) : 0.0f, sw = W > 1 ? (float)(gw - 1) / (float)(W - 1) : 0.0f;
+    const int per = (int)(vec ? W / 4 : W), threads = per >= 256 ? 256 : (per + 63) / 64 * 64;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(bt::k_ga_scaled_dmaps<true>, dim3((unsigned)(T * H)), dim3(threads), lds, st, dmaps, frame_scales, frame_shifts, out,
+                           (int)H, (int)W, (int)gh, (int)gw, sh, sw);
+    else
+        hipLaunchKernelGGL(bt::k_ga_scaled_dmaps<false>, dim3((unsigned)(T * H)), dim3(threads), lds, st, dmaps, frame_scales, frame_shifts, out,
+                           (int)H, (int)W, (int)gh, (int)gw, sh, sw);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}

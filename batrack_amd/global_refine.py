@@ -95,6 +95,7 @@ class RefineLosses:
         self._mono_scaled = torch.empty(self.T, self.N, self.S_local, device=dev, dtype=torch.float32)
         self._losses = torch.zeros(5, device=dev, dtype=torch.float64)
         self._g_ms = None
+        self.dmaps, self.results, self._result_dtypes = None, None, None       # set by from_results
 
     # ------------------------------------------------------------------ the hand-off from the sparse-SLAM stage
     @classmethod
@@ -162,6 +163,8 @@ class RefineLosses:
                   refine_intrinsics=refine_intrinsics, K_scale=K_scale)
         net.trajs_valid = f("trajs_valid")
         net.results = results
+        net.dmaps = dmaps.view(T, 1, H, W)                 # RefineNet.dmaps ([T,1,H,W], after align_depth), for scaled_dmaps
+        net._result_dtypes = {k: np.asarray(results[k]).dtype for k in ("trajs_2d_disp", "dmaps", "cams_T_world", "intrinsics")}
         return net
 
     @property
@@ -187,6 +190,39 @@ class RefineLosses:
             setattr(a, n, t.data_ptr())
         a.pw_break, a.half_disp = self.pw_break, 1 if self.half_disp else 0
         return a
+
+    # ------------------------------------------------------------------ the stage's output (refine_net.py:394-416)
+    @property
+    def scaled_dmaps(self):
+        """RefineNet.scaled_dmaps: dmaps / (F.interpolate(exp(frame_scales_ / 10), (H, W), bilinear, align_corners=True)
+        + frame_shifts_ * dmaps), [T,1,H,W] float32, by bt_ga_scaled_dmaps.  A new tensor outside autograd (the reference
+        only ever reads it detached)."""
+        if self.dmaps is None:
+            raise RuntimeError("RefineLosses.scaled_dmaps: no depth maps (build the object with RefineLosses.from_results)")
+        gh, gw = self.frame_scales_.shape[1:]
+        out = torch.empty_like(self.dmaps)
+        st = torch.cuda.current_stream(self.dmaps.device).cuda_stream
+        _lib.check(self._lib.bt_ga_scaled_dmaps(self.dmaps.data_ptr(), self.frame_scales_.data_ptr(), self.frame_shifts_.data_ptr(),
+                                                out.data_ptr(), self.T, gh, gw, self.H, self.W, st), "bt_ga_scaled_dmaps")
+        return out
+
+    def get_results(self):
+        """RefineNet.get_results (refine_net.py:394-406): the results dictionary from_results was given, updated in place and
+        returned, with `final_trajs_2d` [T,N,S,2], `dmaps` and `dmaps_scaled` [T,1,H,W], `cams_T_world` [T,4,4] (`pose`
+        through SE3.matrix()) and `intrinsics` [T,4].  Each array has the dtype of the input array it derives from
+        (trajs_2d_disp, dmaps, cams_T_world, intrinsics), as the reference's do; the values are computed in float32."""
+        if self.results is None:
+            raise RuntimeError("RefineLosses.get_results: no results dictionary (build the object with RefineLosses.from_results)")
+        from .backend.lietorch import SE3
+        dt = self._result_dtypes
+        host = lambda t, k: t.detach().cpu().numpy().astype(dt[k])
+        res = self.results
+        res["final_trajs_2d"] = host(self.trajs_2d, "trajs_2d_disp")
+        res["dmaps"] = host(self.dmaps, "dmaps")
+        res["dmaps_scaled"] = host(self.scaled_dmaps, "dmaps")
+        res["cams_T_world"] = host(SE3(self.pose.detach().contiguous()).matrix(), "cams_T_world")
+        res["intrinsics"] = host(self.intrinsics, "intrinsics")
+        return res
 
     # ------------------------------------------------------------------ the total and its weights
     def weights(self, alpha=None):
@@ -310,3 +346,160 @@ class _TotalLoss(torch.autograd.Function):
         need = ctx.needs_input_grad
         return (g["trajs_scales"] * gout if need[0] else None, g["frame_scales_"] * gout if need[1] else None,
                 g["pose"] * gout if need[2] else None, g["K"] * gout if need[3] else None, None, None)
+
+
+# ---------------------------------------------------------------------- the reference's optimisation loop (model/trainer.py)
+def cosine_schedule(t, lr_start, lr_end):
+    """trainer.py:5-7."""
+    import numpy as np
+    assert 0 <= t <= 1
+    return lr_end + (lr_start - lr_end) * (1 + np.cos(t * np.pi)) / 2
+
+
+def linear_schedule(t, lr_start, lr_end):
+    """trainer.py:10-12."""
+    assert 0 <= t <= 1
+    return lr_start + (lr_end - lr_start) * t
+
+
+def adjust_learning_rate_by_lr(optimizer, lr):
+    """trainer.py:15-20: the learning rate written into every parameter group (times its `lr_scale`, if it has one)."""
+    for param_group in optimizer.param_groups:
+        if "lr_scale" in param_group:
+            param_group["lr"] = lr * param_group["lr_scale"]
+        else:
+            param_group["lr"] = lr
+
+
+def global_alignment_loop(net, lr=0.01, niter=300, schedule="cosine", lr_min=1e-6, fixed_pose=False, fixed_K=False):
+    """trainer.py:23-77 over a `RefineLosses` or a `RefineNet`: Adam with betas (0.9, 0.9) over the reference's parameter groups
+    (trajs_scales and frame_scales_ at `lr`, frame_shifts_ at 0.3 lr if it requires grad, pose and K at 1e-2 unless fixed), the
+    scheduled lr written into every group at every iteration (which overrides those initial rates, as in the reference), and
+    `loss = net.loss(); loss.backward(); optimizer.step()`.  The parameters it steps are made to require grad.  Returns the
+    last iteration's loss as a float (inf for niter = 0); a module with no parameter that requires grad is returned as is."""
+    if isinstance(net, torch.nn.Module) and not any(p.requires_grad for p in net.parameters()):
+        return net
+    if schedule not in ("cosine", "linear"):
+        raise ValueError(f"bad lr {schedule=}")
+    if getattr(net, "frame_shifts_", None) is not None and net.frame_shifts_.requires_grad:
+        raise NotImplementedError("global_alignment_loop: the gradient of frame_shifts_ is not computed on the HIP path "
+                                  "(the reference never optimises it: refine_net.py:44)")
+    groups = [{"params": [net.trajs_scales], "lr": lr}, {"params": [net.frame_scales_], "lr": lr}]
+    if not fixed_pose:
+        groups.append({"params": [net.pose], "lr": 1e-2})
+    if not fixed_K:
+        groups.append({"params": [net.K], "lr": 1e-2})
+    for g in groups:
+        g["params"][0].requires_grad_(True)
+    verbose = getattr(net, "verbose", False)
+    if verbose and isinstance(net, torch.nn.Module):
+        print("Global alignement - optimizing for:")
+        print([name for name, value in net.named_parameters() if value.requires_grad])
+    optimizer = torch.optim.Adam(groups, lr=lr, betas=(0.9, 0.9))
+    loss = float("inf")
+    bar = None
+    if verbose:
+        import tqdm
+        bar = tqdm.tqdm(total=niter)
+    for n in range(niter):
+        loss, cur = global_alignment_iter(net, n, niter, lr, lr_min, optimizer, schedule)
+        if bar is not None:
+            bar.set_postfix_str(f"lr={cur:g} loss={loss:g}")
+            bar.update()
+    if bar is not None:
+        bar.close()
+    return loss
+
+
+def global_alignment_iter(net, cur_iter, niter, lr_base, lr_min, optimizer, schedule):
+    """trainer.py:63-77: one iteration; returns (loss, lr)."""
+    t = cur_iter / niter
+    if schedule == "cosine":
+        lr = cosine_schedule(t, lr_base, lr_min)
+    elif schedule == "linear":
+        lr = linear_schedule(t, lr_base, lr_min)
+    else:
+        raise ValueError(f"bad lr {schedule=}")
+    adjust_learning_rate_by_lr(optimizer, lr)
+    optimizer.zero_grad()
+    loss = net.loss()
+    loss.backward()
+    optimizer.step()
+    return float(loss.detach()), lr
+
+
+# ---------------------------------------------------------------------- RefineNet (refine_net.py:15-48) over RefineLosses
+class RefineNet(torch.nn.Module):
+    """The reference's `RefineNet` as an nn.Module over `RefineLosses.from_results`: the constructor signature of
+    refine_net.py:16, `trajs_scales`, `frame_scales_`, `pose` and `K` registered as parameters (sharing storage with the
+    kernels' arguments), forward() = the total of RefineLosses.loss(), and `frame_shifts_`, `verbose`, `results`, `dmaps`,
+    `scaled_dmaps`, `get_results()` as the reference exposes them.  Every other attribute is RefineLosses'.  Only
+    scale_mode 'exp' is implemented (the kernels apply exp(x / 10))."""
+
+    def __init__(self, device, result_path, grid_size=4, pw_break=20, verbose=True, scale_mode="exp", align_depth=False,
+                 loss_weight_dict=None, refine_intrinsics=False, alpha=0.5, scale_smoothness_weight=0.1, scale_smoothness_mode="l2"):
+        super().__init__()
+        if scale_mode != "exp":
+            raise NotImplementedError(f"RefineNet: scale_mode {scale_mode!r} is not implemented on the HIP path (only 'exp')")
+        impl = RefineLosses.from_results(result_path, device=device, grid_size=grid_size, pw_break=pw_break, align_depth=align_depth,
+                                         loss_weight_dict=loss_weight_dict, refine_intrinsics=refine_intrinsics, alpha=alpha,
+                                         scale_smoothness_weight=scale_smoothness_weight, scale_smoothness_mode=scale_smoothness_mode)
+        for name in ("trajs_scales", "frame_scales_", "pose", "K"):
+            p = torch.nn.Parameter(getattr(impl, name))
+            setattr(impl, name, p)
+            setattr(self, name, p)
+        self._impl = impl                             # (after the parameters: __getattr__ falls back to it)
+        self.device, self.verbose, self.scale_mode, self.result_path = device, verbose, scale_mode, result_path
+        self.align_depth, self.norm_pw_scale = align_depth, True
+        self.grid_size = tuple(grid_size) if isinstance(grid_size, (list, tuple)) else (grid_size, grid_size)
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            impl = self.__dict__.get("_impl")
+            if impl is None:
+                raise
+            return getattr(impl, name)
+
+    @property
+    def frame_shifts_(self):
+        return self._impl.frame_shifts_
+
+    @frame_shifts_.setter
+    def frame_shifts_(self, value):
+        self._impl.frame_shifts_ = value
+
+    @property
+    def frame_shifts(self):
+        return self._impl.frame_shifts_
+
+    @property
+    def frame_scales(self):
+        """refine_net.py:138-143 (scale_mode 'exp')."""
+        return (self.frame_scales_ / 10.0).exp()
+
+    @property
+    def results(self):
+        return self._impl.results
+
+    @results.setter
+    def results(self, value):
+        self._impl.results = value
+
+    @property
+    def intrinsics(self):
+        return self._impl.intrinsics
+
+    @property
+    def scaled_dmaps(self):
+        return self._impl.scaled_dmaps
+
+    def get_results(self):
+        return self._impl.get_results()
+
+    def loss(self):
+        return self._impl.loss()
+
+    def forward(self):
+        return self._impl.loss()

@@ -1,0 +1,45 @@
+/* batrack_depth.h — C ABI of the video-depth metrics the reference reports after its dense global alignment.
+ *
+ * Reference: main/global_refine/model/utils.py:103-116 (eval_depth), :187-201 (align_with_lstsq), :203-240
+ * (compute_errors), :253-265 (eval_depth_metric).  The reference scores a refined depth map against ground truth in numpy on
+ * the host; bt_depth_metrics does the same for one pair of arrays on the device.  Device pointers, sizes, integer status codes
+ * (include/batrack_ba.h); nothing allocates or synchronises.
+ */
+#ifndef BATRACK_DEPTH_H
+#define BATRACK_DEPTH_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define BT_DEPTH_SCALE_NONE 0
+#define BT_DEPTH_SCALE_MEDIAN 1
+#define BT_DEPTH_SCALE_LSTSQ 2
+
+/* Bytes of device workspace bt_depth_metrics needs for n elements (independent of the data); BT_EINVAL for n < 0,
+ * BT_EUNSUPPORTED for n > 2^31 - 1. */
+int64_t bt_depth_metrics_workspace_bytes(int64_t n);
+
+/* compute_errors(gt[valid], pred[valid], depth_min, depth_max, scaling) for the valid set
+ *   valid = mask & (gt > depth_min) & (gt < depth_max)          (mask NULL: every element; a nonzero byte is true)
+ * scaling BT_DEPTH_SCALE_MEDIAN: pred *= median(gt_v) / median(pred_v), numpy's median (exact selection; an even count takes
+ *   the float64 mean of the two middle elements) by radix select on the order-preserving key of the float32 values;
+ * BT_DEPTH_SCALE_LSTSQ: pred = s pred + t, (s, t) the least-squares fit of gt by [pred, 1] from float64 sums of 1, p, p^2, g,
+ *   p g; a singular system (in np.linalg.lstsq's sense, rcond = eps * max(count, 2)) gets the minimum-norm solution;
+ * BT_DEPTH_SCALE_NONE: no scaling.
+ * Then pred is clamped to [depth_min, depth_max] and every per-element operation runs in float64 on the float32 inputs.
+ * out [11] (device, float64): abs_rel, sq_rel, log10, rmse, rmse_log, a1, a2, a3 (the reference's order), then the valid count,
+ * the ratio (median) or s (lstsq) or 1, and t (lstsq) or 0.  An empty valid set gives NaN for the eight metrics (BT_OK); a NaN
+ * among the valid preds propagates as numpy propagates it.  Sums are per-workgroup float64 partials reduced in a fixed order:
+ * a call is bit-for-bit repeatable.  `workspace`: bt_depth_metrics_workspace_bytes(n) bytes, 256-byte aligned.  n > 2^31 - 1:
+ * BT_EUNSUPPORTED, checked before anything is enqueued.  Enqueued on `stream`. */
+int bt_depth_metrics(const float *gt, const float *pred, const uint8_t *mask, int64_t n, float depth_min, float depth_max,
+                     int32_t scaling, void *workspace, double *out, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* BATRACK_DEPTH_H */

@@ -100,6 +100,19 @@ int bt_ga_mat_to_se3(const float *mats, float *poses, int64_t T, void *stream);
 int bt_ga_sample_disp_mono(const float *dmaps, const float *trajs_2d, float *disp_mono_out,
                            int64_t T, int64_t N, int64_t S, int64_t H, int64_t W, void *stream);
 
+/* ---- the stage's output: RefineNet.scaled_dmaps (refine_net.py:136-143, 408-416)
+ *
+ * bt_ga_scaled_dmaps: for every frame t and pixel (y, x)  out = d / (s + frame_shifts[t] * d),  d = dmaps[t, y, x] and s the
+ * bilinear, align_corners=True upsampling to H x W of exp(frame_scales[t] / 10) (F.interpolate).  Source coordinate and lerp
+ * in float32 in the order of PyTorch's upsample_bilinear2d: scale = (g - 1) / (n - 1) (0 when n == 1), src = scale * i,
+ * i0 = (int)src, i1 = i0 + (i0 < g - 1), l = src - i0.  dmaps, out [T,H,W] float32 (out may not alias dmaps); frame_scales
+ * [T,gh,gw] raw, as bt_ga_args holds it; frame_shifts [T].  One pass over the maps, 16-byte accesses where W % 4 == 0.
+ * Size limits, checked before anything is enqueued: T * H <= 2^31 - 1 and gw <= BT_GA_MAX_GRID_W (two grid rows are
+ * staged in LDS), else BT_EUNSUPPORTED.  Enqueued on `stream`. */
+#define BT_GA_MAX_GRID_W 8192
+int bt_ga_scaled_dmaps(const float *dmaps, const float *frame_scales, const float *frame_shifts, float *out,
+                       int64_t T, int64_t gh, int64_t gw, int64_t H, int64_t W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

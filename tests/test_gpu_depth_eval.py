@@ -1,0 +1,317 @@
+"""-m gpu: the output of the dense global-alignment stage and its depth metrics on the HIP kernels.
+  bt_depth_metrics     against the unmodified reference's compute_errors / eval_depth_metric (tests/golden/depth_eval.npz), numpy's
+                       median bit for bit, and the numpy restatement of tests/depth_util.py at the Sintel size
+  bt_ga_scaled_dmaps   against the reference's RefineNet.scaled_dmaps (fixture) and F.interpolate on the device
+  the loop             global_alignment_loop against 20 iterations of the reference's (fixture)
+  end to end           WindowedBA -> results -> RefineLosses.from_results -> loop -> eval_depth, and the reference's
+                       eval_sintel_depth.py body through the `model.*` names of integration/global_refine.
+Gates: with median or no scaling a1/a2/a3 exactly the fixture's (the same float64 thresholds on the same float32 inputs); with
+lstsq within one element's share (SVD and the normal equations round s and t differently); the other five metrics 1e-9
+relative (float64 sums in another order)."""
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from depth_util import np_depth_metrics
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+D = dict(np.load(os.path.join(ROOT, "tests", "golden", "depth_eval.npz")))
+NAMES = [str(n) for n in D["ce.names"]]
+SCALING = {0: "none", 1: "median", 2: "lstsq"}
+DEV = "cuda:0"
+RUN_WEIGHTS = {"spatial_loss": 5.0, "inter_frame_loss": 0.3, "pts_3d_loss": 1.0, "cam_smooth_vec_loss": 1.0, "scale_smoothness_loss": 0.3}
+
+
+def case(name):
+    kg, kp, km = (str(k) for k in D[f"ce.{name}.inputs"])
+    dmin, dmax = D[f"ce.{name}.limits"]
+    return D[f"ce.in.{kg}"], D[f"ce.in.{kp}"], D[f"ce.in.{km}"], float(dmin), float(dmax), SCALING[int(D[f"ce.{name}.scaling"])]
+
+
+def metrics(gt, pred, mask=None, dmin=1e-2, dmax=1e2, scaling="median"):
+    from batrack_amd.evaluation import depth_metrics
+    t = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32), device=DEV)
+    m = None if mask is None else (mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask, bool), device=DEV))
+    return depth_metrics(t(gt), t(pred), m, dmin, dmax, scaling)
+
+
+def check_gates(r, ref, count, scaling):
+    assert r[8] == count
+    np.testing.assert_allclose(r[:5], ref[:5], rtol=1e-9)
+    tol = 1.0 / count if scaling == "lstsq" else 0.0
+    assert np.abs(r[5:8] - ref[5:8]).max() <= tol, (r[5:8], ref[5:8])
+
+
+# ---------------------------------------------------------------------- bt_depth_metrics
+@pytest.mark.parametrize("name", NAMES)
+def test_metrics_match_the_reference_fixture(name):
+    gt, pred, mask, dmin, dmax, scaling = case(name)
+    r, ref, aux = metrics(gt, pred, mask, dmin, dmax, scaling), D[f"ce.{name}.metrics"], D[f"ce.{name}.aux"]
+    check_gates(r, ref, aux[0], scaling)
+    if scaling == "median":
+        assert abs(r[9] - aux[1]) <= np.spacing(aux[1]), (r[9], aux[1])
+    elif scaling == "lstsq":
+        np.testing.assert_allclose(r[9:11], aux[1:3], rtol=1e-9)
+
+
+def test_the_reference_entry_points_on_numpy_inputs():
+    from batrack_amd.evaluation import compute_errors, eval_depth_metric
+    gt, pred, mask, dmin, dmax, scaling = case("median_even")
+    res = eval_depth_metric(gt.astype(np.float64), {"final": pred.astype(np.float64)}, mask, exp_name="t", depth_min=dmin, depth_max=dmax)
+    n_valid = D["ce.median_even.aux"][0]
+    check_gates(np.concatenate([res["final"], [n_valid]]), D["ce.median_even.metrics"], n_valid, scaling)
+    v = mask & (gt > dmin) & (gt < dmax)
+    ce = np.array(compute_errors(gt[v], pred[v].copy(), dmin, dmax, scaling="median"))
+    check_gates(np.concatenate([ce, [v.sum()]]), D["ce.median_even.metrics"], D["ce.median_even.aux"][0], scaling)
+    with pytest.raises(ValueError, match="not inside"):
+        compute_errors(gt, pred, dmin, dmax)                           # gt outside the limits: the reference never passes such
+    r = eval_depth_metric(gt, {"final": pred}, mask, depth_min=dmin, depth_max=dmax, scaling="something else")   # no scaling
+    check_gates(np.concatenate([r["final"], [n_valid]]), D["ce.none_even.metrics"], n_valid, "none")          # (the same inputs)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 1_000_001, (1 << 24) + 3])
+@pytest.mark.parametrize("kind", ["normal", "equal", "tied"])
+def test_median_selection_is_numpy_median_bit_for_bit(n, kind):
+    """gt = 1 and pred = x: the ratio is 1 / median(x); gt = x and pred = 1: median(x).  Negative values included."""
+    g = torch.Generator(device=DEV).manual_seed(n + len(kind))
+    if kind == "normal":
+        x = torch.randn(n, generator=g, device=DEV)
+    elif kind == "equal":
+        x = torch.full((n,), -2.5, device=DEV)
+    else:
+        x = torch.randint(-3, 4, (n,), generator=g, device=DEV).float() * 0.75
+    ones = torch.ones(n, device=DEV)
+    xh = x.cpu().numpy().astype(np.float64)
+    med = np.median(xh)
+    big = 3e38
+    r = metrics(x, ones, None, -big, big)
+    assert r[8] == n and r[9] == med, (r[9], med)
+    x2 = x.abs() + 0.5                                                # a pred median of 0 would make the ratio inf
+    r = metrics(ones, x2, None, -big, big)
+    assert r[9] == 1.0 / np.median(x2.cpu().numpy().astype(np.float64))
+
+
+def test_repeatable_empty_and_nan():
+    rng = np.random.default_rng(3)
+    gt = np.exp(rng.uniform(-1, 3, 300_001)).astype(np.float32)
+    pred = (gt * np.exp(0.3 * rng.standard_normal(gt.size))).astype(np.float32)
+    for s in ("median", "lstsq", "none"):
+        a, b = metrics(gt, pred, scaling=s), metrics(gt, pred, scaling=s)
+        assert a.tobytes() == b.tobytes()
+    r = metrics(gt, pred, np.zeros(gt.size, bool))
+    assert r[8] == 0 and np.isnan(r[:8]).all()
+    r = metrics(gt, pred, None, 1e3, 1e4)
+    assert r[8] == 0 and np.isnan(r[:8]).all()
+    bad = pred.copy()
+    bad[1234] = np.nan
+    for s in ("median", "none"):
+        r, ref = metrics(gt, bad, scaling=s), np_depth_metrics(gt, bad, scaling=s)
+        assert np.isnan(r[:5]).all() and np.isnan(ref[:5]).all()
+        np.testing.assert_array_equal(r[5:8], ref[5:8])                # numpy's counts: NaN is never below a threshold
+
+
+def test_sintel_size_against_numpy():
+    T, H, W = 50, 436, 1024
+    g = torch.Generator(device=DEV).manual_seed(7)
+    gt = torch.exp(torch.rand(T, H, W, generator=g, device=DEV) * 6.0 - 1.5)
+    pred = gt * 0.4 * torch.exp(0.3 * torch.randn(T, H, W, generator=g, device=DEV))
+    mask = torch.rand(T, H, W, generator=g, device=DEV) < 0.9
+    gh, ph, mh = gt.cpu().numpy(), pred.cpu().numpy(), mask.cpu().numpy()
+    for s in ("median", "lstsq"):
+        r, ref = metrics(gt, pred, mask, scaling=s), np_depth_metrics(gh, ph, mh, scaling=s)
+        check_gates(r, ref, ref[8], s)
+        if s == "median":
+            assert r[9] == ref[9]
+
+
+# ---------------------------------------------------------------------- bt_ga_scaled_dmaps
+def scaled(dm, fs, sh):
+    from batrack_amd import _lib
+    T, _, H, W = dm.shape
+    out = torch.empty_like(dm)
+    _lib.check(_lib.lib().bt_ga_scaled_dmaps(dm.data_ptr(), fs.data_ptr(), sh.data_ptr(), out.data_ptr(), T, fs.shape[1], fs.shape[2],
+                                             H, W, torch.cuda.current_stream().cuda_stream), "bt_ga_scaled_dmaps")
+    return out
+
+
+def torch_scaled(dm, fs, sh):
+    import torch.nn.functional as F
+    s = F.interpolate((fs / 10.0).exp()[:, None], size=dm.shape[-2:], mode="bilinear", align_corners=True)
+    return dm / (s + sh.view(-1, 1, 1, 1) * dm)
+
+
+@pytest.mark.parametrize("tag", ["g44", "g35"])
+def test_scaled_dmaps_match_the_reference_fixture(tag):
+    t = lambda k: torch.as_tensor(D[k], device=DEV)
+    out = scaled(t("sd.dmaps"), t(f"sd.{tag}.frame_scales_"), t(f"sd.{tag}.frame_shifts_")).cpu().numpy().astype(np.float64)
+    ref = D[f"sd.{tag}.scaled"].astype(np.float64)
+    assert np.abs(out / ref - 1).max() < 1e-6
+
+
+@pytest.mark.parametrize("T,H,W,gh,gw", [(3, 40, 64, 4, 4), (2, 33, 37, 3, 5), (2, 1, 64, 4, 4), (2, 17, 1, 4, 4), (1, 1, 1, 3, 3),
+                                         (2, 9, 13, 12, 40), (1, 20, 44, 1, 1), (2, 436, 1024, 12, 12)])
+def test_scaled_dmaps_match_f_interpolate_on_the_device(T, H, W, gh, gw):
+    g = torch.Generator(device=DEV).manual_seed(T * H * W)
+    dm = torch.rand(T, 1, H, W, generator=g, device=DEV) * 10 + 0.5
+    fs = torch.randn(T, gh, gw, generator=g, device=DEV) * 2
+    sh = torch.rand(T, generator=g, device=DEV) * 0.08 - 0.03
+    out, ref = scaled(dm, fs, sh), torch_scaled(dm, fs, sh)
+    assert float((out / ref - 1).abs().max()) < 1e-6
+    odd = torch.empty(T * H * W + 1, device=DEV)[1:].view(T, 1, H, W)   # a map that does not start on 16 bytes: the scalar path
+    odd.copy_(dm)
+    assert float((scaled(odd, fs, sh) / ref - 1).abs().max()) < 1e-6
+
+
+# ---------------------------------------------------------------------- get_results, the loop
+def ga_init_results():
+    G = dict(np.load(os.path.join(ROOT, "tests", "golden", "ga_init.npz"), allow_pickle=False))
+    res = {k[3:]: v for k, v in G.items() if k.startswith("in.")}
+    res.update(rgbs=None, dmaps_gt=None)
+    return res
+
+
+def test_get_results_has_the_reference_keys_shapes_and_dtypes():
+    from batrack_amd.global_refine import RefineLosses
+    res = ga_init_results()
+    cams, dmaps_in = np.array(res["cams_T_world"]), np.array(res["dmaps"])
+    net = RefineLosses.from_results(res, DEV, grid_size=(3, 5), loss_weight_dict=RUN_WEIGHTS, refine_intrinsics=True)
+    T, N, S, _ = res["trajs_2d_disp"].shape
+    H, W = res["dmaps"].shape[1:3]
+    out = net.get_results()
+    assert out is res
+    want = dict(final_trajs_2d=((T, N, S, 2), res["trajs_2d_disp"].dtype), dmaps=((T, 1, H, W), res["dmaps"].dtype),
+                dmaps_scaled=((T, 1, H, W), res["dmaps"].dtype), cams_T_world=((T, 4, 4), cams.dtype), intrinsics=((T, 4), res["intrinsics"].dtype))
+    for k, (shape, dt) in want.items():
+        assert out[k].shape == shape and out[k].dtype == dt, (k, out[k].shape, out[k].dtype)
+    assert np.abs(out["cams_T_world"] - cams).max() < 1e-6
+    # at the initial parameters (scales exp(1 / 10), no shift) the refined map is the map over exp(0.1)
+    np.testing.assert_allclose(out["dmaps_scaled"], out["dmaps"] / np.exp(0.1), rtol=1e-6)
+    np.testing.assert_allclose(out["dmaps"][:, 0], dmaps_in[..., 0], rtol=1e-7)
+    np.testing.assert_array_equal(out["intrinsics"], np.tile(net.K.cpu().numpy() * np.float32(20.0), (T, 1)))   # K * K_scale, every frame
+
+
+@pytest.mark.parametrize("tag,fixed", [("free", False), ("fixed", True)])
+def test_loop_matches_the_reference_loop(tag, fixed, monkeypatch):
+    from batrack_amd import global_refine as gr
+    d = {k[8:]: v for k, v in D.items() if k.startswith("loop.in.")}
+    t = lambda k: torch.as_tensor(np.asarray(d[k]), device=DEV)
+    net = gr.RefineLosses(t("trajs_2d"), t("trajs_disp"), t("trajs_disp_mono"), t("trajs_vis"), t("trajs_static"), t("jj"),
+                          t("intrinsics"), t("grid_query_frames"), t("trajs_scales"), t("frame_scales_"), t("frame_shifts"), t("pose"),
+                          int(d["H"]), int(d["W"]), float(d["pw_break"]), loss_weight_dict=RUN_WEIGHTS, refine_intrinsics=True,
+                          alpha=0.5, scale_smoothness_weight=0.1)
+    lrs, losses = [], []
+    inner = gr.adjust_learning_rate_by_lr
+
+    def rec(opt, lr):
+        lrs.append(lr)
+        inner(opt, lr)
+    monkeypatch.setattr(gr, "adjust_learning_rate_by_lr", rec)
+    it = gr.global_alignment_iter
+
+    def rec_iter(*a, **k):
+        out = it(*a, **k)
+        losses.append(out[0])
+        return out
+    monkeypatch.setattr(gr, "global_alignment_iter", rec_iter)
+    last = gr.global_alignment_loop(net, lr=1e-2, niter=20, schedule="cosine", lr_min=1e-6, fixed_pose=fixed, fixed_K=fixed)
+    assert lrs == list(D[f"loop.{tag}.lr"])
+    ref = D[f"loop.{tag}.loss"]
+    assert last == losses[-1] and max(abs(a / b - 1) for a, b in zip(losses, ref)) < 2e-3, (losses, ref)
+    pose, K = net.pose.detach().cpu().numpy(), net.K.detach().cpu().numpy()
+    assert np.abs(pose - D[f"loop.{tag}.pose"]).max() < 2e-3
+    assert np.abs(K - D[f"loop.{tag}.K"]).max() < 2e-3 * np.abs(D[f"loop.{tag}.K"]).max()
+    a, b = net.trajs_scales.detach().cpu().numpy(), D[f"loop.{tag}.trajs_scales"]
+    assert np.linalg.norm(a - b) / np.linalg.norm(b) < 2e-3
+    # the scale grid starts flat: the l1 smoothness term's gradient is sign(a - b) of neighbours that differ by rounding after the
+    # first step, and Adam normalises it to a full lr step whichever the sign — the float32 and float64 grids part by ~0.5 % of
+    # their norm within 20 iterations while the losses agree to 2e-3
+    a, b = net.frame_scales_.detach().cpu().numpy(), D[f"loop.{tag}.frame_scales_"]
+    assert np.linalg.norm(a - b) / np.linalg.norm(b) < 1e-2
+    if fixed:
+        assert np.array_equal(pose, np.asarray(d["pose"], np.float32))
+
+
+# ---------------------------------------------------------------------- end to end
+def sequence_results(tmp_path):
+    from batrack_amd import graphgen
+    from batrack_amd.backend.ba import BA_rgbd_droid
+    from batrack_amd.sequence import SlamConfig, SyntheticObservations, WindowedBA
+    cam = dict(graphgen.SINTEL, wd=256, ht=112, cx=128.0, cy=56.0, fx=125.0, fy=125.0)
+    n_frames, M = 20, 48
+    obs = SyntheticObservations(n_frames=n_frames, M=M, seed=5, cam=cam)
+    cfg = SlamConfig(PATCHES_PER_FRAME=M, BUFFER_SIZE=n_frames + 1, num_init=6, init_updates=6, ITER=2, OPTIMIZATION_WINDOW=8, REMOVAL_WINDOW=10, S_slam=6)
+    trk = WindowedBA(obs, BA_rgbd_droid, cfg, device=DEV)
+    trk.run()
+    rng = np.random.default_rng(2)
+    gt = [obs.depth_map(f) for f in range(n_frames)]
+    mono = [d * 1.3 * (1 + 0.05 * rng.standard_normal(d.shape)) for d in gt]      # a mono-depth estimate: scaled and noisy
+    path = str(tmp_path / "results.pkl")
+    trk.get_results(dmaps=mono, dmaps_gt=gt, save_path=path)
+    return path
+
+
+def test_sequence_to_refined_depth_metrics(tmp_path):
+    from batrack_amd.evaluation import eval_depth
+    from batrack_amd.global_refine import RefineLosses, global_alignment_loop
+    path = sequence_results(tmp_path)
+    weights = {"spatial_loss": 5.0, "inter_frame_loss": 0.3, "pts_3d_loss": 1.0}                   # eval_sintel_depth.py
+    net = RefineLosses.from_results(path, DEV, grid_size=12, align_depth=True, loss_weight_dict=weights)
+    l0 = float(net.loss())
+    last = global_alignment_loop(net, niter=20)
+    assert np.isfinite(last) and last < l0
+    res = eval_depth(net)["final"]
+    assert res.shape == (8,) and np.isfinite(res).all()
+    gt = np.asarray(net.results["dmaps_gt"])[..., 0]
+    pred = net.scaled_dmaps[:, 0].cpu().numpy()
+    g32 = gt.astype(np.float32)
+    ref = np_depth_metrics(g32, pred, (g32 > np.float32(1e-2)) & (g32 < np.float32(1e2)))
+    check_gates(np.concatenate([res, [ref[8]]]), ref, ref[8], "median")
+    out = net.get_results()
+    assert out["dmaps_scaled"].shape == (gt.shape[0], 1) + gt.shape[1:] and out["dmaps_scaled"].dtype == np.float64
+
+
+SCRIPT = r"""
+import os, sys, pickle
+import numpy as np, torch
+from model.refine_net import RefineNet
+from model.trainer import global_alignment_loop
+from model.utils import eval_depth
+result_dir, scene = sys.argv[1], sys.argv[2]
+# eval_sintel_depth.py:test_all, one scene, niter 20
+loss_weight_dict = {'spatial_loss': 5.0, 'inter_frame_loss': 0.3, 'pts_3d_loss': 1.0}
+device = torch.device('cuda')
+result_path = os.path.join(result_dir, scene, 'results.pkl')
+refine_net = RefineNet(device=device, result_path=result_path, scale_mode='exp', grid_size=12, align_depth=True,
+                       loss_weight_dict=loss_weight_dict, refine_intrinsics=False, verbose=False)
+refine_net.to(device)
+global_alignment_loop(refine_net, lr=1e-2, niter=20, schedule='cosine', lr_min=1e-6, fixed_pose=True, fixed_K=True)
+results = eval_depth(refine_net, depth_min=1e-2, depth_max=1e2, scaling='median', scene_name=scene)
+print('final', *[f'{results["final"][i]:.6f}' for i in (0, 5, 6, 7)])
+# run_global_refine.py:test_all's output
+with open(os.path.join(result_dir, scene, 'results_refined.pkl'), 'wb+') as f:
+    pickle.dump(refine_net.get_results(), f)
+"""
+
+
+def test_reference_scripts_through_the_model_names(tmp_path):
+    scene = tmp_path / "alley_2"
+    scene.mkdir()
+    src = sequence_results(tmp_path)
+    os.replace(src, scene / "results.pkl")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "integration", "global_refine"), ROOT]))
+    r = subprocess.run([sys.executable, "-c", SCRIPT, str(tmp_path), "alley_2"], capture_output=True, text=True, env=env,
+                       cwd=str(tmp_path), timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [x for x in r.stdout.splitlines() if x.startswith("final")][-1].split()
+    vals = np.array([float(x) for x in line[1:]])
+    assert np.isfinite(vals).all() and 0 <= vals[1] <= vals[2] <= vals[3] <= 1
+    with open(scene / "results_refined.pkl", "rb") as f:
+        out = pickle.load(f)
+    for k in ("final_trajs_2d", "dmaps", "dmaps_scaled", "cams_T_world", "intrinsics", "dmaps_gt", "trajs_2d_disp"):
+        assert k in out
