@@ -328,7 +328,7 @@ static StepArgs make_args(const bt_plan *pl, const bt_ba_args *a, void *ws) {
     s.S = reinterpret_cast<double *>(w + L.sys); s.y = s.S + D * D;
     s.pairacc = reinterpret_cast<double *>(w + L.pairacc);
     // (k_edge2's private copies: only where k_edge2 is the plan's Jacobian kernel — k_pair_finalize adds up what it is given)
-    s.priv = L.priv && edge_applies(pl->dev) ? reinterpret_cast<double *>(w + L.priv) : nullptr;
+    s.priv = L.priv && pl->dev.route.kernel == Route::kEdge ? reinterpret_cast<double *>(w + L.priv) : nullptr;
     s.pairgeo = reinterpret_cast<float *>(w + L.pairgeo);
     s.packed = reinterpret_cast<double *>(w + L.packed); s.qw = reinterpret_cast<float2 *>(w + L.qw);
     s.lfac = reinterpret_cast<float *>(w + L.lfac);
@@ -338,7 +338,7 @@ static StepArgs make_args(const bt_plan *pl, const bt_ba_args *a, void *ws) {
     s.esave = reinterpret_cast<double *>(w + L.esave);
     static const int dbg = std::getenv("BT_DEBUG_MODE") ? std::atoi(std::getenv("BT_DEBUG_MODE")) : 0;
     s.dbg = dbg;
-    s.prec = edge_precision(pl->dev);
+    s.prec = pl->dev.route.prec == 8 ? 1 : 0;
     return s;
 }
 
@@ -377,14 +377,13 @@ extern "C" {
 int bt_version(void) { return BT_VERSION; }
 int bt_plan_jacobian_kernel(const bt_plan *pl) {
     if (!pl || !pl->dev_base) return -1;
-    return edge_applies(pl->dev) ? 2 : stream_applies(pl->dev) ? 1 : etile_precision_bytes(pl->dev) ? 3 : 0;
+    return pl->dev.route.kernel;
 }
 int bt_plan_built_on_device(const bt_plan *pl) { return pl && (pl->dev_pm || pl->dev_slots) ? 1 : 0; }
 
 int bt_plan_edge_precision(const bt_plan *pl) {
     if (!pl || !pl->dev_base) return -1;
-    if (edge_precision(pl->dev)) return 8;
-    return (pl->dev.T > 0 && (edge_applies(pl->dev) || stream_applies(pl->dev))) ? 6 : 4;     // 6: mixed (ba_edge.hpp: edge_eval_mixed)
+    return pl->dev.route.prec;                      // 6: mixed (ba_edge.hpp: edge_eval_mixed)
 }
 const char *bt_target_arch(void) { return "gfx950"; }
 
@@ -775,8 +774,8 @@ int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
         *data = pl->dev_readback.data();
         return 4;
     }
-    if (std::strcmp(name, "solver_mode") == 0) {              // 0 .. 3 (ba_kernels.hpp: solver_mode), -1 for a host-only plan
-        pl->dev_readback.assign(1, pl->dev_base ? (int32_t)solver_mode(pl->dev) : -1);
+    if (std::strcmp(name, "solver_mode") == 0) {              // 0 .. 3 (ba_plan.hpp: Route), -1 for a host-only plan
+        pl->dev_readback.assign(1, pl->dev_base ? (int32_t)(pl->dev.route.solver >= Route::kSolveFused ? Route::kSolveLds : pl->dev.route.solver) : -1);
         *data = pl->dev_readback.data();
         return 1;
     }
@@ -841,7 +840,7 @@ int bt_ba_reduce(const bt_plan *pl, const bt_ba_args *a, void *ws, void *stream)
     if (rc != BT_OK) return rc;
     const StepArgs s = make_args(pl, a, ws);
     mark_launch(pl, stream);
-    return launch_reduce(pl->dev, s, pl->ws.zero_bytes / sizeof(double), is_so(pl, a), static_cast<hipStream_t>(stream));
+    return launch_reduce(pl->dev, s, is_so(pl, a), static_cast<hipStream_t>(stream));
 }
 
 int bt_ba_solve_update(const bt_plan *pl, const bt_ba_args *a, void *ws, void *stream) {
@@ -866,7 +865,7 @@ int bt_ba_step(const bt_plan *pl, const bt_ba_args *a, void *ws, void *stream) {
     const StepArgs s = make_args(pl, a, ws);
     const bool copy_poses = so && a->poses_out && a->poses_out != a->poses;
     bool fused = false;              // (structure-only steps on the k_tile path are one launch)
-    int r = launch_reduce(pl->dev, s, pl->ws.zero_bytes / sizeof(double), so, st, nullptr, nullptr, so ? (copy_poses ? 1 : 0) : -1, &fused);
+    int r = launch_reduce(pl->dev, s, so, st, nullptr, nullptr, so ? (copy_poses ? 1 : 0) : -1, &fused);
     if (r == BT_OK && !fused) r = launch_solve_update(pl->dev, s, so, copy_poses, st);
     return r;
 }
@@ -883,7 +882,7 @@ int bt_ba_step_timed(const bt_plan *pl, const bt_ba_args *a, void *ws, void *str
     const StepArgs s = make_args(pl, a, ws);
     const bool copy_poses = so && a->poses_out && a->poses_out != a->poses;
     unsigned ran = 0;
-    int r = launch_reduce(pl->dev, s, pl->ws.zero_bytes / sizeof(double), so, st, ev, &ran);
+    int r = launch_reduce(pl->dev, s, so, st, ev, &ran);
     if (r == BT_OK) r = launch_solve_update(pl->dev, s, so, copy_poses, st, ev, &ran);
     if (r == BT_OK && hipStreamSynchronize(st) != hipSuccess) r = BT_EHIP;
     for (int k = 0; k < 6; ++k) {

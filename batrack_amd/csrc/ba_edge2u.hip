@@ -314,15 +314,6 @@ static int launch_u(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEve
 
 }  // namespace e2
 
-// k_edge2 / k_edge2u take graphs of many tiles, all slot-uniform (the plan's em_ok), whose tiles see at most 10 cameras (row
-// tiles of the Schur product) and 64 camera pairs (one lane per pair in the prologue).
-// Measured on the benchmark generator (whole-step times; profiles/r02_kernel_choice.txt, r05_edge2_vs_edge.txt): k_tile is
-// fastest up to ~1500 tiles; from 2048 tiles k_edge2 where the tiles are slot-uniform (whole step 122 against k_stream's 130 us at
-// 2048 tiles, 151 against 160 at 4096), k_stream otherwise (tiles of more than 64 slots: the edge-major layout does not hold them).
-bool edge_applies(const PlanDev &pd) {
-    return pd.em_ok && pd.T >= pd.em_min && pd.max_cams <= 10 && pd.max_cams > 0 && pd.max_tile_pairs <= 64 && pd.max_tile_pairs > 0;
-}
-
 // mode 0: the pose+structure reduce (k_edge2), 1: structure-only, 2: a pose+structure step's depth back-substitution (k_edge2u)
 int launch_edge(const PlanDev &pd, const StepArgs &a, int mode, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     if ((unsigned long long)pd.e_all * (unsigned long long)a.tstride * 4ull >= (1ull << 32)) return BT_EUNSUPPORTED;   // 32-bit byte offsets into the targets

@@ -624,15 +624,6 @@ static size_t etile_lds_bytes(const PlanDev &pd, int mode, size_t rsz) {
     return etile_full_lds_bytes(pd.max_rows16, pd.max_tile_pairs, rsz);
 }
 
-constexpr size_t kEtLdsBudget = kEtileLdsBudget;
-
-// 8: the tiles' E fits LDS as double, 4: only as float, 0: k_etile does not take this plan
-int etile_precision_bytes(const PlanDev &pd) {
-    if (pd.pm_ok != 2 || pd.T <= 0 || edge_applies(pd) || stream_applies(pd)) return 0;
-    if (etile_lds_bytes(pd, kEtFull, sizeof(double)) <= kEtLdsBudget) return 8;
-    return 0;                       // (k_tile then decides: float64 if ITS tile fits LDS as double, else float32)
-}
-
 template <int MODE, typename R, bool PROF = false, bool TWO = false>
 static int launch_etile_t(const PlanDev &pd, const StepArgs &a, int do_poses, int extra_blocks, int zero_blocks, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     const size_t lds = etile_lds_bytes(pd, MODE, sizeof(R));
@@ -659,11 +650,8 @@ int launch_etile(const PlanDev &pd, const StepArgs &a, int mode, int do_poses, i
     if (mode == kEtSO) return dbl ? launch_etile_t<kEtSO, double>(pd, a, do_poses, extra_blocks, 0, st, ev0, ev1) : launch_etile_t<kEtSO, float>(pd, a, do_poses, extra_blocks, 0, st, ev0, ev1);
     if (mode == kEtUpd) return dbl ? launch_etile_t<kEtUpd, double>(pd, a, do_poses, extra_blocks, zero_blocks, st, ev0, ev1) : launch_etile_t<kEtUpd, float>(pd, a, do_poses, extra_blocks, zero_blocks, st, ev0, ev1);
     // float64: two rounds per trip (both variants need more than 128 registers: one workgroup per CU either way)
-    constexpr bool two = true;
-    if ((a.dbg & 32) && dbl && two) return launch_etile_t<kEtFull, double, true, true>(pd, a, 0, 0, 0, st, ev0, ev1);
-    if (a.dbg & 32) return dbl ? launch_etile_t<kEtFull, double, true>(pd, a, 0, 0, 0, st, ev0, ev1) : launch_etile_t<kEtFull, float, true>(pd, a, 0, 0, 0, st, ev0, ev1);
-    if (dbl && two) return launch_etile_t<kEtFull, double, false, true>(pd, a, 0, 0, 0, st, ev0, ev1);
-    return dbl ? launch_etile_t<kEtFull, double>(pd, a, 0, 0, 0, st, ev0, ev1) : launch_etile_t<kEtFull, float>(pd, a, 0, 0, 0, st, ev0, ev1);
+    if (a.dbg & 32) return dbl ? launch_etile_t<kEtFull, double, true, true>(pd, a, 0, 0, 0, st, ev0, ev1) : launch_etile_t<kEtFull, float, true>(pd, a, 0, 0, 0, st, ev0, ev1);
+    return dbl ? launch_etile_t<kEtFull, double, false, true>(pd, a, 0, 0, 0, st, ev0, ev1) : launch_etile_t<kEtFull, float>(pd, a, 0, 0, 0, st, ev0, ev1);
 }
 
 }  // namespace bt

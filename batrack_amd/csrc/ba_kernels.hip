@@ -24,14 +24,13 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <utility>
-#include <vector>
 
 #include "ba_kernels.hpp"
 #include "probe.hpp"
 #include "ba_edge.hpp"
 #include "ba_update.hpp"
+#include "dev_cache.hpp"
 
 namespace bt {
 
@@ -2424,20 +2423,7 @@ int launch_xchg_pull(const PlanDev &pd, const StepArgs &a, void *own, int world,
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }
 
-// ------------------------------------------------------------------ launchers
-// 8 waves per tile; 16 for graphs of few tiles with deep slot loops (BT_FORCE wide=0 / wide=1 forces: measurement only)
-int edge_precision(const PlanDev &pd);
-static bool tile_wide(const PlanDev &pd) {
-    if (edge_precision(pd)) return false;
-    const int env = force().tile_wide;
-    if (env >= 0) return env != 0;
-    return pd.T <= 128 && pd.max_tile_slots >= 24;
-}
-// (the float64 instantiation runs 8 waves per tile whatever the graph: its slot loop wants more than the 128 registers
-// a 16-wave workgroup leaves a thread, and the window graphs' SIMDs are issue-saturated at 8 waves already)
-static int tile_threads(const PlanDev &pd) { return tile_wide(pd) ? 1024 : 512; }
-
-
+// ------------------------------------------------------------------ the plan's route
 // rsz: sizeof(R) of the k_tile instantiation
 static inline size_t tile_lds_bytes_r(const PlanDev &pd, bool so, size_t rsz, size_t kTileWaves) {
     const size_t rows = so ? 0 : (size_t)pd.max_rows16;
@@ -2445,181 +2431,171 @@ static inline size_t tile_lds_bytes_r(const PlanDev &pd, bool so, size_t rsz, si
     return (rows * kLdsRowStride + kTileWaves * 8 * 64 + 128 + mtp * kPairGeomFloats) * rsz + (kTileWaves * 64 + rows) * sizeof(int) + 64;
 }
 
-int edge_precision(const PlanDev &pd) {
-    if (force().f32_edges || pd.T <= 0 || edge_applies(pd) || stream_applies(pd)) return 0;
-    const int eb = etile_precision_bytes(pd);
-    if (eb) return eb == 8 ? 1 : 0;
-    return tile_lds_bytes_r(pd, false, sizeof(double), 8) <= kLdsBudget ? 1 : 0;
-}
+// 12 waves: enough helper threads for one round of update rows on banded systems, and a 170-register budget per thread so
+// that a whole 6x6 operand block can be in flight from LDS
+constexpr int kSolveThreads = 768;
 
-// the pair-major tile kernel takes the plan (ba_etile.hip)
-static bool etile_applies(const PlanDev &pd) { return etile_precision_bytes(pd) != 0; }
-
-static inline size_t tile_lds_bytes(const PlanDev &pd, bool so) {
-    return tile_lds_bytes_r(pd, so, edge_precision(pd) ? sizeof(double) : sizeof(float), (size_t)tile_threads(pd) / 64);
-}
-
-// 0: factor in LDS as double, 1: in LDS as float, 2: in the global workspace (float), 3: dense in the global workspace (double; wide plans)
-int solver_mode(const PlanDev &pd) {
-    if (pd.wide) return 3;                           // more than 255 free poses, or a factor too large for LDS as double: dense, in the global workspace (ba_dense.hip)
-    const int fs = force().solver;                   // (tests, measurement)
-    if (fs == 3) return 2;
-    if (fs == 2 && solve_lds_bytes(pd, sizeof(float)) <= kLdsBudget) return 1;
-    if (solve_lds_bytes(pd, sizeof(double)) <= kLdsBudget) return 0;
-    if (solve_lds_bytes(pd, sizeof(float)) <= kLdsBudget) return 1;
-    return 2;
-}
-
-static int solver_threads();
-// one-phase-per-level variant of the double LDS solver; BT_FORCE solver=lds: the two-phase k_solve_lds
-static bool use_fused_solver(const PlanDev &pd) {
-    const int fs = force().solver;
-    return fs != 1 && pd.fz_ok != 0 && solve_fused_lds_bytes(pd, solver_threads()) <= kLdsBudget;
-}
-
-// barrier-free variant of k_solve_fused; BT_FORCE solver=fused: one workgroup barrier per level
-static bool use_pipe_solver(const PlanDev &pd) {
-    const int fs = force().solver;
-    return fs < 0 && pd.fzp_ok != 0 && pd.fz_ok != 0 && solve_pipe_lds_bytes(pd) <= kLdsBudget;
-}
-
-static int solver_threads() {
-    // 12 waves: enough helper threads for one round of update rows on banded systems, and a
-    // 170-register budget per thread so that a whole 6x6 operand block can be in flight from LDS
-    return 768;
-}
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is one value per kernel for the whole process, while up to eight cached
-// plans (and the prefetch thread building the next one) coexist: the limit is only ever RAISED, under a lock, so a
-// small plan uploaded later cannot pull it below what an earlier plan launches with.
-static int raise_lds_limit(const void *fn, size_t need, int dev) {
-    struct Entry { const void *fn; int dev; size_t bytes; };
-    static std::mutex mu;
-    static std::vector<Entry> *set = new std::vector<Entry>();
-    if (need <= 48 * 1024) return BT_OK;                              // (the attribute is per device as well: `dev` = the plan's)
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto &e : *set)
-        if (e.fn == fn && e.dev == dev) {
-            if (e.bytes >= need) return BT_OK;
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need) != hipSuccess) return BT_EHIP;
-            e.bytes = need;
-            return BT_OK;
-        }
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need) != hipSuccess) return BT_EHIP;
-    set->push_back(Entry{fn, dev, need});
-    return BT_OK;
-}
-
-int configure_kernels(const PlanDev &pd) {
-    const size_t need = etile_applies(pd) ? 0 : tile_lds_bytes(pd, false);
-    if (need > kLdsBudget) return BT_EUNSUPPORTED;
-    const void *tiles[6] = { reinterpret_cast<const void *>(&k_tile<false, false>), reinterpret_cast<const void *>(&k_tile<false, false, true>),
-                             reinterpret_cast<const void *>(&k_tile<false, true>), reinterpret_cast<const void *>(&k_tile<false, true, true>),
-                             reinterpret_cast<const void *>(&k_tile<false, false, false, false, double>),
-                             reinterpret_cast<const void *>(&k_tile<false, true, false, false, double>) };
-    const bool dbl = edge_precision(pd) != 0;
-    for (int i = dbl ? 4 : 0; i < (dbl ? 6 : 4); ++i) if (raise_lds_limit(tiles[i], need, pd.dev_id) != BT_OK) return BT_EHIP;
-    if (dbl && !etile_applies(pd)) {
-        const size_t nu = ((size_t)pd.max_tile_pairs * kUpdGeo + kUpdThreads) * sizeof(double);
-        if (nu > kLdsBudget) return BT_EUNSUPPORTED;
-        if (raise_lds_limit(reinterpret_cast<const void *>(&k_update<false, kUpdThreads, double>), nu, pd.dev_id) != BT_OK) return BT_EHIP;
-        if (raise_lds_limit(reinterpret_cast<const void *>(&k_tile<true, false, false, true, double>), tile_lds_bytes(pd, true), pd.dev_id) != BT_OK ||
-            raise_lds_limit(reinterpret_cast<const void *>(&k_tile<true, false, false, false, double>), tile_lds_bytes(pd, true), pd.dev_id) != BT_OK) return BT_EHIP;
+// Which kernels the plan's steps launch: from the plan's scalars and BT_FORCE (tests, measurement) alone, once per plan.
+static Route plan_route(const PlanDev &pd) {
+    const Force &f = force();
+    Route r{};
+    // Jacobian kernel.  k_edge2 / k_edge2u take graphs of many tiles, all slot-uniform (the plan's em_ok), whose tiles see at
+    // most 10 cameras (row tiles of the Schur product) and 64 camera pairs (one lane per pair in the prologue); k_stream those
+    // whose tiles see at most 10 cameras (row tiles of its register accumulators) and 32 camera pairs (one lane per pair in the
+    // prologue, LDS of the per-pair sums).  The plan records the tile counts it was laid out for (em_min, st_min).
+    // Measured on the benchmark generator (whole-step times; profiles/r02_kernel_choice.txt, r05_edge2_vs_edge.txt): k_tile is
+    // fastest up to ~1500 tiles; from 2048 tiles k_edge2 where the tiles are slot-uniform (whole step 122 against k_stream's 130 us
+    // at 2048 tiles, 151 against 160 at 4096), k_stream otherwise (tiles of more than 64 slots: the edge-major layout does not
+    // hold them).  The pair-major k_etile takes the graphs k_tile would take that were tiled for it (pm_ok 2) when the tile's
+    // E fits LDS as double.
+    if (pd.T > 0 && pd.em_ok && pd.T >= pd.em_min && pd.max_cams <= 10 && pd.max_cams > 0 && pd.max_tile_pairs <= 64 && pd.max_tile_pairs > 0)
+        r.kernel = Route::kEdge;
+    else if (pd.T > 0 && pd.st_ok && pd.T >= pd.st_min && pd.max_cams <= 10 && pd.max_tile_pairs <= 32 && pd.max_tile_pairs > 0)
+        r.kernel = Route::kStream;
+    else if (pd.T > 0 && pd.pm_ok == 2 && etile_full_lds_bytes(pd.max_rows16, pd.max_tile_pairs, sizeof(double)) <= kEtileLdsBudget)
+        r.kernel = Route::kEtile;
+    else
+        r.kernel = Route::kTile;
+    // per-edge maths: mixed on the wave-per-tile kernels (ba_edge.hpp: edge_eval_mixed); float64 on k_etile, and on k_tile where
+    // its 8-wave tile fits LDS as double; float32 on request (BT_FORCE prec=f32)
+    if (r.kernel == Route::kEdge || r.kernel == Route::kStream) r.prec = 6;
+    else if (f.f32_edges || pd.T <= 0) r.prec = 4;
+    else r.prec = r.kernel == Route::kEtile || tile_lds_bytes_r(pd, false, sizeof(double), 8) <= kLdsBudget ? 8 : 4;
+    // k_tile runs 16 waves per tile on graphs of few tiles with deep slot loops (BT_FORCE wide=0 / wide=1 forces: measurement
+    // only).  The float64 instantiation runs 8 waves whatever the graph: its slot loop wants more than the 128 registers a
+    // 16-wave workgroup leaves a thread, and the window graphs' SIMDs are issue-saturated at 8 waves already.
+    r.wide = r.kernel == Route::kTile && r.prec == 4 && (f.tile_wide >= 0 ? f.tile_wide != 0 : pd.T <= 128 && pd.max_tile_slots >= 24);
+    // reduced solver: dense for wide plans (more than 255 free poses, or a factor too large for LDS as double: ba_dense.hip);
+    // else the factor in LDS as double where it fits, as float where that fits, else in the global workspace (both float ones
+    // refined).  Of the double ones: the barrier-free k_solve_pipe where the schedule allows it, else k_solve_fused (one
+    // workgroup barrier per level), else the two-phase k_solve_lds.  BT_FORCE solver=fused | lds | lds32 | global.
+    const int fs = f.solver;
+    if (pd.wide) r.solver = Route::kSolveDense;
+    else if (fs == 3) r.solver = Route::kSolveGlobal;
+    else if (fs == 2 && solve_lds_bytes(pd, sizeof(float)) <= kLdsBudget) r.solver = Route::kSolveLds32;
+    else if (solve_lds_bytes(pd, sizeof(double)) <= kLdsBudget) {
+        if (fs < 0 && pd.fzp_ok && pd.fz_ok && solve_pipe_lds_bytes(pd) <= kLdsBudget) r.solver = Route::kSolvePipe;
+        else if (fs != 1 && pd.fz_ok && solve_fused_lds_bytes(pd, kSolveThreads) <= kLdsBudget) r.solver = Route::kSolveFused;
+        else r.solver = Route::kSolveLds;
     }
-    const int mode = solver_mode(pd);
-    if (mode == 3) return BT_OK;                     // (the dense solver raises its own limit at launch)
-    const void *fns[4] = { reinterpret_cast<const void *>(&k_solve_lds<double, false>),
-                           reinterpret_cast<const void *>(&k_solve_lds<double, true>),
-                           reinterpret_cast<const void *>(&k_solve_lds<float, false>),
-                           reinterpret_cast<const void *>(&k_solve_lds<float, true>) };
-    if (mode < 2)
-        for (int v = 0; v < 2; ++v)
-            if (raise_lds_limit(fns[2 * mode + v], solve_lds_bytes(pd, mode == 0 ? 8 : 4), pd.dev_id) != BT_OK) return BT_EHIP;
-    if (mode == 0 && use_pipe_solver(pd))
-        if (raise_lds_limit(reinterpret_cast<const void *>(&k_solve_pipe<false>), solve_pipe_lds_bytes(pd), pd.dev_id) != BT_OK ||
-            raise_lds_limit(reinterpret_cast<const void *>(&k_solve_pipe<true>), solve_pipe_lds_bytes(pd), pd.dev_id) != BT_OK)
-            return BT_EHIP;
-    if (mode == 0 && use_fused_solver(pd))
-        if (raise_lds_limit(reinterpret_cast<const void *>(&k_solve_fused<false>), solve_fused_lds_bytes(pd, solver_threads()), pd.dev_id) != BT_OK ||
-            raise_lds_limit(reinterpret_cast<const void *>(&k_solve_fused<true>), solve_fused_lds_bytes(pd, solver_threads()), pd.dev_id) != BT_OK)
-            return BT_EHIP;
+    else if (solve_lds_bytes(pd, sizeof(float)) <= kLdsBudget) r.solver = Route::kSolveLds32;
+    else r.solver = Route::kSolveGlobal;
+    return r;
+}
+
+// ------------------------------------------------------------------ launchers
+// The k_tile (K = 1), solver (K = 3) or k_update (K = 4) instantiation of a route, its workgroup and dynamic LDS, and the LDS
+// limit kept for it (K: the kernel numbers of the event pairs below).  fn == nullptr: the route launches none of that family
+// (k_stream, k_edge2 and k_etile launch their own; so does the dense solver).
+struct Pick { const void *fn; LdsLimit *lim; int threads; size_t lds; };
+
+template <auto K> static Pick pick_of(int threads, size_t lds) {
+    static LdsLimit lim;
+    return Pick{reinterpret_cast<const void *>(K), &lim, threads, lds};
+}
+
+template <typename R, bool WIDE>
+static Pick pick_tile(const PlanDev &pd, bool so, bool fused, bool prof) {
+    constexpr int kThreads = WIDE ? 1024 : 512;
+    const size_t lds = tile_lds_bytes_r(pd, so, sizeof(R), kThreads / 64);
+    if (so && fused) return pick_of<&k_tile<true, false, WIDE, true, R>>(kThreads, lds);
+    if (so) return pick_of<&k_tile<true, false, WIDE, false, R>>(kThreads, lds);
+    if (prof) return pick_of<&k_tile<false, true, WIDE, false, R>>(kThreads, lds);
+    return pick_of<&k_tile<false, false, WIDE, false, R>>(kThreads, lds);
+}
+
+// fused: the structure-only k_tile that also does the step's update; prof: the cycle-counting variant (BT_DEBUG_MODE 32 for
+// k_tile, 16 for the solver)
+static Pick pick(const PlanDev &pd, int K, bool so, bool fused, bool prof) {
+    const Route &r = pd.route;
+    if (K == 1) {
+        if (r.kernel != Route::kTile) return Pick{};
+        if (r.prec == 8) return pick_tile<double, false>(pd, so, fused, prof);
+        return r.wide ? pick_tile<float, true>(pd, so, fused, prof) : pick_tile<float, false>(pd, so, fused, prof);
+    }
+    if (K == 4) {
+        if (so) return pick_of<&k_update<true>>(kUpdThreads, 0);
+        if (r.kernel == Route::kEtile) return Pick{};
+        const size_t geo = (size_t)pd.max_tile_pairs * kUpdGeo;
+        if (r.prec == 8) return pick_of<&k_update<false, kUpdThreads, double>>(kUpdThreads, (geo + kUpdThreads) * sizeof(double));
+        if (r.wide) return pick_of<&k_update<false, 1024>>(1024, (geo + 1024) * sizeof(float));
+        return pick_of<&k_update<false>>(kUpdThreads, (geo + kUpdThreads) * sizeof(float));
+    }
+    switch (r.solver) {
+    case Route::kSolvePipe:
+        return prof ? pick_of<&k_solve_pipe<true>>(kSolveThreads, solve_pipe_lds_bytes(pd)) : pick_of<&k_solve_pipe<false>>(kSolveThreads, solve_pipe_lds_bytes(pd));
+    case Route::kSolveFused: {
+        const size_t lds = solve_fused_lds_bytes(pd, kSolveThreads);
+        return prof ? pick_of<&k_solve_fused<true>>(kSolveThreads, lds) : pick_of<&k_solve_fused<false>>(kSolveThreads, lds);
+    }
+    case Route::kSolveLds: {
+        const size_t lds = solve_lds_bytes(pd, sizeof(double));
+        return prof ? pick_of<&k_solve_lds<double, true>>(kSolveThreads, lds) : pick_of<&k_solve_lds<double, false>>(kSolveThreads, lds);
+    }
+    case Route::kSolveLds32: {
+        const size_t lds = solve_lds_bytes(pd, sizeof(float));
+        return prof ? pick_of<&k_solve_lds<float, true>>(kSolveThreads, lds) : pick_of<&k_solve_lds<float, false>>(kSolveThreads, lds);
+    }
+    case Route::kSolveGlobal: return pick_of<&k_solve_global>(1024, 0);
+    default: return Pick{};
+    }
+}
+
+// ev: the kernel's (start, stop) event pair, or nullptr; args: exactly the kernel's parameter types
+template <typename... Args>
+static void launch_pick(const Pick &p, unsigned grid, hipStream_t st, const hipEvent_t *ev, Args... args) {
+    void *argv[] = {&args...};
+    if (ev) (void)hipExtLaunchKernel(p.fn, dim3(grid), dim3(p.threads), argv, p.lds, st, ev[0], ev[1], 0);
+    else (void)hipLaunchKernel(p.fn, dim3(grid), dim3(p.threads), argv, p.lds, st);      // (errors: hipGetLastError, as for <<< >>>)
+}
+
+int configure_kernels(PlanDev &pd) {
+    pd.route = plan_route(pd);
+    // the LDS limits of everything the route can launch, raised here at upload (never first inside a captured step); the
+    // launchers of the other kernel families raise their own
+    for (int K : {1, 3, 4})
+        for (int v = 0; v < 8; ++v) {
+            const Pick p = pick(pd, K, v & 1, v & 2, v & 4);
+            if (!p.fn) continue;
+            if (p.lds > kLdsBudget) return BT_EUNSUPPORTED;
+            if (!p.lim->ensure(p.fn, p.lds, pd.dev_id)) return BT_EHIP;
+        }
     return BT_OK;
 }
 
-// ev == nullptr: plain launches.  ev != nullptr: hipExtLaunchKernelGGL with a
-// (start, stop) event pair per kernel — ev[2*k], ev[2*k+1], k = 0 prep, 1 tile,
-// 2 pair_finalize, 3 solve, 4 update, 5 the depth walk of the wave-per-tile plans — so bench.py can read each kernel's own
-// duration on the stream it ran on.
-#define BT_LAUNCH(K, kern, grid, block, lds, ...)                                                        \
-    do {                                                                                                 \
-        if (ran) *ran |= 1u << (K);                                                                      \
-        if (ev) hipExtLaunchKernelGGL(kern, grid, block, lds, st, ev[2 * (K)], ev[2 * (K) + 1], 0, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                                \
-    } while (0)
-
-int launch_reduce(const PlanDev &pd, const StepArgs &a, size_t zero_doubles, bool so, hipStream_t st, hipEvent_t *ev, unsigned *ran,
+// ev == nullptr: plain launches.  ev != nullptr: hipExtLaunchKernel with a (start, stop) event pair per kernel — ev[2*k],
+// ev[2*k+1], k = 0 prep, 1 tile, 2 pair_finalize, 3 solve, 4 update, 5 the depth walk of the wave-per-tile plans — so bench.py
+// can read each kernel's own duration on the stream it ran on.
+int launch_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st, hipEvent_t *ev, unsigned *ran,
                   int fuse_so_poses, bool *fused) {
-    if (fused) *fused = false;
-    (void)zero_doubles;   // the accumulators are cleared by their consumers (k_pair_finalize, k_update)
-    if (pd.T > 0 && edge_applies(pd)) {
-        if (ran) *ran |= 1u << 1;
-        const int rc = launch_edge(pd, a, so ? 1 : 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-        if (rc != BT_OK) return rc;
-    } else if (pd.T > 0 && stream_applies(pd)) {
-        if (ran) *ran |= 1u << 1;
-        const int rc = launch_stream(pd, a, so ? 1 : 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-        if (rc != BT_OK) return rc;
-    } else if (pd.T > 0 && etile_applies(pd)) {
-        if (ran) *ran |= 1u << 1;
-        int rc;
-        if (so && fuse_so_poses >= 0 && fused && pd.nlz == 0) {
-            const int total = pd.p_tot + (fuse_so_poses ? pd.n_buf : 0), nbr = (total + 511) / 512;
-            rc = launch_etile(pd, a, 1, fuse_so_poses, nbr, 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-            *fused = true;
-        } else if (so) {
-            // split structure-only step (multi-GPU phases, the timed path): the tile blocks only — they leave (Q, w') for the
-            // k_update<true> that follows
-            rc = launch_etile(pd, a, 1, 0, 0, 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-        } else {
-            rc = launch_etile(pd, a, 0, 0, 0, 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-        }
-        if (rc != BT_OK) return rc;
-    } else if (pd.T > 0) {
-        const bool wide = tile_wide(pd);
-        const dim3 blk(tile_threads(pd)), grid(pd.T);
-        if (a.prec) {                      // float64 per-edge path (8 waves per tile)
-            if (so && fuse_so_poses >= 0 && fused && pd.nlz == 0) {
-                const int total = pd.p_tot + (fuse_so_poses ? pd.n_buf : 0), nbr = (total + (int)blk.x - 1) / (int)blk.x;
-                BT_LAUNCH(1, (k_tile<true, false, false, true, double>), dim3(pd.T + nbr), blk, tile_lds_bytes(pd, true), pd, a, fuse_so_poses);
-                *fused = true;
-            }
-            else if (so)         BT_LAUNCH(1, (k_tile<true, false, false, false, double>), grid, blk, tile_lds_bytes(pd, true), pd, a, 0);
-            else if (a.dbg & 32) BT_LAUNCH(1, (k_tile<false, true, false, false, double>), grid, blk, tile_lds_bytes(pd, false), pd, a, 0);
-            else                 BT_LAUNCH(1, (k_tile<false, false, false, false, double>), grid, blk, tile_lds_bytes(pd, false), pd, a, 0);
-        }
-        else if (so && fuse_so_poses >= 0 && fused && pd.nlz == 0) {
-            // the whole structure-only step in this launch: tile workgroups, then the rest of the patch buffer and the poses
-            const int total = pd.p_tot + (fuse_so_poses ? pd.n_buf : 0), nbr = (total + (int)blk.x - 1) / (int)blk.x;
-            const dim3 gridf(pd.T + nbr);
-            if (wide) BT_LAUNCH(1, (k_tile<true, false, true, true>), gridf, blk, tile_lds_bytes(pd, true), pd, a, fuse_so_poses);
-            else      BT_LAUNCH(1, (k_tile<true, false, false, true>), gridf, blk, tile_lds_bytes(pd, true), pd, a, fuse_so_poses);
-            *fused = true;
-        }
-        else if (so && wide)   BT_LAUNCH(1, (k_tile<true, false, true>), grid, blk, tile_lds_bytes(pd, true), pd, a, 0);
-        else if (so)           BT_LAUNCH(1, (k_tile<true, false>), grid, blk, tile_lds_bytes(pd, true), pd, a, 0);
-        else if ((a.dbg & 32) && wide) BT_LAUNCH(1, (k_tile<false, true, true>), grid, blk, tile_lds_bytes(pd, false), pd, a, 0);
-        else if (a.dbg & 32)   BT_LAUNCH(1, (k_tile<false, true>), grid, dim3(512), tile_lds_bytes(pd, false), pd, a, 0);
-        else if (wide)         BT_LAUNCH(1, (k_tile<false, false, true>), grid, blk, tile_lds_bytes(pd, false), pd, a, 0);
-        else                   BT_LAUNCH(1, (k_tile<false, false>), grid, blk, tile_lds_bytes(pd, false), pd, a, 0);
+    const Route &r = pd.route;
+    // a structure-only step in one launch: tile workgroups, then the rest of the patch buffer and the poses (k_tile, k_etile)
+    const bool fuse = so && fuse_so_poses >= 0 && fused && pd.nlz == 0 && (r.kernel == Route::kTile || r.kernel == Route::kEtile);
+    const int total = pd.p_tot + (fuse_so_poses > 0 ? pd.n_buf : 0);
+    if (fused) *fused = fuse && pd.T > 0;
+    if (ran && pd.T > 0) *ran |= 1u << 1;
+    int rc = BT_OK;
+    if (r.kernel == Route::kEdge || r.kernel == Route::kStream)
+        rc = (r.kernel == Route::kEdge ? launch_edge : launch_stream)(pd, a, so ? 1 : 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
+    else if (r.kernel == Route::kEtile)
+        // unfused structure-only step (multi-GPU phases, the timed path): the tile blocks only — they leave (Q, w') for the
+        // k_update<true> that follows
+        rc = launch_etile(pd, a, so ? 1 : 0, fuse ? fuse_so_poses : 0, fuse ? (total + 511) / 512 : 0, 0, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
+    else if (pd.T > 0) {
+        const Pick p = pick(pd, 1, so, fuse, (a.dbg & 32) != 0);
+        const int nbr = fuse ? (total + p.threads - 1) / p.threads : 0;
+        launch_pick(p, pd.T + nbr, st, ev ? ev + 2 : nullptr, pd, a, fuse ? fuse_so_poses : 0);
     }
-    {   // the tracks that sit in no tile (more than 64 free cameras): their edges, their Schur terms (ba_loose.hip)
-        const int rc = launch_loose_reduce(pd, a, so, st);
-        if (rc != BT_OK) return rc;
-    }
+    if (rc != BT_OK) return rc;
+    // the tracks that sit in no tile (more than 64 free cameras): their edges, their Schur terms (ba_loose.hip)
+    rc = launch_loose_reduce(pd, a, so, st);
+    if (rc != BT_OK) return rc;
     if (!so && pd.P > 0) {
         const int pb = (pd.P + 3) / 4, nt16 = pd.max_rows16 >> 4;
-        const int sp_blocks = (pd.T > 0 && etile_applies(pd) && pd.sp_ok) ? pd.sg_n * (nt16 * (nt16 + 1) / 2 + 1) : 0;
-        BT_LAUNCH(2, k_pair_finalize, dim3(pb + sp_blocks), dim3(256), 0, pd, a, pb);
+        const int sp_blocks = (r.kernel == Route::kEtile && pd.sp_ok) ? pd.sg_n * (nt16 * (nt16 + 1) / 2 + 1) : 0;
+        if (ran) *ran |= 1u << 2;
+        if (ev) hipExtLaunchKernelGGL(k_pair_finalize, dim3(pb + sp_blocks), dim3(256), 0, st, ev[4], ev[5], 0, pd, a, pb);
+        else hipLaunchKernelGGL(k_pair_finalize, dim3(pb + sp_blocks), dim3(256), 0, st, pd, a, pb);
     }
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }
@@ -2633,76 +2609,46 @@ int launch_pack(const PlanDev &pd, const StepArgs &a, bool unpack, hipStream_t s
 }
 
 int launch_solve_update(const PlanDev &pd, const StepArgs &a, bool so, bool copy_poses, hipStream_t st, hipEvent_t *ev, unsigned *ran) {
+    const Route &r = pd.route;
     if (!so) {
-        const int mode = solver_mode(pd);
-        const bool prof = (a.dbg & 16) != 0;
-        const int nthr = solver_threads();
-        const int passes = mode == 3 ? 0 : mode >= 1 ? 1 + kRefineSteps : 1;        // float32 factor: iterative refinement
-        if (mode == 3) {
-            if (ran) *ran |= 1u << 3;
+        if (ran) *ran |= 1u << 3;
+        if (r.solver == Route::kSolveDense) {
             const int rc = launch_solve_dense(pd, a, st, ev ? ev[6] : nullptr, ev ? ev[7] : nullptr);
             if (rc != BT_OK) return rc;
-        }
-        for (int pass = 0; pass < passes; ++pass) {
-            if (pass >= 1) hipLaunchKernelGGL(k_refine_residual, dim3((pd.D + 3) / 4), dim3(256), 0, st, pd, a, pass > 1 ? 1 : 0);
-            hipEvent_t *evp = pass == 0 ? ev : nullptr;                // (the event pair of kernel 3 times the first pass)
-            unsigned *ranp = pass == 0 ? ran : nullptr;
-#define BT_LAUNCH_S(kern, grid, block, lds)                                                                                  \
-            do {                                                                                                             \
-                if (ranp) *ranp |= 1u << 3;                                                                                  \
-                if (evp) hipExtLaunchKernelGGL(kern, grid, block, lds, st, evp[6], evp[7], 0, pd, a);                        \
-                else hipLaunchKernelGGL(kern, grid, block, lds, st, pd, a);                                                  \
-            } while (0)
-            if (mode == 0 && use_pipe_solver(pd) && !prof)  BT_LAUNCH_S(k_solve_pipe<false>, dim3(1), dim3(768), solve_pipe_lds_bytes(pd));
-            else if (mode == 0 && use_pipe_solver(pd))      BT_LAUNCH_S(k_solve_pipe<true>, dim3(1), dim3(768), solve_pipe_lds_bytes(pd));
-            else if (mode == 0 && use_fused_solver(pd) && !prof) BT_LAUNCH_S(k_solve_fused<false>, dim3(1), dim3(nthr), solve_fused_lds_bytes(pd, nthr));
-            else if (mode == 0 && use_fused_solver(pd))     BT_LAUNCH_S(k_solve_fused<true>, dim3(1), dim3(nthr), solve_fused_lds_bytes(pd, nthr));
-            else if (mode == 0 && !prof) BT_LAUNCH_S((k_solve_lds<double, false>), dim3(1), dim3(nthr), solve_lds_bytes(pd, 8));
-            else if (mode == 0)          BT_LAUNCH_S((k_solve_lds<double, true>), dim3(1), dim3(nthr), solve_lds_bytes(pd, 8));
-            else if (mode == 1 && !prof) BT_LAUNCH_S((k_solve_lds<float, false>), dim3(1), dim3(nthr), solve_lds_bytes(pd, 4));
-            else if (mode == 1)          BT_LAUNCH_S((k_solve_lds<float, true>), dim3(1), dim3(nthr), solve_lds_bytes(pd, 4));
-            else                BT_LAUNCH_S(k_solve_global, dim3(1), dim3(1024), 0);
-#undef BT_LAUNCH_S
-            if (pass >= 1 && pass == passes - 1) hipLaunchKernelGGL(k_refine_add, dim3(1), dim3(1024), 0, st, pd, a);
+        } else {
+            const Pick p = pick(pd, 3, false, false, (a.dbg & 16) != 0);
+            const bool f32 = r.solver == Route::kSolveLds32 || r.solver == Route::kSolveGlobal;
+            const int passes = f32 ? 1 + kRefineSteps : 1;             // float32 factor: iterative refinement
+            for (int pass = 0; pass < passes; ++pass) {
+                if (pass >= 1) hipLaunchKernelGGL(k_refine_residual, dim3((pd.D + 3) / 4), dim3(256), 0, st, pd, a, pass > 1 ? 1 : 0);
+                launch_pick(p, 1, st, pass == 0 && ev ? ev + 6 : nullptr, pd, a);          // (the event pair of kernel 3 times the first pass)
+                if (pass >= 1 && pass == passes - 1) hipLaunchKernelGGL(k_refine_add, dim3(1), dim3(1024), 0, st, pd, a);
+            }
         }
     }
     const int do_poses = so ? (copy_poses ? 1 : 0) : 1;
     const int total = pd.p_tot + (do_poses ? pd.n_buf : 0);
-    const int nb = (total + kUpdThreads - 1) / kUpdThreads;
     const size_t nz = (size_t)pd.D * pd.D + pd.D;
-    const int zb = (int)((nz + 4 * kUpdThreads - 1) / (4 * kUpdThreads));
-    const size_t upd_lds = ((size_t)pd.max_tile_pairs * kUpdGeo + kUpdThreads) * sizeof(float);
-    if (so) BT_LAUNCH(4, k_update<true>, dim3(nb), dim3(kUpdThreads), 0, pd, a, do_poses, 0, nb);
-    else if (pd.T > 0 && edge_applies(pd)) {
+    if (!so && (r.kernel == Route::kEdge || r.kernel == Route::kStream)) {
+        // the tracks' depths by the wave-per-tile walk (event pair 5), then the rest in k_update
         if (ran) *ran |= 1u << 5;
-        const int rc = launch_edge(pd, a, 2, st, ev ? ev[10] : nullptr, ev ? ev[11] : nullptr);
+        const int rc = (r.kernel == Route::kEdge ? launch_edge : launch_stream)(pd, a, 2, st, ev ? ev[10] : nullptr, ev ? ev[11] : nullptr);
         if (rc != BT_OK) return rc;
-        BT_LAUNCH(4, k_update<false>, dim3(nb + zb), dim3(kUpdThreads), upd_lds, pd, a, do_poses, 0, nb);
     }
-    else if (pd.T > 0 && stream_applies(pd)) {
-        // the tracks' depths by the wave-per-tile walk (event pair 5), then the rest
-        if (ran) *ran |= 1u << 5;
-        const int rc = launch_stream(pd, a, 2, st, ev ? ev[10] : nullptr, ev ? ev[11] : nullptr);
-        if (rc != BT_OK) return rc;
-        BT_LAUNCH(4, k_update<false>, dim3(nb + zb), dim3(kUpdThreads), upd_lds, pd, a, do_poses, 0, nb);
-    }
-    else if (pd.T > 0 && etile_applies(pd)) {
-        if (ran) *ran |= 1u << 4;
+    if (ran) *ran |= 1u << 4;
+    if (!so && r.kernel == Route::kEtile) {
         const int nbe = (total + 511) / 512, zbe = (int)((nz + 4 * 512 - 1) / (4 * 512));
         const int rc = launch_etile(pd, a, 2, do_poses, nbe, zbe, st, ev ? ev[8] : nullptr, ev ? ev[9] : nullptr);
         if (rc != BT_OK) return rc;
+    } else {
+        // k_update: the k_tile route's tile blocks, the rest of the patch buffer and the poses, then the clearing of [S | y]
+        const Pick p = pick(pd, 4, so, false, false);
+        const int tb = !so && r.kernel == Route::kTile ? pd.T : 0;
+        const int nb = (total + p.threads - 1) / p.threads, zb = so ? 0 : (int)((nz + 4 * p.threads - 1) / (4 * p.threads));
+        launch_pick(p, tb + nb + zb, st, ev ? ev + 8 : nullptr, pd, a, do_poses, tb, tb + nb);
     }
-    else if (a.prec)
-        BT_LAUNCH(4, (k_update<false, kUpdThreads, double>), dim3(pd.T + nb + zb), dim3(kUpdThreads), ((size_t)pd.max_tile_pairs * kUpdGeo + kUpdThreads) * sizeof(double), pd, a, do_poses, pd.T, pd.T + nb);
-    else if (tile_wide(pd)) {
-        constexpr int W = 1024;
-        const int nbw = (total + W - 1) / W, zbw = (int)((nz + 4 * W - 1) / (4 * W));
-        BT_LAUNCH(4, (k_update<false, W>), dim3(pd.T + nbw + zbw), dim3(W), ((size_t)pd.max_tile_pairs * kUpdGeo + W) * sizeof(float), pd, a, do_poses, pd.T, pd.T + nbw);
-    }
-    else    BT_LAUNCH(4, k_update<false>, dim3(pd.T + nb + zb), dim3(kUpdThreads), upd_lds, pd, a, do_poses, pd.T, pd.T + nb);
     if (!so) { const int rc = launch_loose_update(pd, a, st); if (rc != BT_OK) return rc; }
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }
-#undef BT_LAUNCH
 
 }  // namespace bt

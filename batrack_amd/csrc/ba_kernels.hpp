@@ -27,31 +27,23 @@ struct StepArgs {
     int dbg;                      // env BT_DEBUG_MODE, 0 in production: 16 / 32 launch the cycle-counting variants of the solver / k_tile
 };
 
-int configure_kernels(const PlanDev &pd);
-// precision of the per-edge maths for this plan: 1 = float64 (graphs that take k_tile, unless BT_FORCE prec=f32 or the
-// tile's E would not fit LDS as double), 0 = float32 (k_stream / k_edge2: graphs of >= 2048 tiles)
-int edge_precision(const PlanDev &pd);
-// the reduced-system solver of this plan: 0 = factor in LDS as double, 1 = in LDS as float (refined), 2 = in the global workspace as
-// float (refined), 3 = dense in the global workspace as double (wide plans)
-int solver_mode(const PlanDev &pd);
+// decides the plan's route (pd.route: which Jacobian kernel, per-edge precision and solver its steps launch) and raises the
+// dynamic-LDS limit of every k_tile / k_update / solver instantiation that route can launch
+int configure_kernels(PlanDev &pd);
 // wave-per-tile streaming kernels (ba_stream.hip) for graphs of many tiles; mode 0 = pose+structure, 1 = structure-only,
 // 2 = depth back-substitution
-bool stream_applies(const PlanDev &pd);
 int launch_stream(const PlanDev &pd, const StepArgs &a, int mode, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-// the same for slot-uniform graphs in the edge-major layout (ba_stream3.hip)
-bool edge_applies(const PlanDev &pd);
+// the same for slot-uniform graphs in the edge-major layout (ba_edge2u.hip)
 int launch_edge(const PlanDev &pd, const StepArgs &a, int mode, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 // its pose+structure reduce with two edges per lane (ba_edge2.hip)
 int launch_edge2(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-// the pair-major tile kernel (ba_etile.hip) for the graphs k_tile would take, whenever the plan has the pair-major tables
-// (every tile <= 64 camera pairs) and the tile's E fits LDS: 8 / 4 = as double / only as float, 0 = k_tile takes the plan.
-// launch_etile: mode 0 = pose+structure reduce, 1 = the whole structure-only step, 2 = a pose+structure step's last kernel
-int etile_precision_bytes(const PlanDev &pd);
+// the pair-major tile kernel (ba_etile.hip): mode 0 = pose+structure reduce, 1 = the whole structure-only step, 2 = a
+// pose+structure step's last kernel
 int launch_etile(const PlanDev &pd, const StepArgs &a, int mode, int do_poses, int extra_blocks, int zero_blocks, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 // ev != nullptr: a (start, stop) event pair per kernel; *ran gets bit k set for every kernel k that was launched
 // fuse_so_poses >= 0 (and `fused` given): a structure-only step on the k_tile path also does the step's update in the same
 // launch (fuse_so_poses = 1: copy the poses too) and sets *fused; the caller then skips launch_solve_update
-int launch_reduce(const PlanDev &pd, const StepArgs &a, size_t zero_doubles, bool so, hipStream_t st, hipEvent_t *ev = nullptr, unsigned *ran = nullptr,
+int launch_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st, hipEvent_t *ev = nullptr, unsigned *ran = nullptr,
                   int fuse_so_poses = -1, bool *fused = nullptr);
 // dense [S | y] <-> its non-zero blocks in factor order (bt_ba_pack / bt_ba_unpack)
 int launch_pack(const PlanDev &pd, const StepArgs &a, bool unpack, hipStream_t st);

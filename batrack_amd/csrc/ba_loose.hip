@@ -206,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_loose_update(PlanDev pd, StepArgs 
 // the loose tracks' share of the reduce phase (behind the Jacobian kernel, in front of k_pair_finalize) ...
 int launch_loose_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st) {
     if (pd.nlz <= 0) return BT_OK;
-    const int rawk = (edge_applies(pd) || stream_applies(pd)) ? 1 : 0;
+    const int rawk = (pd.route.kernel == Route::kEdge || pd.route.kernel == Route::kStream) ? 1 : 0;
     const size_t lds = so ? 0 : (size_t)pd.n * (6 * sizeof(double) + sizeof(int));
     if (lds > 150 * 1024) return BT_EUNSUPPORTED;
     if (so) hipLaunchKernelGGL(lz::k_loose_reduce<true>, dim3(pd.nlz), dim3(lz::kThreads), 0, st, pd, a, rawk);

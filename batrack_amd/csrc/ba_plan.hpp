@@ -71,6 +71,19 @@ BT_HD inline size_t etile_full_lds_bytes(int max_rows16, int max_tile_pairs, siz
     return (size_t)4 * 26 * smax * sizeof(double) + (rows * kLdsRowStride + 128 + mtp * kPairGeomFloats) * rsz + rows * sizeof(int) + 64;
 }
 
+// The kernels a plan's BA step launches: decided once per plan from its PlanDev scalars and BT_FORCE (ba_kernels.hip:
+// plan_route, called by configure_kernels) and read by the launchers only.
+struct Route {
+    enum : int { kTile = 0, kStream = 1, kEdge = 2, kEtile = 3 };          // kernel: the bt_plan_jacobian_kernel codes
+    // solver: 0 .. 3 are the "solver_mode" readback (factor in LDS as double, in LDS as float, in the global workspace as
+    // float, dense as double: wide plans); kSolveFused and kSolvePipe are variants of kSolveLds (k_solve_fused, k_solve_pipe)
+    enum : int { kSolveLds = 0, kSolveLds32 = 1, kSolveGlobal = 2, kSolveDense = 3, kSolveFused = 4, kSolvePipe = 5 };
+    int kernel;
+    int prec;                     // bytes of the per-edge maths (bt_plan_edge_precision): 8 float64, 6 mixed (k_stream, k_edge2), 4 float32
+    int wide;                     // kTile with float32 maths only: k_tile / k_update run 16 waves per tile instead of 8
+    int solver;
+};
+
 // Device-side view: raw pointers into one device allocation + sizes.
 struct PlanDev {
     int E, n_buf, p_tot, fixedp, n_all, n, D, m, P, T, slots, erows, nnzb, nupd, max_rows16;
@@ -121,6 +134,7 @@ struct PlanDev {
     int fz_npend, fz_nlazy, fz_ok;      // fz_ok: no level has more than two columns
     int fzp_ok;                         // and every column's panel fits one wave (k_solve_pipe)
     const int32_t *lvl_meta;   // [nlev][kMaxLevelCols][8]: col, diag pos, #sub-blocks, first rest triple, #rest triples, dp first, #dp, 0  (col = -1: unused)
+    Route route;               // set by configure_kernels (host side only: no kernel reads it)
 };
 
 // Bytes of the status block at WsLayout::status: int 0 the solver status, 1 the exchange time-out, 4.. profiling counters, 200 / 201

@@ -16,7 +16,7 @@
 //     only when the cameras change; E Q w' by a wave reduce-scatter;
 //   * MODE kModeSO: structure-only steps (C, w, Q, w' only);  kModeUpd: the depth back-substitution of k_update
 //     (ba_kernels.hip) for the same tile walk.
-// Which graphs take this kernel: stream_applies() below and edge_applies() in ba_stream3.hip (profiles/r02_kernel_choice.txt).
+// Which graphs take this kernel: plan_route() in ba_kernels.hip (profiles/r02_kernel_choice.txt).
 // Reference: ba.py:228-337, projective_ops.py:54-100.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -543,12 +543,6 @@ static size_t stream_lds_bytes(const PlanDev &pd, int mode) {
     if (mode == kModeSO) return (mtp * kPairGeomFloats + 1024) * sizeof(float);
     return (mtp * kPairGeomFloats + 1024 + (Rmax + 1) * kLdsRowStride + 128 + ((Rmax + 3) & ~(size_t)3) + ((mtp + 3) & ~(size_t)3)) * sizeof(float) +
            2 * mtp * 32 * sizeof(double) + 16;
-}
-
-// The streaming kernels take graphs of many tiles whose tiles see at most 10 cameras (row tiles of the register
-// accumulators) and 32 camera pairs (one lane per pair in the prologue, LDS of the per-pair sums).
-bool stream_applies(const PlanDev &pd) {
-    return pd.st_ok != 0 && pd.T >= pd.st_min && pd.max_cams <= 10 && pd.max_tile_pairs <= 32 && pd.max_tile_pairs > 0;
 }
 
 template <int MODE, int NT, bool PROF = false>

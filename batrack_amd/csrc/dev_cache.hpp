@@ -1,11 +1,12 @@
 // dev_cache.hpp — what the launchers remember per DEVICE: the device's properties and, per kernel, the dynamic-LDS limit that
 // hipFuncSetAttribute has raised (the attribute is per device: a process-wide static would leave a second GPU of the process at
-// its 64 KB default and hand it the first device's CU count).  Thread-safe: atomics, values only ever raised.
+// its 64 KB default and hand it the first device's CU count).  Thread-safe: atomic reads, values only ever raised.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
 #include <cstddef>
+#include <mutex>
 
 namespace bt {
 
@@ -32,20 +33,22 @@ inline bool device_props(DevProps *out, int dev = -1) {
     return true;
 }
 
-// one per kernel instantiation (a function-local static of its launcher)
+// one per kernel instantiation (a function-local static of its launcher).  The attribute is one value per kernel and device
+// while several plans (and the prefetch thread building the next one) launch it with different amounts: it is only ever
+// RAISED, and the setting is serialised, so a smaller request racing a larger one cannot leave it below the larger.
 struct LdsLimit {
     std::atomic<size_t> raised[kMaxDevices];
+    std::mutex mu;
     // make `bytes` of dynamic LDS launchable for `func` on device `dev` (-1: the current device; the attribute is set on the current one)
     bool ensure(const void *func, size_t bytes, int dev = -1) {
         if (bytes <= 48 * 1024) return true;
         if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return false;
         const int slot = dev >= 0 && dev < kMaxDevices ? dev : -1;
         if (slot >= 0 && raised[slot].load(std::memory_order_acquire) >= bytes) return true;
+        std::lock_guard<std::mutex> lk(mu);
+        if (slot >= 0 && raised[slot].load(std::memory_order_relaxed) >= bytes) return true;
         if (hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
-        if (slot >= 0) {
-            size_t cur = raised[slot].load(std::memory_order_relaxed);
-            while (cur < bytes && !raised[slot].compare_exchange_weak(cur, bytes, std::memory_order_release)) { }
-        }
+        if (slot >= 0) raised[slot].store(bytes, std::memory_order_release);
         return true;
     }
 };
