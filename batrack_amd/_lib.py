@@ -8,7 +8,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "ga_kernels.hip", "depth_eval.hip"]
+SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip"]
 HEADERS = ["ba_kernels.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
@@ -17,11 +17,12 @@ HEADERS = ["ba_kernels.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
 BT_OK, BT_EINVAL, BT_ENOMEM, BT_EHIP, BT_EUNSUPPORTED = 0, -1, -2, -3, -4
+BT_DEPTH_F32, BT_DEPTH_F64 = 0, 1                    # include/batrack_depth.h
 ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "HIP runtime error",
           BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
                            "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
                            "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward, or more than 8192 cells wide in "
-                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements)"}
+                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -266,6 +267,10 @@ def lib():
     L.bt_depth_metrics_workspace_bytes.argtypes = [i64]
     L.bt_depth_metrics.restype = i32
     L.bt_depth_metrics.argtypes = [vp, vp, vp, i64, ctypes.c_float, ctypes.c_float, i32, vp, vp, vp]
+    L.bt_align_depth_maps_workspace_bytes.restype = i64
+    L.bt_align_depth_maps_workspace_bytes.argtypes = [i64, i32]
+    L.bt_align_depth_maps.restype = i32
+    L.bt_align_depth_maps.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

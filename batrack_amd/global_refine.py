@@ -33,7 +33,8 @@ _SMOOTH = {"l1": 0, "l2": 1, "huber": 2}
 def _align_depth_maps(depth_maps):
     """model/utils.py:268-312 (`align_depth_maps`, used when RefineNet is built with align_depth=True): every depth map is
     scaled so that its median over the overlap with its aligned predecessor matches the median of the previous (two) aligned
-    maps.  A one-off pass over numpy arrays at construction, on the host as in the reference."""
+    maps.  The host restatement, bit-equal to the reference: align_depth_maps runs float32 / float64 maps on the device and
+    this function for other dtypes; the tests hold the device to it."""
     import numpy as np
     S = depth_maps.shape[0]
     out = np.zeros_like(depth_maps)
@@ -51,6 +52,89 @@ def _align_depth_maps(depth_maps):
             med_prev = np.median(np.concatenate((past[(past > 0) & (prev > 0)], prev[mask])))
         out[i, ..., 0] = med_prev / np.median(cur[mask]) * cur
     return out
+
+
+_ALIGN_DTYPES = {torch.float32: _lib.BT_DEPTH_F32, torch.float64: _lib.BT_DEPTH_F64}
+
+
+def align_depth_maps_device(maps, out=None):
+    """bt_align_depth_maps on channel 0 of a scene: `maps` a contiguous float32 or float64 GPU tensor [T, ...] (one frame per
+    index of the first dimension), `out` a tensor like it or `maps` itself (in place; default: a new one).  Returns
+    (aligned, scales, overlap): `scales` [T] float64 (s, NaN for frame 0 and the frames with fewer than 100 overlapping
+    pixels), `overlap` [T] int64 (the overlap count, 0 for frame 0).  Enqueued on the current stream; nothing synchronises."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda):
+        raise RuntimeError("align_depth_maps_device: `maps` must be a GPU tensor (no CPU fallback in batrack_amd)")
+    if maps.dtype not in _ALIGN_DTYPES:
+        raise TypeError(f"align_depth_maps_device: float32 or float64 maps, not {maps.dtype}")
+    if maps.dim() < 1 or maps.numel() == 0 or not maps.is_contiguous():
+        raise ValueError("align_depth_maps_device: `maps` must be a non-empty contiguous [T, ...] tensor")
+    if out is None:
+        out = torch.empty_like(maps)
+    elif out.shape != maps.shape or out.dtype != maps.dtype or out.device != maps.device or not out.is_contiguous():
+        raise ValueError("align_depth_maps_device: `out` must be a contiguous tensor of the shape, dtype and device of `maps`")
+    T = maps.shape[0]
+    hw, dt, dev = maps.numel() // T, _ALIGN_DTYPES[maps.dtype], maps.device
+    L = _lib.lib()
+    wb = L.bt_align_depth_maps_workspace_bytes(hw, dt)
+    if wb < 0:
+        _lib.check(int(wb), "bt_align_depth_maps_workspace_bytes")
+    ws = torch.empty(int(wb), dtype=torch.uint8, device=dev)
+    scales = torch.empty(T, dtype=torch.float64, device=dev)
+    overlap = torch.empty(T, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.bt_align_depth_maps(maps.data_ptr(), out.data_ptr(), T, hw, dt, scales.data_ptr(), overlap.data_ptr(),
+                                         ws.data_ptr(), st), "bt_align_depth_maps")
+    return out, scales, overlap
+
+
+def align_depth_maps(depth_maps, *, return_stats=False):
+    """model/utils.py:268-312 on the HIP kernels (bt_align_depth_maps): every depth map's channel 0 is scaled so that its median
+    over the overlap with its aligned predecessor matches the median of the previous (two) aligned maps; a map with fewer
+    than 100 overlapping pixels is kept as it is.  Bit for bit what the reference computes, in the input's dtype.
+      numpy [T,H,W,C] float32 / float64: numpy out, the reference's array (frame 0 whole, channel 0 only for the others), and
+        the reference's message for every skipped frame, printed after the one read-back at the end.  Other numpy dtypes
+        take the host function (_align_depth_maps).
+      GPU tensor [T,H,W] or [T,H,W,C], float32 / float64: a GPU tensor of the same shape (the same channel layout as the
+        numpy result); nothing is printed and nothing synchronises.
+    `return_stats=True` also returns `scales` [T] float64 and `overlap` [T] int64 (align_depth_maps_device), as numpy arrays
+    for numpy input and GPU tensors for tensor input."""
+    import numpy as np
+    if isinstance(depth_maps, torch.Tensor):
+        x = depth_maps
+        if not x.is_cuda:
+            raise RuntimeError("align_depth_maps: a tensor must be on the GPU (no CPU fallback in batrack_amd)")
+        if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[-1] < 1):
+            raise ValueError("align_depth_maps: a tensor must be [T,H,W] or [T,H,W,C]")
+        if x.dim() == 3 or x.shape[-1] == 1:
+            aligned, scales, overlap = align_depth_maps_device(x.contiguous())
+            out = aligned.view(x.shape)
+        else:
+            aligned, scales, overlap = align_depth_maps_device(x[..., 0].contiguous())
+            out = torch.zeros_like(x)
+            out[0] = x[0]
+            out[1:, ..., 0] = aligned[1:]
+        return (out, scales, overlap) if return_stats else out
+    a = np.asarray(depth_maps)
+    if a.ndim != 4:
+        raise ValueError("align_depth_maps: depth_maps must be [T,H,W,C]")
+    if a.dtype not in (np.float32, np.float64):
+        if return_stats:
+            raise TypeError(f"align_depth_maps: return_stats needs float32 or float64 maps, not {a.dtype}")
+        return _align_depth_maps(a)
+    if not torch.cuda.is_available():
+        raise RuntimeError("align_depth_maps: needs a GPU (no CPU fallback in batrack_amd)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    aligned, scales, overlap = align_depth_maps_device(torch.as_tensor(np.ascontiguousarray(a[..., 0]), device=dev))
+    al, sc, ov = aligned.cpu().numpy(), scales.cpu().numpy(), overlap.cpu().numpy()
+    for i in range(1, a.shape[0]):
+        if ov[i] < 100:
+            print(f"Insufficient overlapping region found between depth map {i - 1} and {i} ({ov[i]} pixels). "
+                  "Using previous transformation.")
+    out = np.zeros_like(a)
+    out[0] = a[0]
+    out[1:, ..., 0] = al[1:]
+    return (out, sc, ov) if return_stats else out
 
 
 class RefineLosses:
@@ -110,7 +194,8 @@ class RefineLosses:
           jj = t + s - S // 2 (refine_net.py:92-97)
           dmaps [T,H,W,1] -> `trajs_disp_mono` [T,N,S] = 1 / max(bilinear sample of frame clamp(jj) at the track, 1e-2) by
                              bt_ga_sample_disp_mono (refine_net.py:99-110); `align_depth=True` first rescales the maps by
-                             their running medians as model/utils.py:268-312 does (on the host, where the reference does it).
+                             their running medians as model/utils.py:268-312 does: float32 / float64 maps on the device in
+                             their dtype (bt_align_depth_maps, bit-equal to the reference), other dtypes on the host.
                              The maps are sampled in FLOAT32 (the reference keeps results['dmaps'] float64 and samples and
                              inverts in float64): `trajs_disp_mono` is within ~1e-7 relative of the reference's, tested at
                              1e-5 of its largest entry — the losses it enters are float32 anyway
@@ -135,7 +220,8 @@ class RefineLosses:
         dm = np.asarray(results["dmaps"])
         if dm.ndim != 4 or dm.shape[-1] < 1:
             raise ValueError("results['dmaps'] must be [T,H,W,C]")
-        if align_depth:
+        on_device = align_depth and dm.dtype in (np.float32, np.float64)
+        if align_depth and not on_device:
             dm = _align_depth_maps(dm)
         t2d = torch.as_tensor(np.ascontiguousarray(results["trajs_2d_disp"]), dtype=torch.float32, device=dev)
         if t2d.dim() != 4 or t2d.shape[-1] != 3:
@@ -144,7 +230,11 @@ class RefineLosses:
         if dm.shape[0] != T:
             raise ValueError("results['dmaps'] and results['trajs_2d_disp'] disagree about the number of frames")
         H, W = int(dm.shape[1]), int(dm.shape[2])
-        dmaps = torch.as_tensor(np.ascontiguousarray(dm[..., 0]), dtype=torch.float32, device=dev)
+        if on_device:                                      # channel 0 in its own dtype, aligned in place, then float32
+            ch0 = torch.as_tensor(np.ascontiguousarray(dm[..., 0]), device=dev)
+            dmaps = align_depth_maps_device(ch0, out=ch0)[0].to(torch.float32)
+        else:
+            dmaps = torch.as_tensor(np.ascontiguousarray(dm[..., 0]), dtype=torch.float32, device=dev)
         trajs_2d = t2d[..., :2].contiguous()
         mono = torch.empty(T, N, S, device=dev, dtype=torch.float32)
         _lib.check(L.bt_ga_sample_disp_mono(dmaps.data_ptr(), trajs_2d.data_ptr(), mono.data_ptr(), T, N, S, H, W, st), "bt_ga_sample_disp_mono")

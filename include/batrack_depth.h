@@ -1,8 +1,10 @@
-/* batrack_depth.h — C ABI of the video-depth metrics the reference reports after its dense global alignment.
+/* batrack_depth.h — C ABI of the video-depth metrics the reference reports after its dense global alignment, and of the
+ * depth-map alignment that prepares that stage.
  *
  * Reference: main/global_refine/model/utils.py:103-116 (eval_depth), :187-201 (align_with_lstsq), :203-240
- * (compute_errors), :253-265 (eval_depth_metric).  The reference scores a refined depth map against ground truth in numpy on
- * the host; bt_depth_metrics does the same for one pair of arrays on the device.  Device pointers, sizes, integer status codes
+ * (compute_errors), :253-265 (eval_depth_metric), :268-312 (align_depth_maps).  The reference scores a refined depth map
+ * against ground truth in numpy on the host; bt_depth_metrics does the same for one pair of arrays on the device, and
+ * bt_align_depth_maps aligns a scene's depth maps there.  Device pointers, sizes, integer status codes
  * (include/batrack_ba.h); nothing allocates or synchronises.
  */
 #ifndef BATRACK_DEPTH_H
@@ -38,6 +40,32 @@ int64_t bt_depth_metrics_workspace_bytes(int64_t n);
  * BT_EUNSUPPORTED, checked before anything is enqueued.  Enqueued on `stream`. */
 int bt_depth_metrics(const float *gt, const float *pred, const uint8_t *mask, int64_t n, float depth_min, float depth_max,
                      int32_t scaling, void *workspace, double *out, void *stream);
+
+#define BT_DEPTH_F32 0
+#define BT_DEPTH_F64 1
+
+/* Bytes of device workspace bt_align_depth_maps needs for frames of hw pixels (independent of the data and of T); BT_EINVAL
+ * for hw < 1 or a bad dtype, BT_EUNSUPPORTED for hw >= 2^30. */
+int64_t bt_align_depth_maps_workspace_bytes(int64_t hw, int32_t dtype);
+
+/* align_depth_maps (main/global_refine/model/utils.py:268-312) on channel 0 of T depth maps of hw pixels, in the dtype
+ * (BT_DEPTH_F32: float, BT_DEPTH_F64: double) as numpy computes it.  aligned[0] = maps[0]; then for i = 1 .. T-1 in order
+ *   m = (aligned[i-1] > 0) & (maps[i] > 0),  c = count(m)
+ *   c < 100:  aligned[i] = maps[i]
+ *   else:     aligned[i] = s * maps[i],  s = med_prev / med_cur (one correctly rounded division in the dtype),
+ *             med_cur = median(maps[i][m]),  med_prev = median(aligned[0][m]) for i == 1, else the median of the multiset
+ *             aligned[i-2][(aligned[i-2] > 0) & (aligned[i-1] > 0)] + aligned[i-1][m]
+ * with numpy's median (exact selection; an even count takes np.mean of the two middle elements in the dtype).  The `> 0`
+ * tests drop NaN; every pixel is scaled, NaN and non-positive ones included.  The frames are a chain: each reads the
+ * materialised aligned[i-1] and aligned[i-2].  `maps`, `aligned`: device, [T, hw] contiguous, the same buffer (in place) or
+ * not overlapping.  scales [T] (device float64, or NULL): s widened, NaN for frame 0 and skipped frames.  overlap [T] (device
+ * int64, or NULL): c, 0 for frame 0.  The whole chain is one fixed sequence of launches on `stream`: the counts, the branch,
+ * the medians and s stay in device state (integer atomics only: a call repeats bit for bit).  `workspace`:
+ * bt_align_depth_maps_workspace_bytes(hw, dtype) bytes, 16-byte aligned, contents arbitrary.  BT_EINVAL for T < 1, hw < 1, a
+ * bad dtype, a NULL maps / aligned / workspace or a partial overlap of the two buffers; BT_EUNSUPPORTED for hw >= 2^30 (a union
+ * count, at most 2 hw, stays below 2^31); both before anything is enqueued. */
+int bt_align_depth_maps(const void *maps, void *aligned, int64_t T, int64_t hw, int32_t dtype, double *scales, int64_t *overlap,
+                        void *workspace, void *stream);
 
 #ifdef __cplusplus
 }
