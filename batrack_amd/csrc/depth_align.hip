@@ -6,7 +6,7 @@
 //   k_ad_hist   one pass of a radix select (8-bit digits, most significant first: 4 passes for float32, 8 for float64) over
 //               the raw bits of the selected values (all > 0, so the bits order them), for four selections at once: the
 //               lower and upper middle element of cur and of prev.  Per-workgroup LDS histograms with wave-aggregated
-//               increments (depth_eval.hip's hist_add), flushed to global memory with integer atomics.  An upper selection
+//               increments (radix_select.hpp's hist_add), flushed to global memory with integer atomics.  An upper selection
 //               shares its lower one's histogram while their prefixes agree.
 //   k_ad_pick   one workgroup, one wave per selection: narrows (prefix, rank) and clears the histogram for the next pass.
 //               Pass 0 records c and the union count and decides the c < 100 branch; later passes of a skipped frame do
@@ -18,6 +18,7 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_depth.h"
+#include "radix_select.hpp"
 
 namespace bt {
 namespace ad {
@@ -43,6 +44,9 @@ constexpr size_t kStateOff = kHistBytes;
 constexpr size_t kWsBytes = kStateOff + 256;
 static_assert(sizeof(State) <= 256, "State");
 
+using rs::hist_add;
+using rs::mean2;
+
 __device__ __forceinline__ State *state(unsigned char *ws) { return reinterpret_cast<State *>(ws + kStateOff); }
 __device__ __forceinline__ const State *state(const unsigned char *ws) { return reinterpret_cast<const State *>(ws + kStateOff); }
 
@@ -51,14 +55,6 @@ __device__ __forceinline__ uint64_t key(double f) { return (uint64_t)__double_as
 template <class T> __device__ __forceinline__ T decode(uint64_t k);
 template <> __device__ __forceinline__ float decode<float>(uint64_t k) { return __uint_as_float((uint32_t)k); }
 template <> __device__ __forceinline__ double decode<double>(uint64_t k) { return __longlong_as_double((long long)k); }
-
-// numpy's median of the two middle elements, np.mean in the dtype: float32 sums in float32 and divides by the count in float64
-// (float32 / intp), which is exact halving rounded once; float64 sums and divides in float64
-__device__ __forceinline__ float mean2(float lo, float hi) {
-    const float s = lo + hi;
-    return (float)((double)s / 2.0);
-}
-__device__ __forceinline__ double mean2(double lo, double hi) { return (lo + hi) / 2.0; }
 
 // med_prev / med_cur in the dtype, correctly rounded: a float64 quotient of float32 operands rounds to float32 innocuously
 // (53 >= 2 * 24 + 2), whatever the compiler's float32 division does
@@ -86,20 +82,6 @@ __device__ __forceinline__ void for_pixels(const T *cur, const T *prev, const T 
         start = W * nv;
     }
     for (int64_t i = start + tid; i < n; i += nth) f(cur[i], prev[i], past ? past[i] : T(0));
-}
-
-// h[bin of key] += 1 for the lanes with `act`: the lanes that share the first active lane's bin add once, together
-__device__ __forceinline__ void hist_add(uint32_t *h, uint64_t k, int shift, bool act) {
-    const uint64_t am = __ballot(act);
-    if (am == 0) return;
-    const int bin = (int)((k >> shift) & 0xffu);
-    const int leader = __ffsll((unsigned long long)am) - 1;
-    const int lb = __shfl(bin, leader);
-    const uint64_t same = __ballot(act && bin == lb);
-    if (act) {
-        if (bin != lb) atomicAdd(&h[bin], 1u);
-        else if ((int)__lane_id() == leader) atomicAdd(&h[lb], (uint32_t)__popcll(same));
-    }
 }
 
 template <class T, bool VEC>

@@ -16,6 +16,7 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_depth.h"
+#include "radix_select.hpp"
 
 namespace bt {
 namespace de {
@@ -40,15 +41,9 @@ constexpr size_t kStateOff = kHistBytes, kPartOff = kHistBytes + 256;
 constexpr size_t kWsBytes = kPartOff + (size_t)kSumBlocks * kParts * sizeof(double);
 static_assert(sizeof(State) <= 256, "State");
 
-__device__ __forceinline__ uint32_t fkey(float f) {               // order-preserving; -0 and +0 are one key, as numpy compares them
-    uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float fdecode(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+using rs::fdecode;
+using rs::fkey;
+using rs::hist_add;
 
 __device__ __forceinline__ State *state(unsigned char *ws) { return reinterpret_cast<State *>(ws + kStateOff); }
 __device__ __forceinline__ double *partials(unsigned char *ws) { return reinterpret_cast<double *>(ws + kPartOff); }
@@ -71,21 +66,6 @@ __device__ __forceinline__ void for_elems(const float *gt, const float *pred, co
         start = 4 * n4;
     }
     for (int64_t i = start + tid; i < n; i += nth) f(gt[i], pred[i], mask ? mask[i] != 0 : true);
-}
-
-// h[bin of key] += 1 for the lanes with `act`: the lanes that share the first active lane's bin add once, together (a tied or
-// constant input then costs one LDS atomic per wave), the others one each
-__device__ __forceinline__ void hist_add(uint32_t *h, uint32_t key, int shift, bool act) {
-    const uint64_t am = __ballot(act);
-    if (am == 0) return;
-    const int bin = (int)((key >> shift) & 0xffu);
-    const int leader = __ffsll((unsigned long long)am) - 1;
-    const int lb = __shfl(bin, leader);
-    const uint64_t same = __ballot(act && bin == lb);
-    if (act) {
-        if (bin != lb) atomicAdd(&h[bin], 1u);
-        else if ((int)__lane_id() == leader) atomicAdd(&h[lb], (uint32_t)__popcll(same));
-    }
 }
 
 template <bool VEC>

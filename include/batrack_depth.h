@@ -2,7 +2,8 @@
  * depth-map alignment that prepares that stage.
  *
  * Reference: main/global_refine/model/utils.py:103-116 (eval_depth), :187-201 (align_with_lstsq), :203-240
- * (compute_errors), :253-265 (eval_depth_metric), :268-312 (align_depth_maps).  The reference scores a refined depth map
+ * (compute_errors), :253-265 (eval_depth_metric), :268-312 (align_depth_maps), and main/mono_depth/get_mono_depth.py:21-150
+ * (align_depth: mono disparity to metric depth, bt_mono_align).  The reference scores a refined depth map
  * against ground truth in numpy on the host; bt_depth_metrics does the same for one pair of arrays on the device, and
  * bt_align_depth_maps aligns a scene's depth maps there.  Device pointers, sizes, integer status codes
  * (include/batrack_ba.h); nothing allocates or synchronises.
@@ -66,6 +67,33 @@ int64_t bt_align_depth_maps_workspace_bytes(int64_t hw, int32_t dtype);
  * count, at most 2 hw, stays below 2^31); both before anything is enqueued. */
 int bt_align_depth_maps(const void *maps, void *aligned, int64_t T, int64_t hw, int32_t dtype, double *scales, int64_t *overlap,
                         void *workspace, void *stream);
+
+/* Bytes of device workspace bt_mono_align needs for T frames of hw pixels (independent of the data; it grows with T, about
+ * 4.2 KB a frame); BT_EINVAL for T < 1, hw < 1 or a bad dtype, BT_EUNSUPPORTED for T * hw > 2^31 - 1. */
+int64_t bt_mono_align_workspace_bytes(int64_t T, int64_t hw, int32_t dtype);
+
+/* align_depth (main/mono_depth/get_mono_depth.py:21-150) on T frames of hw pixels: relative mono disparity `mono` (float32) to
+ * metric depth, given the metric depth `metric` of the same frames in the dtype D (BT_DEPTH_F32: float, BT_DEPTH_F64: double),
+ * as numpy computes it in D.  Per frame t (d = mono[t], m = metric[t])
+ *   g = 1 / (m + 1e-8);  g = 1e-2 where (m < 2) & (d < 0.02)            (d < 0.02 in float32)
+ *   s_t = median((g - median(g) + 1e-8) / (d - median(d) + 1e-8)),  c_t = median(g - s_t d)
+ * (median(d) and d - median(d) + 1e-8 in float32, the rest in D); then across the scene
+ *   p = s c,  k = argmin |p - median(p)|  (the first index on ties; the first NaN if any, so k = 0 when median(p) is NaN)
+ *   a_s = s_k,  a_c = c_k,  n = percentile(a_s d + a_c over all T * hw elements, 98) / 2
+ *   depth_out = clip(1 / ((1 / n) (a_s d + a_c)), 1e-4, 1e4),  0 where that is below 1e-2
+ * with numpy's median (exact selection; an even count takes np.mean of the two middle elements in the dtype) and numpy's
+ * 'linear' percentile (q = D(98) / D(100), the index (T hw - 1) q, its floor, the next index and gamma in D, and np.lerp's two
+ * forms either side of gamma = 0.5); a NaN in a median's or the percentile's input makes it NaN.  Every operation is rounded once
+ * in D (no fused multiply-add) and divisions are correctly rounded.
+ * `mono` [T, hw] float32, `metric` [T, hw] D, `depth_out` [T, hw] D: device, contiguous.  Optional (NULL: not written), in D:
+ * frame_scale [T] (s), frame_shift [T] (c), aligns [3] (a_s, a_c, n); med_index [1] int64 (k).  The whole computation is one fixed
+ * sequence of launches on `stream`: the medians, k and n stay in device state (integer atomics only: a call repeats bit for bit).
+ * `workspace`: bt_mono_align_workspace_bytes(T, hw, dtype) bytes, 16-byte aligned, contents arbitrary.  BT_EINVAL for T < 1,
+ * hw < 1, a bad dtype, a NULL mono / metric / depth_out / workspace, a pointer not aligned to its element, or an output or the
+ * workspace that overlaps an input (or the workspace an output); BT_EUNSUPPORTED for T * hw > 2^31 - 1; both before anything is
+ * enqueued. */
+int bt_mono_align(const float *mono, const void *metric, int64_t T, int64_t hw, int32_t dtype, void *depth_out, void *frame_scale,
+                  void *frame_shift, void *aligns, int64_t *med_index, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }
