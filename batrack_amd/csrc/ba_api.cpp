@@ -186,39 +186,19 @@ struct ApiTick {
     }
 };
 
-// PlanDev of a plan whose arrays sit at `d` in the layout recorded in pl->off (upload_plan, clone_plan_shifted)
+// PlanDev's figures of the plan info and its table pointers, for tables that sit at `d` as pl->off places them (upload_plan,
+// clone_shifted); its other scalars are the planner's and upload_plan's
 static void bind_pointers(bt_plan *pl, const void *d) {
-    const PlanOffsets &O = pl->off;
     const char *b = static_cast<const char *>(d);
     const bt_plan_info &I = pl->info;
     PlanDev &P = pl->dev;
     P.E = (int)I.E; P.n_buf = (int)I.n_buf; P.p_tot = (int)I.p_tot; P.fixedp = (int)I.fixedp;
     P.n_all = (int)I.n_all; P.n = (int)I.n; P.D = (int)(6 * I.n); P.m = (int)I.m; P.P = (int)I.pairs;
     P.T = (int)I.tiles; P.slots = (int)I.slots; P.erows = (int)I.erows; P.nnzb = (int)I.nnz_blocks;
-    P.nupd = (int)I.updates; P.max_rows16 = pl->max_rows16; P.dev_id = pl->dev_id;
-#define BT_I32(off) reinterpret_cast<const int32_t *>(b + (off))
-    P.kx = BT_I32(O.kx);
-    P.act_bits = reinterpret_cast<const uint32_t *>(b + O.ab); P.act_rank = BT_I32(O.ar);
-    P.pair_i = BT_I32(O.pi); P.pair_j = BT_I32(O.pj);
-    P.tile_trk0 = BT_I32(O.t0); P.tile_ntrk = BT_I32(O.tn); P.tile_ncam = BT_I32(O.tc); P.tile_cam0 = BT_I32(O.c0);
-    P.tile_slot0 = BT_I32(O.s0); P.tile_nslot = BT_I32(O.sn); P.tile_erow0 = BT_I32(O.e0); P.tile_cams = BT_I32(O.cams);
-    P.slot_edge = BT_I32(O.se); P.slot_pair = BT_I32(O.sp);
-    P.slot_lab = reinterpret_cast<const uint16_t *>(b + O.sl);
-    P.col_ptr = BT_I32(O.cp); P.row_idx = BT_I32(O.ri); P.upd_ptr = BT_I32(O.up); P.upd = BT_I32(O.u); P.blk_col = BT_I32(O.bc); P.upd_next = BT_I32(O.un);
-    P.perm = BT_I32(O.pm); P.blk_src = BT_I32(O.bs); P.lvl_ptr = BT_I32(O.lp); P.lvl_cols = BT_I32(O.lc);
-    P.col_lvl = BT_I32(O.cl); P.dp_ptr = BT_I32(O.dpp); P.dp = BT_I32(O.dp);
-    P.nlev = pl->cnt_nlev; P.ndp = pl->cnt_ndp;
-    P.lvl_meta = BT_I32(O.lm); P.tile_flags = BT_I32(O.tf);
-    P.fz_pend_ptr = BT_I32(O.fpp); P.fz_pend = BT_I32(O.fp); P.fz_lazy_ptr = BT_I32(O.flp); P.fz_lazy = BT_I32(O.fl);
-    P.fz_yurg = BT_I32(O.fy); P.fz_meta = BT_I32(O.fm); P.fz_pmeta = BT_I32(O.fpm); P.bs_sync = BT_I32(O.bss); P.fz_rowinfo = BT_I32(O.fri); P.fz_pfirst = BT_I32(O.fpf); P.fz_psecond = BT_I32(O.fps); P.tile_ij = BT_I32(O.tij); P.tile_kx = BT_I32(O.tkx);
-    P.tile_cut8 = reinterpret_cast<const uint16_t *>(b + O.tc8); P.tile_cut16 = reinterpret_cast<const uint16_t *>(b + O.tc16);
-    P.fz_npend = pl->cnt_npend; P.fz_nlazy = pl->cnt_nlazy; P.fz_ok = pl->fz_ok; P.fzp_ok = pl->fzp_ok;
-    P.tile_pair0 = BT_I32(O.tp0); P.tile_npair = BT_I32(O.tnp); P.tile_pairs = BT_I32(O.tps);
-    P.slot_lp = reinterpret_cast<const uint8_t *>(b + O.slp); P.max_tile_pairs = pl->max_tile_pairs; P.max_tile_slots = pl->max_tile_slots; P.max_cams = (int)I.max_tile_cams; P.e_all = pl->e_all;
-    P.slot_code = reinterpret_cast<const uint16_t *>(b + O.sc); P.tile_la = reinterpret_cast<const uint8_t *>(b + O.tla); P.tile_rec = BT_I32(O.trec); P.it_edge = BT_I32(O.ite); P.tile_sinfo = reinterpret_cast<const uint32_t *>(b + O.tsi); P.em_ok = pl->em_ok; P.st_ok = pl->st_ok; P.st_min = pl->st_min; P.em_min = pl->em_min; P.em_its = (int)pl->em_its; P.em_lgs = pl->em_lgs; P.em_self = pl->em_self;
-    P.pm_edge = BT_I32(O.pme); P.pm_rec = BT_I32(O.pmr); P.pm_lb = reinterpret_cast<const uint8_t *>(b + O.pmb); P.pm_la = reinterpret_cast<const uint8_t *>(b + O.pml); P.pm_ok = pl->pm_ok; P.sp_ok = pl->sp_ok; P.wide = pl->wide; P.trk_off = pl->trk_off; P.pp_ptr = BT_I32(O.ppp); P.pp_idx = BT_I32(O.ppi); P.sg_ptr = BT_I32(O.sgp); P.sg_n = pl->sg_n; P.et_lgts = pl->et_lgts;
-    P.lz_trk = BT_I32(O.lzt); P.lz_ptr = BT_I32(O.lzp); P.lz_edge = BT_I32(O.lze); P.lz_pair = BT_I32(O.lzq); P.nlz = pl->nlz;
-#undef BT_I32
+    P.nupd = (int)I.updates; P.max_cams = (int)I.max_tile_cams;
+#define BT_BIND(T, name, solver) P.name = reinterpret_cast<const T *>(b + pl->off[tab::name]);
+    BT_PLAN_TABLES(BT_BIND)
+#undef BT_BIND
 }
 
 // Plans of up to this many edges keep their packed edge list on the device (8 bytes per edge) so that the next edge
@@ -228,49 +208,37 @@ constexpr int64_t kKeepPackedMaxEdges = 4 << 20;
 int upload_plan(bt_plan *pl, const uint64_t *d_packed = nullptr) {
     ApiTick tick;
     std::vector<char> &buf = pl->stage;           // capacity survives with the recycled plan object
-    PlanOffsets &O = pl->off;
     buf.clear();
-    O.kx = put(buf, pl->kx), O.ab = put(buf, pl->act_bits), O.ar = put(buf, pl->act_rank);
-    O.pi = put(buf, pl->pair_i), O.pj = put(buf, pl->pair_j);
-    O.t0 = put(buf, pl->tile_trk0), O.tn = put(buf, pl->tile_ntrk), O.tc = put(buf, pl->tile_ncam);
-    O.c0 = put(buf, pl->tile_cam0), O.s0 = put(buf, pl->tile_slot0), O.sn = put(buf, pl->tile_nslot);
-    O.e0 = put(buf, pl->tile_erow0), O.cams = put(buf, pl->tile_cams);
-    O.se = put(buf, pl->slot_edge), O.sp = put(buf, pl->slot_pair), O.sl = put(buf, pl->slot_lab);
-    O.cp = put(buf, pl->col_ptr), O.ri = put(buf, pl->row_idx), O.up = put(buf, pl->upd_ptr), O.u = put(buf, pl->upd);
-    O.bc = put(buf, pl->blk_col), O.un = put(buf, pl->upd_next);
-    O.lm = put(buf, pl->lvl_meta), O.tf = put(buf, pl->tile_flags);
-    O.tp0 = put(buf, pl->tile_pair0), O.tnp = put(buf, pl->tile_npair), O.tps = put(buf, pl->tile_pairs), O.slp = put(buf, pl->slot_lp);
-    O.pm = put(buf, pl->perm), O.bs = put(buf, pl->blk_src), O.lp = put(buf, pl->lvl_ptr), O.lc = put(buf, pl->lvl_cols);
-    O.cl = put(buf, pl->col_lvl), O.dpp = put(buf, pl->dp_ptr), O.dp = put(buf, pl->dp);
-    O.fpp = put(buf, pl->fz_pend_ptr), O.fp = put(buf, pl->fz_pend), O.flp = put(buf, pl->fz_lazy_ptr), O.fl = put(buf, pl->fz_lazy);
-    O.fy = put(buf, pl->fz_yurg), O.fm = put(buf, pl->fz_meta), O.fpm = put(buf, pl->fz_pmeta), O.bss = put(buf, pl->bs_sync), O.fri = put(buf, pl->fz_rowinfo), O.fpf = put(buf, pl->fz_pfirst), O.fps = put(buf, pl->fz_psecond), O.tij = put(buf, pl->tile_ij), O.tkx = put(buf, pl->tile_kx);
-    O.tc8 = put(buf, pl->tile_cut8), O.tc16 = put(buf, pl->tile_cut16);
-    O.sc = put(buf, pl->slot_code), O.tla = put(buf, pl->tile_la), O.trec = put(buf, pl->tile_rec), O.ite = put(buf, pl->it_edge), O.tsi = put(buf, pl->tile_sinfo);
-    O.pme = put(buf, pl->pm_edge), O.pmr = put(buf, pl->pm_rec), O.pmb = put(buf, pl->pm_lb), O.pml = put(buf, pl->pm_la);
-    O.ppp = put(buf, pl->pp_ptr), O.ppi = put(buf, pl->pp_idx), O.sgp = put(buf, pl->sg_ptr);
-    O.lzt = put(buf, pl->lz_trk), O.lzp = put(buf, pl->lz_ptr), O.lze = put(buf, pl->lz_edge), O.lzq = put(buf, pl->lz_pair);
-    pl->nlz = (int)pl->lz_trk.size();
-    pl->sg_n = pl->sg_ptr.empty() ? 0 : (int)pl->sg_ptr.size() - 1;
+#define BT_PUT(T, name, solver) pl->off[tab::name] = put(buf, pl->name); pl->len[tab::name] = pl->name.size();
+    BT_PLAN_TABLES(BT_PUT)
+#undef BT_PUT
+    PlanDev &P = pl->dev;
+    P.nlev = (int)pl->lvl_ptr.size() - 1; P.ndp = (int)pl->dp.size();
+    P.fz_npend = (int)(pl->fz_pend.size() / 2); P.fz_nlazy = (int)(pl->fz_lazy.size() / 3);
+    P.nlz = (int)pl->lz_trk.size();
+    P.sg_n = pl->sg_ptr.empty() ? 0 : (int)pl->sg_ptr.size() - 1;
     tick("pack arrays");
     size_t cap = 0;
     hipEvent_t reuse_after = nullptr;
-    const bool keep_pk = d_packed && pl->e_all > 0 && pl->e_all <= kKeepPackedMaxEdges && pl->info.E == pl->e_all;
-    // (a plan whose pm_edge is written on the device: the table lies behind the staged bytes, nothing of it crosses PCIe)
+    const bool keep_pk = d_packed && P.e_all > 0 && P.e_all <= kKeepPackedMaxEdges && pl->info.E == P.e_all;
+    // (tables the device writes lie behind the staged bytes, nothing of them crosses PCIe: pm_edge of a plan whose pair-major
+    //  table is written there, the [slots][64] arrays of a 64-track layout and with them the tables of the wave-per-tile kernels)
     size_t tables_end = buf.size();
-    if (pl->dev_pm) { O.pme = (buf.size() + 255) / 256 * 256; tables_end = O.pme + (size_t)pl->pm_rounds * kLanes * sizeof(int32_t); }
-    if (pl->dev_slots) {                                   // likewise the [slots][64] arrays of a 64-track layout
-        const size_t ns = (size_t)pl->info.slots * kLanes;
-        auto take = [&](size_t bytes) { const size_t o = (tables_end + 255) / 256 * 256; tables_end = o + bytes; return o; };
-        O.se = take(ns * sizeof(int32_t)); O.sp = take(ns * sizeof(int32_t)); O.sl = take(ns * sizeof(uint16_t)); O.slp = take(ns);
-        if (pl->dev_wpt) {                                 // ... and the tables of the wave-per-tile kernels
-            O.sc = take(ns * sizeof(uint16_t)); O.tla = take((size_t)pl->info.tiles * kLanes);
-            if (pl->em_ok) { O.ite = take((size_t)pl->em_its * kLanes * sizeof(int32_t)); O.tsi = take((size_t)pl->info.tiles * kLanes * sizeof(uint32_t)); }
+    auto take = [&](int t, size_t n, size_t esz) { pl->off[t] = (tables_end + 255) / 256 * 256; pl->len[t] = n; tables_end = pl->off[t] + n * esz; };
+    if (pl->dev_pm) take(tab::pm_edge, (size_t)pl->pm_rounds * kLanes, sizeof(int32_t));
+    if (pl->dev_slots) {
+        const size_t ns = (size_t)pl->info.slots * kLanes, tl = (size_t)pl->info.tiles * kLanes;
+        take(tab::slot_edge, ns, sizeof(int32_t)); take(tab::slot_pair, ns, sizeof(int32_t)); take(tab::slot_lab, ns, sizeof(uint16_t)); take(tab::slot_lp, ns, 1);
+        if (pl->dev_wpt) {
+            take(tab::slot_code, ns, sizeof(uint16_t)); take(tab::tile_la, tl, 1);
+            if (P.em_ok) { take(tab::it_edge, (size_t)P.em_its * kLanes, sizeof(int32_t)); take(tab::tile_sinfo, tl, sizeof(uint32_t)); }
         }
     }
-    const size_t pk_off = (tables_end + 255) / 256 * 256, total = keep_pk ? pk_off + (size_t)pl->e_all * sizeof(uint64_t) : tables_end;
+    const size_t pk_off = (tables_end + 255) / 256 * 256, total = keep_pk ? pk_off + (size_t)P.e_all * sizeof(uint64_t) : tables_end;
     void *d = dev_pool().acquire(total + 256, &cap, &reuse_after);
     if (!d) return BT_ENOMEM;
-    if (hipGetDevice(&pl->dev_id) != hipSuccess) pl->dev_id = 0;      // (once per plan: its launches take their per-device figures from it)
+    if (hipGetDevice(&P.dev_id) != hipSuccess) P.dev_id = 0;          // (once per plan: its launches take their per-device figures from it)
+    bind_pointers(pl, d);                                  // (the fill kernels below read the plan's tile tables in the buffer)
     tick("device buffer");
     hipStream_t cs = copy_stream();
     // a recycled buffer may still be read by kernels of the destroyed plan queued on the caller's stream: the upload
@@ -279,36 +247,33 @@ int upload_plan(bt_plan *pl, const uint64_t *d_packed = nullptr) {
     if (!waited) (void)hipEventSynchronize(reuse_after);
     dev_pool().give_event(reuse_after);
     bool ok = hipMemcpyAsync(d, buf.data(), buf.size(), hipMemcpyHostToDevice, cs) == hipSuccess &&
-              (!keep_pk || hipMemcpyAsync(static_cast<char *>(d) + pk_off, d_packed, (size_t)pl->e_all * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs) == hipSuccess);
+              (!keep_pk || hipMemcpyAsync(static_cast<char *>(d) + pk_off, d_packed, (size_t)P.e_all * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs) == hipSuccess);
     if (ok && (pl->dev_pm || pl->dev_slots)) {
-        bind_pointers(pl, d);                          // (the fill kernels read the plan's tile tables in the buffer)
         char *db = static_cast<char *>(d);
+        auto at = [&](int t) { return db + pl->off[t]; };
         if (pl->dev_pm)
-            ok = plan_device_fill(pl, pl->info.E, reinterpret_cast<int32_t *>(db + O.pmr), reinterpret_cast<int32_t *>(db + O.pme), pl->pm_rounds, cs) == BT_OK;
+            ok = plan_device_fill(pl, pl->info.E, reinterpret_cast<int32_t *>(at(tab::pm_rec)), reinterpret_cast<int32_t *>(at(tab::pm_edge)), pl->pm_rounds, cs) == BT_OK;
         else {
             DevWptOut w{};
             if (pl->dev_wpt) {
-                w.slot_code = reinterpret_cast<uint16_t *>(db + O.sc); w.tile_la = reinterpret_cast<uint8_t *>(db + O.tla); w.tile_rec = reinterpret_cast<int32_t *>(db + O.trec);
-                if (pl->em_ok) { w.it_edge = reinterpret_cast<int32_t *>(db + O.ite); w.tile_sinfo = reinterpret_cast<uint32_t *>(db + O.tsi); w.its = pl->em_its; }
+                w.slot_code = reinterpret_cast<uint16_t *>(at(tab::slot_code)); w.tile_la = reinterpret_cast<uint8_t *>(at(tab::tile_la));
+                w.tile_rec = reinterpret_cast<int32_t *>(at(tab::tile_rec));
+                if (P.em_ok) { w.it_edge = reinterpret_cast<int32_t *>(at(tab::it_edge)); w.tile_sinfo = reinterpret_cast<uint32_t *>(at(tab::tile_sinfo)); w.its = P.em_its; }
             }
-            ok = plan_device_slots_fill(pl, pl->info.E, reinterpret_cast<int32_t *>(db + O.se), reinterpret_cast<int32_t *>(db + O.sp),
-                                        reinterpret_cast<uint16_t *>(db + O.sl), reinterpret_cast<uint8_t *>(db + O.slp),
-                                        reinterpret_cast<uint16_t *>(db + O.tc8), reinterpret_cast<uint16_t *>(db + O.tc16), cs, pl->dev_wpt ? &w : nullptr) == BT_OK;
+            ok = plan_device_slots_fill(pl, pl->info.E, reinterpret_cast<int32_t *>(at(tab::slot_edge)), reinterpret_cast<int32_t *>(at(tab::slot_pair)),
+                                        reinterpret_cast<uint16_t *>(at(tab::slot_lab)), reinterpret_cast<uint8_t *>(at(tab::slot_lp)),
+                                        reinterpret_cast<uint16_t *>(at(tab::tile_cut8)), reinterpret_cast<uint16_t *>(at(tab::tile_cut16)), cs,
+                                        pl->dev_wpt ? &w : nullptr) == BT_OK;
         }
     }
     if (!ok || hipStreamSynchronize(cs) != hipSuccess) { dev_pool().release(d, cap, false, nullptr); return BT_EHIP; }
     // (k_plan_sinfo's verdict: a tile whose tracks do not share their slots' pairs leaves the plan with k_stream)
-    if (pl->dev_slots && pl->dev_wpt && pl->em_ok && plan_device_em_verdict()) { pl->em_ok = 0; pl->em_its = 0; pl->em_lgs = -1; }
+    if (pl->dev_slots && pl->dev_wpt && P.em_ok && plan_device_em_verdict()) { P.em_ok = 0; P.em_its = 0; P.em_lgs = -1; }
     tick("H2D copy");
     pl->dev_base = d;
     pl->dev_cap = cap;
     pl->dev_bytes = total;
     pl->pk_off = keep_pk ? pk_off : 0;
-    pl->n_act_words = (int)pl->act_bits.size(); pl->n_tile_ij = (int)pl->tile_ij.size();
-    pl->cnt_nlev = (int)pl->lvl_ptr.size() - 1; pl->cnt_ndp = (int)pl->dp.size();
-    pl->cnt_npend = (int)(pl->fz_pend.size() / 2); pl->cnt_nlazy = (int)(pl->fz_lazy.size() / 3);
-    bind_pointers(pl, d);
-    PlanDev &P = pl->dev;
     const int rc = configure_kernels(P);
     tick("configure kernels");
     return rc;
@@ -462,13 +427,11 @@ static int clone_shifted(const bt_plan *src, const uint64_t *d_words, int64_t E,
     ApiTick tick;
     bt_plan *pl = plan_pool().take();
     if (!pl) return BT_ENOMEM;
+    // (its dev_pm / dev_slots / dev_wpt stay 0: every table of the clone is in its buffer, none is written there by a planner pass)
     pl->info = src->info; pl->info.fixedp = fixedp; pl->info.n_all = src->info.n_all + di;
-    pl->ws = src->ws; pl->off = src->off; pl->dev_bytes = src->dev_bytes; pl->pk_off = src->pk_off;
-    pl->n_act_words = src->n_act_words; pl->n_tile_ij = src->n_tile_ij;
-    pl->cnt_nlev = src->cnt_nlev; pl->cnt_ndp = src->cnt_ndp; pl->cnt_npend = src->cnt_npend; pl->cnt_nlazy = src->cnt_nlazy;
-    pl->max_rows16 = src->max_rows16; pl->max_tile_pairs = src->max_tile_pairs; pl->max_tile_slots = src->max_tile_slots;
-    pl->fz_ok = src->fz_ok; pl->fzp_ok = src->fzp_ok; pl->em_ok = src->em_ok; pl->st_ok = src->st_ok; pl->st_min = src->st_min; pl->em_min = src->em_min; pl->em_its = src->em_its; pl->em_lgs = src->em_lgs;
-    pl->em_self = src->em_self; pl->e_all = src->e_all; pl->pm_ok = src->pm_ok; pl->sp_ok = src->sp_ok; pl->wide = src->wide; pl->nlz = src->nlz; pl->dev_id = src->dev_id; pl->sg_n = src->sg_n; pl->et_lgts = src->et_lgts; pl->dev_pm = 0; pl->dev_slots = 0; pl->dev_wpt = 0; pl->trk_off = src->trk_off; pl->pm_rounds = src->pm_rounds; pl->k_hi = src->k_hi >= 0 ? src->k_hi + dk : -1;
+    pl->ws = src->ws; pl->off = src->off; pl->len = src->len; pl->dev_bytes = src->dev_bytes; pl->pk_off = src->pk_off; pl->pm_rounds = src->pm_rounds;
+    pl->dev = src->dev;
+    pl->k_hi = src->k_hi >= 0 ? src->k_hi + dk : -1;
     size_t cap = 0;
     hipEvent_t reuse_after = nullptr;
     void *d = dev_pool().acquire(pl->dev_bytes + 256, &cap, &reuse_after);
@@ -478,8 +441,7 @@ static int clone_shifted(const bt_plan *src, const uint64_t *d_words, int64_t E,
     dev_pool().give_event(reuse_after);
     char *nb = static_cast<char *>(d);
     const char *ob = static_cast<const char *>(src->dev_base);
-    const PlanOffsets &O = pl->off;
-    auto I32 = [&](size_t off) { return reinterpret_cast<int32_t *>(nb + off); };
+    auto I32 = [&](int t) { return reinterpret_cast<int32_t *>(nb + pl->off[t]); };
     int rc = BT_OK;
     // the tables as they are, the new packed edge list behind them, then the ones that hold absolute frame / patch numbers
     // (d_words null — a clone made ahead of its list, bt_plan_preshift: the list it expects, the source's words moved by the shift)
@@ -488,9 +450,9 @@ static int clone_shifted(const bt_plan *src, const uint64_t *d_words, int64_t E,
     else rc = launch_words_add(reinterpret_cast<const uint64_t *>(ob + src->pk_off), ((uint64_t)dk << 32) | ((uint64_t)di << 16) | (uint64_t)di,
                                reinterpret_cast<uint64_t *>(nb + pl->pk_off), E, cs);
     if (rc == BT_OK)
-        rc = launch_plan_shift(I32(O.kx), (int)pl->info.m, I32(O.tkx), (int)pl->info.tiles * kLanes, I32(O.tij), pl->n_tile_ij, I32(O.pi), I32(O.pj),
-                               (int)pl->info.pairs, reinterpret_cast<const uint32_t *>(ob + O.ab), reinterpret_cast<uint32_t *>(nb + O.ab), I32(O.ar),
-                               pl->n_act_words, (int)di, (int)dk, cs);
+        rc = launch_plan_shift(I32(tab::kx), (int)pl->info.m, I32(tab::tile_kx), (int)pl->info.tiles * kLanes, I32(tab::tile_ij), (int)pl->len[tab::tile_ij],
+                               I32(tab::pair_i), I32(tab::pair_j), (int)pl->info.pairs, reinterpret_cast<const uint32_t *>(ob + pl->off[tab::act_bits]),
+                               reinterpret_cast<uint32_t *>(nb + pl->off[tab::act_bits]), I32(tab::act_rank), (int)pl->len[tab::act_bits], (int)di, (int)dk, cs);
     // no host wait for the copies: the plan's first launches are ordered behind this event on whatever stream they use
     hipEvent_t ready = rc == BT_OK ? dev_pool().take_event() : nullptr;
     if (rc == BT_OK && (!ready || hipEventRecord(ready, cs) != hipSuccess)) {
@@ -540,7 +502,7 @@ int bt_plan_create_shifted_spec(const bt_plan *src, const int64_t *ii, const int
     *out = nullptr;
     if (!src || !ii || !jj || !kk || E <= 0) return BT_EINVAL;
     if (n_buf > 32768 || p_tot > (int64_t)0x7fffffff || n_buf <= 0 || p_tot % n_buf != 0) return BT_NO_MATCH;
-    if (!src->dev_base || !src->pk_off || src->e_all != E || src->info.E != E || src->info.n_buf != n_buf || src->info.p_tot != p_tot) return BT_NO_MATCH;
+    if (!src->dev_base || !src->pk_off || src->dev.e_all != E || src->info.E != E || src->info.n_buf != n_buf || src->info.p_tot != p_tot) return BT_NO_MATCH;
     if (src->spec_ev || src->spec_epoch || src->spec_unbound) return BT_NO_MATCH;   // (an unconfirmed speculation is no source)
     const int64_t di = fixedp - src->info.fixedp, dk = di * (p_tot / n_buf);
     // every number the clone's tables will hold stays inside the caller's buffers, whatever the new list turns out to be
@@ -585,7 +547,7 @@ int bt_plan_preshift(const bt_plan *src, int64_t df, bt_plan **out) {
     if (!out) return BT_EINVAL;
     *out = nullptr;
     if (!src) return BT_EINVAL;
-    const int64_t n_buf = src->info.n_buf, p_tot = src->info.p_tot, E = src->e_all;
+    const int64_t n_buf = src->info.n_buf, p_tot = src->info.p_tot, E = src->dev.e_all;
     if (!src->dev_base || !src->pk_off || E <= 0 || src->info.E != E || src->spec_ev || src->spec_epoch || src->spec_unbound) return BT_NO_MATCH;
     if (n_buf <= 0 || n_buf > 32768 || p_tot > (int64_t)0x7fffffff || p_tot % n_buf != 0) return BT_NO_MATCH;
     const int64_t dk = df * (p_tot / n_buf);
@@ -602,7 +564,7 @@ int bt_plan_spec_bind(bt_plan *pl, const int64_t *ii, const int64_t *jj, const i
                       int64_t fixedp, void *in_stream) {
     if (!pl || !ii || !jj || !kk) return BT_EINVAL;
     if (!pl->spec_unbound || !pl->dev_base) return BT_EINVAL;
-    if (pl->e_all != E || pl->info.n_buf != n_buf || pl->info.p_tot != p_tot || pl->info.fixedp != fixedp) return BT_NO_MATCH;
+    if (pl->dev.e_all != E || pl->info.n_buf != n_buf || pl->info.p_tot != p_tot || pl->info.fixedp != fixedp) return BT_NO_MATCH;
     ApiTick tick;
     int *h_flag;
     unsigned *ticket;
@@ -611,7 +573,7 @@ int bt_plan_spec_bind(bt_plan *pl, const int64_t *ii, const int64_t *jj, const i
         std::lock_guard<std::mutex> g(spec_mutex());
         SpecSlots &ss = spec_slots();
         if (!ss.ensure()) return BT_ENOMEM;
-        unsigned *tk = ss.tickets_of(pl->dev_id);
+        unsigned *tk = ss.tickets_of(pl->dev.dev_id);
         if (!tk) return BT_ENOMEM;
         const unsigned slot = ss.next++ % 16;
         h_flag = ss.h + 4 * slot; ticket = tk + slot;
@@ -684,7 +646,7 @@ int bt_plan_create_shifted_any(const bt_plan *const *srcs, int nsrc, const int64
     for (int q = 0; q < nsrc && nc < kMaxShiftSources; ++q) {
         const bt_plan *src = srcs[q];
         if (!src) return BT_EINVAL;
-        if (!src->dev_base || !src->pk_off || src->e_all != E || src->info.E != E || src->info.n_buf != n_buf || src->info.p_tot != p_tot) continue;
+        if (!src->dev_base || !src->pk_off || src->dev.e_all != E || src->info.E != E || src->info.n_buf != n_buf || src->info.p_tot != p_tot) continue;
         if (src->spec_ev || src->spec_epoch || src->spec_unbound) continue;
         cand[nc] = src; idx[nc++] = q;
     }
@@ -757,10 +719,21 @@ int bt_plan_get_info(const bt_plan *pl, bt_plan_info *info) {
 
 size_t bt_plan_workspace_bytes(const bt_plan *pl) { return pl ? pl->ws.total : 0; }
 
+// The tables bt_plan_array reads back from the plan's buffer: those the device wrote or amended (upload_plan)
+static bool device_written(const bt_plan *pl, int t) {
+    if (!pl->dev_base) return false;
+    switch (t) {
+    case tab::pm_edge: case tab::pm_rec: return pl->dev_pm != 0;
+    case tab::slot_edge: case tab::slot_pair: case tab::slot_lab: case tab::slot_lp: case tab::tile_cut8: case tab::tile_cut16: return pl->dev_slots != 0;
+    case tab::slot_code: case tab::tile_la: case tab::tile_rec: return pl->dev_slots && pl->dev_wpt;
+    case tab::it_edge: case tab::tile_sinfo: return pl->dev_slots && pl->dev_wpt && pl->dev.em_ok;
+    default: return false;
+    }
+}
+
 int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
     if (!pl || !name || !data) return -1;
-#define BT_ARR(n)                                                        \
-    if (std::strcmp(name, #n) == 0) { *data = pl->n.data(); return (int64_t)pl->n.size(); }
+    if (std::strcmp(name, "trk_loc") == 0) { *data = pl->trk_loc.data(); return (int64_t)pl->trk_loc.size(); }
     if (std::strcmp(name, "trk_of_patch") == 0) {            // kept for the window of patches only: expanded here (tests, tooling)
         pl->trk_of_patch.assign((size_t)pl->info.p_tot, -1);
         for (size_t i = 0; i < pl->trk_win.size(); ++i) pl->trk_of_patch[(size_t)pl->trk_win_lo + i] = pl->trk_win[i];
@@ -780,48 +753,22 @@ int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
         return 1;
     }
     if (std::strcmp(name, "trk_off") == 0) {                  // sharded: distinct tracks in front of the rank's range (one element)
-        pl->dev_readback.assign(1, (int32_t)pl->trk_off);
+        pl->dev_readback.assign(1, (int32_t)pl->dev.trk_off);
         *data = pl->dev_readback.data();
         return 1;
     }
-    if (pl->dev_slots && pl->dev_base) {
-        // a 64-track plan whose slot arrays and wave cuts were written on the device: read back on request (tests, tooling)
-        const size_t ns = (size_t)pl->info.slots * kLanes, T = (size_t)pl->info.tiles;
-        size_t off = 0, bytes = 0, esz = 4;
-        if (std::strcmp(name, "slot_edge") == 0) { off = pl->off.se; bytes = ns * 4; }
-        else if (std::strcmp(name, "slot_pair") == 0) { off = pl->off.sp; bytes = ns * 4; }
-        else if (std::strcmp(name, "slot_lab") == 0) { off = pl->off.sl; bytes = ns * 2; esz = 2; }
-        else if (std::strcmp(name, "slot_lp") == 0) { off = pl->off.slp; bytes = ns; esz = 1; }
-        else if (std::strcmp(name, "tile_cut8") == 0) { off = pl->off.tc8; bytes = T * 9 * 2; esz = 2; }
-        else if (std::strcmp(name, "tile_cut16") == 0) { off = pl->off.tc16; bytes = T * 17 * 2; esz = 2; }
-        else if (pl->dev_wpt && std::strcmp(name, "slot_code") == 0) { off = pl->off.sc; bytes = ns * 2; esz = 2; }
-        else if (pl->dev_wpt && std::strcmp(name, "tile_la") == 0) { off = pl->off.tla; bytes = T * kLanes; esz = 1; }
-        else if (pl->dev_wpt && std::strcmp(name, "tile_rec") == 0) { off = pl->off.trec; bytes = T * 8 * 4; }
-        else if (pl->dev_wpt && pl->em_ok && std::strcmp(name, "it_edge") == 0) { off = pl->off.ite; bytes = (size_t)pl->em_its * kLanes * 4; }
-        else if (pl->dev_wpt && pl->em_ok && std::strcmp(name, "tile_sinfo") == 0) { off = pl->off.tsi; bytes = T * kLanes * 4; }
-        if (bytes) {
-            std::vector<int32_t> &v = pl->dev_readback;
-            v.assign((bytes + 3) / 4, 0);
-            if (hipMemcpy(v.data(), static_cast<const char *>(pl->dev_base) + off, bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-            *data = v.data();
-            return (int64_t)(bytes / esz);
-        }
-    }
-    if (pl->dev_pm && pl->dev_base && (std::strcmp(name, "pm_edge") == 0 || std::strcmp(name, "pm_rec") == 0)) {
-        // a plan whose pair-major table was written on the device: read back on request (tests, tooling)
-        const bool edge = name[3] == 'e';
-        std::vector<int32_t> &v = pl->dev_readback;
-        v.assign(edge ? (size_t)pl->pm_rounds * kLanes : (size_t)pl->info.tiles * 4, 0);
-        if (hipMemcpy(v.data(), static_cast<const char *>(pl->dev_base) + (edge ? pl->off.pme : pl->off.pmr), v.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        *data = v.data();
-        return (int64_t)v.size();
-    }
-    BT_ARR(kx) BT_ARR(trk_loc) BT_ARR(pair_i) BT_ARR(pair_j) BT_ARR(pp_ptr) BT_ARR(pp_idx) BT_ARR(sg_ptr)
-    BT_ARR(tile_trk0) BT_ARR(tile_ntrk) BT_ARR(tile_ncam) BT_ARR(tile_cam0) BT_ARR(tile_slot0)
-    BT_ARR(tile_nslot) BT_ARR(tile_erow0) BT_ARR(tile_cams) BT_ARR(slot_edge) BT_ARR(slot_pair)
-    BT_ARR(slot_lab) BT_ARR(col_ptr) BT_ARR(row_idx) BT_ARR(upd_ptr) BT_ARR(upd) BT_ARR(blk_col) BT_ARR(upd_next) BT_ARR(perm) BT_ARR(blk_src) BT_ARR(lvl_ptr) BT_ARR(lvl_cols)
-    BT_ARR(col_lvl) BT_ARR(dp_ptr) BT_ARR(dp) BT_ARR(tile_pair0) BT_ARR(tile_npair) BT_ARR(tile_pairs) BT_ARR(slot_lp) BT_ARR(tile_flags)
-    BT_ARR(fz_pend_ptr) BT_ARR(fz_pend) BT_ARR(fz_lazy_ptr) BT_ARR(fz_lazy) BT_ARR(fz_yurg) BT_ARR(fz_meta) BT_ARR(fz_pmeta) BT_ARR(bs_sync) BT_ARR(fz_rowinfo) BT_ARR(fz_pfirst) BT_ARR(fz_psecond) BT_ARR(act_bits) BT_ARR(act_rank) BT_ARR(tile_ij) BT_ARR(tile_kx) BT_ARR(lvl_meta) BT_ARR(slot_code) BT_ARR(tile_la) BT_ARR(tile_rec) BT_ARR(it_edge) BT_ARR(tile_sinfo) BT_ARR(tile_cut8) BT_ARR(tile_cut16) BT_ARR(pm_edge) BT_ARR(pm_rec) BT_ARR(pm_lb) BT_ARR(pm_la)
+    // an uploaded table: the host's vector, or — a table the device wrote — read back on request (tests, tooling)
+    const auto table = [&](int t, const auto &v) -> int64_t {
+        if (!device_written(pl, t)) { *data = v.data(); return (int64_t)v.size(); }
+        const size_t bytes = pl->len[t] * sizeof(v[0]);
+        std::vector<int32_t> &r = pl->dev_readback;
+        r.assign((bytes + 3) / 4, 0);
+        if (hipMemcpy(r.data(), static_cast<const char *>(pl->dev_base) + pl->off[t], bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        *data = r.data();
+        return (int64_t)pl->len[t];
+    };
+#define BT_ARR(T, n, solver) if (std::strcmp(name, #n) == 0) return table(tab::n, pl->n);
+    BT_PLAN_TABLES(BT_ARR)
 #undef BT_ARR
     return -1;
 }

@@ -93,7 +93,7 @@ static void layout_workspace(bt_plan *pl) {
     w.pairacc = off;  off += (size_t)I.pairs * kPairAccStride * sizeof(double);
     off = align_up(off, 256);
     w.priv = 0;
-    if (I.tiles >= pl->em_min) {       // (plans k_edge2 can take: by the tile count alone — whether the tiles are slot-uniform is, for
+    if (I.tiles >= pl->dev.em_min) {   // (plans k_edge2 can take: by the tile count alone — whether the tiles are slot-uniform is, for
                                        //  a device-planned list, known only after the upload, and the layout must not depend on the planner)
         w.priv = off;
         off = align_up(off + priv_doubles(D, (size_t)I.pairs) * sizeof(double), 256);
@@ -103,16 +103,16 @@ static void layout_workspace(bt_plan *pl) {
     w.pairgeo = off;  off = align_up(off + (size_t)I.pairs * kPairGeomFloats * sizeof(double), 256);         // k_tile -> k_pair_finalize (float or double)
     w.qw = off;       off = align_up(off + (size_t)I.m * 2 * sizeof(double), 256);                           // (Q, w') per track (float2 or double2)
     // (a wide plan's dense factor: D x D doubles and the right-hand side behind it)
-    w.lfac = off;     off = align_up(off + (pl->wide ? (D * D + D) * sizeof(double) : (size_t)I.nnz_blocks * 36 * sizeof(float)), 256);
+    w.lfac = off;     off = align_up(off + (pl->dev.wide ? (D * D + D) * sizeof(double) : (size_t)I.nnz_blocks * 36 * sizeof(float)), 256);
     w.linv = off;     off = align_up(off + (size_t)I.n * 36 * sizeof(float), 256);
     w.zvec = off;     off = align_up(off + D * sizeof(float), 256);
     w.dx = off;       off = align_up(off + D * sizeof(float) + 64, 256);
     w.dx0 = off;      off = align_up(off + D * sizeof(float) + 64, 256);     // first solution of a refined solve (float32-factor systems)
     w.status = off;   off = align_up(off + kStatusBytes, 256);
     w.spart = off;
-    if (pl->sp_ok) off = align_up(off + (size_t)I.tiles * sp_tile_doubles(pl->max_rows16, pl->max_tile_pairs) * sizeof(double), 256);
+    if (pl->dev.sp_ok) off = align_up(off + (size_t)I.tiles * sp_tile_doubles(pl->dev.max_rows16, pl->dev.max_tile_pairs) * sizeof(double), 256);
     w.esave = off;                                                 // k_etile -> k_etile_upd: the tiles' E, [tile][max_rows16][1 << et_lgts]
-    if (pl->sp_ok) off = align_up(off + (((size_t)I.tiles * pl->max_rows16) << pl->et_lgts) * sizeof(double), 256);
+    if (pl->dev.sp_ok) off = align_up(off + (((size_t)I.tiles * pl->dev.max_rows16) << pl->dev.et_lgts) * sizeof(double), 256);
     w.total = off;
     pl->ws = w;
     pl->info.workspace_bytes = (int64_t)w.total;
@@ -148,7 +148,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     bt_plan_info &I = pl->info;
     I = bt_plan_info{};
     I.n_buf = n_buf; I.p_tot = p_tot; I.fixedp = fixedp;
-    pl->e_all = E;
+    pl->dev.e_all = E;
     // A plan of a SHARDED solve (the caller named a track range, whatever it covers): the ranks exchange [S | y] block by block of the
     // factor's pattern, so every rank must arrive at the same pattern — from what all of them can see, the tracks of the whole list.
     const bool sharded = own_hi > 0;
@@ -247,15 +247,15 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     pp_lo = kmin; pp_hi = kmax;
     // sharded plan: the number of distinct tracks in front of this rank's range — a per-track lmbda tensor (ba.py:299-300) is
     // indexed by the GLOBAL track number, the kernels count from the rank's first track
-    pl->trk_off = 0;
+    pl->dev.trk_off = 0;
     if (dstats) {
-        if (dstats->sliced) pl->trk_off = (int)dstats->trk_before;
-        else for (int64_t k = kmin; k < std::min(own_lo, kmax + 1); ++k) pl->trk_off += dstats->tab[(size_t)(k - dstats->tab_lo)].cnt > 0 ? 1 : 0;
+        if (dstats->sliced) pl->dev.trk_off = (int)dstats->trk_before;
+        else for (int64_t k = kmin; k < std::min(own_lo, kmax + 1); ++k) pl->dev.trk_off += dstats->tab[(size_t)(k - dstats->tab_lo)].cnt > 0 ? 1 : 0;
     } else if (E_own != E && own_lo > 0) {
         std::vector<uint8_t> seen((size_t)own_lo, 0);
-        for (int64_t e = 0; e < E; ++e) { const int64_t k = KK(e); if (k < own_lo && !seen[(size_t)k]) { seen[(size_t)k] = 1; ++pl->trk_off; } }
+        for (int64_t e = 0; e < E; ++e) { const int64_t k = KK(e); if (k < own_lo && !seen[(size_t)k]) { seen[(size_t)k] = 1; ++pl->dev.trk_off; } }
     }
-    pl->em_self = any_self ? 1 : 0;
+    pl->dev.em_self = any_self ? 1 : 0;
     if (E == 0) f_lo = 0;
     I.n_all = n_all;
     I.sorted_input = sorted ? 1 : 0;
@@ -564,7 +564,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     }
     const int32_t T = (int32_t)pl->tile_trk0.size();
     I.tiles = T; I.slots = slots; I.erows = erows; I.max_tile_cams = max_cams;
-    pl->max_rows16 = (int)((6 * max_cams + 15) / 16 * 16);
+    pl->dev.max_rows16 = (int)((6 * max_cams + 15) / 16 * 16);
     if (tcap < kLanes && T >= std::min(std::min(em_min_p, st_min_p), 1024)) {
         // the camera limit closed 16-track tiles early: the plan reached the tile count of the wave-per-tile kernels, whose
         // tables come from the [slots][64] arrays a small-tile plan does not have — or simply four times the CUs, where
@@ -601,7 +601,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     pl->slot_lp.assign(slot_elems, 0);
     pl->tile_pair0.assign((size_t)T, 0); pl->tile_npair.assign((size_t)T, 0);
     pl->tile_pairs.clear();
-    pl->max_tile_pairs = 0;
+    pl->dev.max_tile_pairs = 0;
     // tile_cut8 / tile_cut16: where k_tile's 8 or 16 waves split the tile's slots.  Repeated observations of one (track,
     // target camera) are consecutive slots of that track; a wave sums such a run in registers and writes it once, but a run
     // that continues into the next wave's chunk forces LDS float atomics on every slot of it (~500 cycles per wave
@@ -793,7 +793,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
             pl->tile_pair0[(size_t)t] = (int32_t)pl->tile_pairs.size();
             pl->tile_npair[(size_t)t] = (int32_t)mine.size();
             pl->tile_pairs.insert(pl->tile_pairs.end(), mine.begin(), mine.end());
-            pl->max_tile_pairs = std::max(pl->max_tile_pairs, (int)mine.size());
+            pl->dev.max_tile_pairs = std::max(pl->dev.max_tile_pairs, (int)mine.size());
             for (int32_t q : mine) lp_of[(size_t)q] = -1;
         }
     }
@@ -834,19 +834,18 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     // which the block-sparse solvers can only hold as float32 (or in global memory) — 24 ms a solve at 179 poses and a float32
     // factor's precision, against the dense solver's 3 ms in double.
     const auto go_wide = [&]() {
-        pl->wide = 1;
+        pl->dev.wide = 1;
+#define BT_CLEAR_SOLVER(T, name, solver) if (solver) pl->name.clear();
+        BT_PLAN_TABLES(BT_CLEAR_SOLVER)
+#undef BT_CLEAR_SOLVER
         pl->perm.resize((size_t)n);
         std::iota(pl->perm.begin(), pl->perm.end(), 0);
         pl->col_ptr.assign((size_t)n + 1, 0); pl->upd_ptr.assign((size_t)n + 1, 0); pl->upd_next.assign((size_t)n + 1, 0);
         pl->lvl_ptr.assign(1, 0); pl->dp_ptr.assign((size_t)n + 1, 0);
-        for (auto *v : {&pl->row_idx, &pl->upd, &pl->blk_col, &pl->blk_src, &pl->lvl_cols, &pl->col_lvl, &pl->dp, &pl->lvl_meta, &pl->fz_pend_ptr,
-                        &pl->fz_pend, &pl->fz_lazy_ptr, &pl->fz_lazy, &pl->fz_yurg, &pl->fz_meta, &pl->fz_pmeta, &pl->bs_sync, &pl->fz_rowinfo,
-                        &pl->fz_pfirst, &pl->fz_psecond})
-            v->clear();
-        pl->fz_ok = 0; pl->fzp_ok = 0;
+        pl->dev.fz_ok = 0; pl->dev.fzp_ok = 0;
         I.nnz_blocks = n * (n + 1) / 2; I.updates = 0;
     };
-    pl->wide = 0;
+    pl->dev.wide = 0;
     if (n > kMaxFree) go_wide();
     const auto symbolic = [&]() -> int {
     // ---- block structure of S (lower) and symbolic Cholesky ----------------
@@ -1244,11 +1243,11 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
             }
         }
         pl->fz_meta.assign((size_t)nlev * kMaxLevelCols * 8, 0);
-        pl->fz_ok = (pl->fz_lazy.size() / 3 < 65536 && pl->row_idx.size() < 32768 && pend_ok) ? 1 : 0;
-        pl->fzp_ok = pl->fz_ok;                          // additionally: every column's panel rows (+ y) fit one wave
-        for (int64_t j = 0; j < n; ++j) if (6 * (pl->col_ptr[(size_t)j + 1] - pl->col_ptr[(size_t)j] - 1) + 1 > 64) pl->fzp_ok = 0;
+        pl->dev.fz_ok = (pl->fz_lazy.size() / 3 < 65536 && pl->row_idx.size() < 32768 && pend_ok) ? 1 : 0;
+        pl->dev.fzp_ok = pl->dev.fz_ok;                          // additionally: every column's panel rows (+ y) fit one wave
+        for (int64_t j = 0; j < n; ++j) if (6 * (pl->col_ptr[(size_t)j + 1] - pl->col_ptr[(size_t)j] - 1) + 1 > 64) pl->dev.fzp_ok = 0;
         for (int32_t l = 0; l < nlev; ++l) {
-            if (pl->lvl_ptr[(size_t)l + 1] - pl->lvl_ptr[(size_t)l] > 2) { pl->fz_ok = 0; pl->fzp_ok = 0; }
+            if (pl->lvl_ptr[(size_t)l + 1] - pl->lvl_ptr[(size_t)l] > 2) { pl->dev.fz_ok = 0; pl->dev.fzp_ok = 0; }
             int32_t w0 = 0;
             for (int q = 0; q < kMaxLevelCols; ++q) {
                 int32_t *mrow = pl->fz_meta.data() + ((size_t)l * kMaxLevelCols + q) * 8;
@@ -1265,7 +1264,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
 
     return BT_OK;
     };
-    if (!pl->wide) {
+    if (!pl->dev.wide) {
         const int src_rc = symbolic();
         if (src_rc != BT_OK) return src_rc;
         // The factor does not fit LDS as double: float32 with refinement, or the dense solver — whichever is priced lower.  Measured
@@ -1288,7 +1287,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     //   tile_ij[t][max_tile_pairs]   cameras (i | j << 16) of the tile's pairs, in local pair order
     //   tile_kx[t][64]               patch of every track of the tile (-1: no track in this lane)
     {
-        const size_t mtp = (size_t)std::max(pl->max_tile_pairs, 1);
+        const size_t mtp = (size_t)std::max(pl->dev.max_tile_pairs, 1);
         pl->tile_ij.assign((size_t)I.tiles * mtp, 0);
         pl->tile_kx.assign((size_t)I.tiles * kLanes, -1);
         for (int64_t t = 0; t < I.tiles; ++t) {
@@ -1307,8 +1306,8 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     //   [0] ntrk | ncam << 8 | npair << 16 | flags << 24   [1] slot0  [2] nslot  [3] cam0  [4] pair0  [5] trk0
     const bool want_stream_tables = want_slots && I.tiles >= std::min(em_min_p, st_min_p);   // (they are made from the slot arrays)
     const bool dev_wpt = dev_slots && I.tiles >= std::min(em_min_p, st_min_p);               // (... where those are: on the device)
-    pl->st_ok = want_stream_tables || dev_wpt ? 1 : 0;
-    pl->st_min = st_min_p; pl->em_min = em_min_p;
+    pl->dev.st_ok = want_stream_tables || dev_wpt ? 1 : 0;
+    pl->dev.st_min = st_min_p; pl->dev.em_min = em_min_p;
     pl->dev_wpt = dev_wpt ? 1 : 0;
     if (dev_wpt) {
         // the records but for the straddle flag (k_plan_slots adds it); slot_code, tile_la, it_edge and tile_sinfo are written
@@ -1363,60 +1362,62 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     //   tile_sinfo[t * 64 + s]           local target camera | local pair << 8 | repeat << 16 | used << 17   (s < S)
     //                                    repeat: this slot or a neighbour holds the same pair again (repeated observation)
     //   tile_rec[6] = it0, tile_rec[7] = log2 S | iterations << 8
-    pl->em_ok = 0; pl->em_its = 0; pl->em_lgs = -1;
+    pl->dev.em_ok = 0; pl->dev.em_its = 0; pl->dev.em_lgs = -1;
     if (dev_wpt && I.tiles >= em_min_p) {
         // (the iteration counts follow from the tiles' slot and track counts; whether every tile is slot-uniform is k_plan_sinfo's
         //  verdict, read back by upload_plan: em_ok here is "as far as the host can tell")
-        pl->em_ok = 1;
+        pl->dev.em_ok = 1;
         int64_t its = 0;
         for (int64_t t = 0; t < I.tiles; ++t) {
             const int32_t ns = pl->tile_nslot[(size_t)t], nt = pl->tile_ntrk[(size_t)t];
             int lg = 0;
             while ((1 << lg) < ns) ++lg;
-            if (lg > 6) { pl->em_ok = 0; break; }
+            if (lg > 6) { pl->dev.em_ok = 0; break; }
             const int32_t G = kLanes >> lg;
             const int32_t nit_t = em_iterations(nt, G);
             pl->tile_rec[(size_t)t * 8 + 6] = (int32_t)its;
             pl->tile_rec[(size_t)t * 8 + 7] = lg | (nit_t << 8);
             its += nit_t;
-            if (t == 0) pl->em_lgs = lg; else if (pl->em_lgs != lg) pl->em_lgs = -1;
+            if (t == 0) pl->dev.em_lgs = lg; else if (pl->dev.em_lgs != lg) pl->dev.em_lgs = -1;
         }
-        if (!pl->em_ok) { for (int64_t t = 0; t < I.tiles; ++t) pl->tile_rec[(size_t)t * 8 + 6] = pl->tile_rec[(size_t)t * 8 + 7] = 0; pl->em_lgs = -1; }
-        pl->em_its = pl->em_ok ? its : 0;
+        if (!pl->dev.em_ok) { for (int64_t t = 0; t < I.tiles; ++t) pl->tile_rec[(size_t)t * 8 + 6] = pl->tile_rec[(size_t)t * 8 + 7] = 0; pl->dev.em_lgs = -1; }
+        if (its > INT32_MAX) return BT_EUNSUPPORTED;               // (PlanDev::em_its is an int)
+        pl->dev.em_its = pl->dev.em_ok ? (int)its : 0;
     }
     if (want_stream_tables && I.tiles >= em_min_p) {
-        pl->em_ok = 1;
+        pl->dev.em_ok = 1;
         int64_t its = 0;
         std::vector<int32_t> it0((size_t)I.tiles), lgS((size_t)I.tiles), nit((size_t)I.tiles);
         for (int64_t t = 0; t < I.tiles; ++t) {
             const int32_t ns = pl->tile_nslot[(size_t)t], nt = pl->tile_ntrk[(size_t)t];
             int lg = 0;
             while ((1 << lg) < ns) ++lg;
-            if (lg > 6) { pl->em_ok = 0; break; }
+            if (lg > 6) { pl->dev.em_ok = 0; break; }
             const int32_t G = kLanes >> lg;
             it0[(size_t)t] = (int32_t)its; lgS[(size_t)t] = lg; nit[(size_t)t] = em_iterations(nt, G);
             its += nit[(size_t)t];
         }
-        pl->tile_sinfo.assign(pl->em_ok ? (size_t)I.tiles * kLanes : 0, 0);
-        for (int64_t t = 0; t < I.tiles && pl->em_ok; ++t) {
+        if (its > INT32_MAX) return BT_EUNSUPPORTED;               // (PlanDev::em_its is an int)
+        pl->tile_sinfo.assign(pl->dev.em_ok ? (size_t)I.tiles * kLanes : 0, 0);
+        for (int64_t t = 0; t < I.tiles && pl->dev.em_ok; ++t) {
             const size_t b0 = (size_t)pl->tile_slot0[(size_t)t] * kLanes;
             const int32_t ns = pl->tile_nslot[(size_t)t], nt = pl->tile_ntrk[(size_t)t];
-            for (int32_t sl = 0; sl < ns && pl->em_ok; ++sl) {
+            for (int32_t sl = 0; sl < ns && pl->dev.em_ok; ++sl) {
                 int32_t code = -1;
                 for (int ln = 0; ln < nt; ++ln) {
                     const size_t i = b0 + (size_t)sl * kLanes + (size_t)ln;
                     if (pl->slot_edge[i] < 0) continue;
                     const int32_t c = (int32_t)pl->slot_code[i];
-                    if (code < 0) code = c; else if (code != c) { pl->em_ok = 0; break; }
+                    if (code < 0) code = c; else if (code != c) { pl->dev.em_ok = 0; break; }
                 }
                 if (code >= 0) pl->tile_sinfo[(size_t)t * kLanes + (size_t)sl] = (uint32_t)code | (1u << 17);
             }
-            for (int32_t sl = 0; sl + 1 < ns && pl->em_ok; ++sl) {
+            for (int32_t sl = 0; sl + 1 < ns && pl->dev.em_ok; ++sl) {
                 uint32_t &x = pl->tile_sinfo[(size_t)t * kLanes + (size_t)sl], &y = pl->tile_sinfo[(size_t)t * kLanes + (size_t)sl + 1];
                 if ((x >> 17 & 1u) && (y >> 17 & 1u) && ((x >> 8) & 0xffu) == ((y >> 8) & 0xffu)) { x |= 1u << 16; y |= 1u << 16; }
             }
         }
-        if (pl->em_ok) {
+        if (pl->dev.em_ok) {
             pl->it_edge.assign((size_t)its * kLanes, -1);
             for (int64_t t = 0; t < I.tiles; ++t) {
                 const size_t b0 = (size_t)pl->tile_slot0[(size_t)t] * kLanes;
@@ -1431,11 +1432,11 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
         } else {
             pl->it_edge.clear(); pl->tile_sinfo.clear();
         }
-        pl->em_its = pl->em_ok ? its : 0;
-        pl->em_lgs = -1;
-        if (pl->em_ok && I.tiles > 0) {
-            pl->em_lgs = lgS[0];
-            for (int64_t t = 1; t < I.tiles; ++t) if (lgS[(size_t)t] != pl->em_lgs) { pl->em_lgs = -1; break; }
+        pl->dev.em_its = pl->dev.em_ok ? (int)its : 0;
+        pl->dev.em_lgs = -1;
+        if (pl->dev.em_ok && I.tiles > 0) {
+            pl->dev.em_lgs = lgS[0];
+            for (int64_t t = 1; t < I.tiles; ++t) if (lgS[(size_t)t] != pl->dev.em_lgs) { pl->dev.em_lgs = -1; break; }
         }
     }
 
@@ -1452,18 +1453,18 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     //   pm_la[t * 64 + l]   local source camera of track l of the tile (0xff: fixed / no track)
     // pm_ok: 2 = the plan was tiled FOR the pair-major kernel (small tiles) or BT_ETILE=2 forces it, 1 = the tables exist but
     // k_tile keeps the plan (at one tile per CU, e.g. the 64-keyframe benchmark, k_tile measured 12.7 us against 15.0)
-    pl->pm_ok = I.tiles > 0 ? 1 : 0; pl->pm_rounds = 0;
+    pl->dev.pm_ok = I.tiles > 0 ? 1 : 0; pl->pm_rounds = 0;
     if (dstats) {
         if (I.tiles <= 0) return BT_NEED_EDGES;
         if (pm_direct) {
-            if (pm_fail || etile_full_lds_bytes(pl->max_rows16, pl->max_tile_pairs, sizeof(double)) > kEtileLdsBudget) {
+            if (pm_fail || etile_full_lds_bytes(pl->dev.max_rows16, pl->dev.max_tile_pairs, sizeof(double)) > kEtileLdsBudget) {
                 if (tcap_retry) return BT_NEED_EDGES;
                 RetryScope guard(tcap_retry);                      // small tiles are for k_etile only: lay the plan out again for k_tile
                 return build_plan_host(ii64, jj64, kk64, E, n_buf, p_tot, fixedp, n_all_min, own_lo, own_hi, pl, packed, keep_slots, dstats);
             }
-            pl->pm_ok = 2; pl->dev_pm = 1;
+            pl->dev.pm_ok = 2; pl->dev_pm = 1;
         } else {
-            pl->pm_ok = 0; pl->dev_slots = 1;
+            pl->dev.pm_ok = 0; pl->dev_slots = 1;
             pl->pm_edge.clear(); pl->pm_rec.clear(); pl->pm_lb.clear(); pl->pm_la.clear();
             pl->dev_off = off;
         }
@@ -1471,11 +1472,11 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     } else
     if (pm_direct) {
         // (built tile by tile above) — the plan stays with k_etile only if that kernel's LDS need fits in float64
-        if (pm_fail || I.tiles <= 0 || etile_full_lds_bytes(pl->max_rows16, pl->max_tile_pairs, sizeof(double)) > kEtileLdsBudget) {
-            pl->pm_ok = 0;
+        if (pm_fail || I.tiles <= 0 || etile_full_lds_bytes(pl->dev.max_rows16, pl->dev.max_tile_pairs, sizeof(double)) > kEtileLdsBudget) {
+            pl->dev.pm_ok = 0;
             pl->pm_edge.clear(); pl->pm_rec.clear(); pl->pm_lb.clear(); pl->pm_la.clear();
         } else {
-            pl->pm_ok = 2;
+            pl->dev.pm_ok = 2;
             pl->pm_rounds = pm_rounds_acc;
         }
     } else {
@@ -1483,16 +1484,16 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     }
     if (!pm_direct) {
         const int pm_env = etile_mode();                            // 0: k_tile forced
-        if (!pm_env || (pm_env != 2 && tcap == kLanes)) pl->pm_ok = 0;      // (tables only for the plans that will use them)
-        if (!loose.empty()) pl->pm_ok = 0;                                   // (k_etile's stored per-tile sums bypass the accumulators the loose tracks add to)
-        for (int64_t t = 0; t < I.tiles && pl->pm_ok; ++t) if (pl->tile_npair[(size_t)t] > kLanes) pl->pm_ok = 0;
-        if (pl->pm_ok) {
+        if (!pm_env || (pm_env != 2 && tcap == kLanes)) pl->dev.pm_ok = 0;      // (tables only for the plans that will use them)
+        if (!loose.empty()) pl->dev.pm_ok = 0;                                   // (k_etile's stored per-tile sums bypass the accumulators the loose tracks add to)
+        for (int64_t t = 0; t < I.tiles && pl->dev.pm_ok; ++t) if (pl->tile_npair[(size_t)t] > kLanes) pl->dev.pm_ok = 0;
+        if (pl->dev.pm_ok) {
             pl->pm_rec.assign((size_t)I.tiles * 4, 0);
             pl->pm_lb.assign((size_t)I.tiles * kLanes, 0xff);
             pl->pm_la.assign((size_t)I.tiles * kLanes, 0xff);
             std::vector<int32_t> cnt;                              // edges of (track, local pair) placed so far
             int64_t rounds = 0;
-            for (int64_t t = 0; t < I.tiles && pl->pm_ok; ++t) {
+            for (int64_t t = 0; t < I.tiles && pl->dev.pm_ok; ++t) {
                 const size_t b0 = (size_t)pl->tile_slot0[(size_t)t] * kLanes;
                 const int32_t ns = pl->tile_nslot[(size_t)t], nt = pl->tile_ntrk[(size_t)t], np = pl->tile_npair[(size_t)t];
                 int lg = 0;
@@ -1507,7 +1508,7 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
                         if (pl->slot_edge[i] < 0) continue;
                         D = std::max(D, ++cnt[(size_t)k * S + pl->slot_lp[i]]);
                     }
-                if (D > 255) { pl->pm_ok = 0; break; }
+                if (D > 255) { pl->dev.pm_ok = 0; break; }
                 pl->pm_rec[(size_t)t * 4] = (int32_t)rounds;
                 pl->pm_rec[(size_t)t * 4 + 1] = lg | (D << 8);
                 pl->pm_rec[(size_t)t * 4 + 2] = nit;
@@ -1525,12 +1526,12 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
                 rounds += (int64_t)nit * D;
             }
             pl->pm_rounds = rounds;
-            if (pl->pm_ok && (tcap < kLanes || pm_env == 2)) pl->pm_ok = 2;
-            if (!pl->pm_ok) { pl->pm_edge.clear(); pl->pm_rec.clear(); pl->pm_lb.clear(); pl->pm_la.clear(); }
+            if (pl->dev.pm_ok && (tcap < kLanes || pm_env == 2)) pl->dev.pm_ok = 2;
+            if (!pl->dev.pm_ok) { pl->pm_edge.clear(); pl->pm_rec.clear(); pl->pm_lb.clear(); pl->pm_la.clear(); }
         }
     }
     {
-        if (!pl->pm_ok && tcap < kLanes && !tcap_retry) {          // small tiles are for k_etile only: lay the plan out again for k_tile
+        if (!pl->dev.pm_ok && tcap < kLanes && !tcap_retry) {          // small tiles are for k_etile only: lay the plan out again for k_tile
             RetryScope guard(tcap_retry);
             return build_plan_host(ii64, jj64, kk64, E, n_buf, p_tot, fixedp, n_all_min, own_lo, own_hi, pl, packed, keep_slots);
         }
@@ -1541,21 +1542,21 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     // the products by position over each GROUP of consecutive tiles with the same cameras (a sliding window: the tiles of one
     // source frame; at most kSpGroupMax tiles, so that the sum is one round of independent loads), the pair sums over the
     // plan's list of every pair's (tile, local pair) entries.
-    pl->sp_ok = 0; pl->et_lgts = 0;
+    pl->dev.sp_ok = 0; pl->dev.et_lgts = 0;
     {
         int mt = 1;
         for (int64_t t = 0; t < I.tiles; ++t) mt = std::max(mt, (int)pl->tile_ntrk[(size_t)t]);
-        while ((1 << pl->et_lgts) < mt) ++pl->et_lgts;
+        while ((1 << pl->dev.et_lgts) < mt) ++pl->dev.et_lgts;
     }
-    if (pl->pm_ok == 2 && ((int64_t)sp_tile_doubles(pl->max_rows16, pl->max_tile_pairs) + ((int64_t)pl->max_rows16 << pl->et_lgts)) * I.tiles * 8 <= ((int64_t)96 << 20)) pl->sp_ok = 1;
+    if (pl->dev.pm_ok == 2 && ((int64_t)sp_tile_doubles(pl->dev.max_rows16, pl->dev.max_tile_pairs) + ((int64_t)pl->dev.max_rows16 << pl->dev.et_lgts)) * I.tiles * 8 <= ((int64_t)96 << 20)) pl->dev.sp_ok = 1;
     pl->sg_ptr.clear();
-    if (pl->sp_ok) {
+    if (pl->dev.sp_ok) {
         for (int64_t t = 0; t < I.tiles; ++t)
             if (t == 0 || !(pl->tile_flags[(size_t)t] & 1) || t - pl->sg_ptr.back() >= kSpGroupMax) pl->sg_ptr.push_back((int32_t)t);
         pl->sg_ptr.push_back((int32_t)I.tiles);
     }
     pl->pp_ptr.clear(); pl->pp_idx.clear();
-    if (pl->sp_ok) {                                               // which tiles hold sums of which camera pair
+    if (pl->dev.sp_ok) {                                               // which tiles hold sums of which camera pair
         pl->pp_ptr.assign((size_t)I.pairs + 1, 0);
         for (size_t q = 0; q < pl->tile_pairs.size(); ++q) pl->pp_ptr[(size_t)pl->tile_pairs[q] + 1]++;
         for (int64_t p = 0; p < I.pairs; ++p) pl->pp_ptr[(size_t)p + 1] += pl->pp_ptr[(size_t)p];
@@ -1567,8 +1568,8 @@ int build_plan_host(const int64_t *ii64, const int64_t *jj64, const int64_t *kk6
     }
 
     BT_TICK("14");
-    pl->max_tile_slots = 0;
-    for (int64_t t = 0; t < I.tiles; ++t) pl->max_tile_slots = std::max(pl->max_tile_slots, (int)pl->tile_nslot[(size_t)t]);
+    pl->dev.max_tile_slots = 0;
+    for (int64_t t = 0; t < I.tiles; ++t) pl->dev.max_tile_slots = std::max(pl->dev.max_tile_slots, (int)pl->tile_nslot[(size_t)t]);
 
     // ---- k_update: which patches carry a track (bitmap + rank per 32 patches: the patch buffer is BUFFER_SIZE x M
     // = 262,144 slots in the reference's configuration, the window's tracks a few thousand)

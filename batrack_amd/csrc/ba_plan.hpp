@@ -1,6 +1,7 @@
 // ba_plan.hpp — structure of one BA edge list, shared by the host planner
 // (ba_plan.cpp), the kernels (ba_kernels.hip) and the C ABI (ba_api.cpp).
 #pragma once
+#include <array>
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
@@ -149,72 +150,57 @@ struct WsLayout {
     size_t priv;                       // inside the cleared region: [kPrivY][D] then [kPrivP][pairs][kPairAccStride] doubles; 0 = none
 };
 
+// The tables a plan uploads, in their order in the device buffer (ba_api.cpp: upload_plan): element type, name, and 1 for the
+// tables of the block-sparse reduced solver (a wide plan has none: ba_plan.cpp, go_wide).  Each name is a vector of bt_plan, a
+// pointer of PlanDev and a name bt_plan_array answers to.
+#define BT_PLAN_TABLES(X)                                                                                                      \
+    X(int32_t, kx, 0) X(uint32_t, act_bits, 0) X(int32_t, act_rank, 0) X(int32_t, pair_i, 0) X(int32_t, pair_j, 0)              \
+    X(int32_t, tile_trk0, 0) X(int32_t, tile_ntrk, 0) X(int32_t, tile_ncam, 0) X(int32_t, tile_cam0, 0)                         \
+    X(int32_t, tile_slot0, 0) X(int32_t, tile_nslot, 0) X(int32_t, tile_erow0, 0) X(int32_t, tile_cams, 0)                       \
+    X(int32_t, slot_edge, 0) X(int32_t, slot_pair, 0) X(uint16_t, slot_lab, 0)                                                  \
+    X(int32_t, col_ptr, 1) X(int32_t, row_idx, 1) X(int32_t, upd_ptr, 1) X(int32_t, upd, 1) X(int32_t, blk_col, 1)              \
+    X(int32_t, upd_next, 1) X(int32_t, lvl_meta, 1) X(int32_t, tile_flags, 0)                                                   \
+    X(int32_t, tile_pair0, 0) X(int32_t, tile_npair, 0) X(int32_t, tile_pairs, 0) X(uint8_t, slot_lp, 0)                         \
+    X(int32_t, perm, 1) X(int32_t, blk_src, 1) X(int32_t, lvl_ptr, 1) X(int32_t, lvl_cols, 1) X(int32_t, col_lvl, 1)            \
+    X(int32_t, dp_ptr, 1) X(int32_t, dp, 1)                                                                                     \
+    X(int32_t, fz_pend_ptr, 1) X(int32_t, fz_pend, 1) X(int32_t, fz_lazy_ptr, 1) X(int32_t, fz_lazy, 1) X(int32_t, fz_yurg, 1)   \
+    X(int32_t, fz_meta, 1) X(int32_t, fz_pmeta, 1) X(int32_t, bs_sync, 1) X(int32_t, fz_rowinfo, 1) X(int32_t, fz_pfirst, 1)     \
+    X(int32_t, fz_psecond, 1) X(int32_t, tile_ij, 0) X(int32_t, tile_kx, 0) X(uint16_t, tile_cut8, 0) X(uint16_t, tile_cut16, 0) \
+    X(uint16_t, slot_code, 0) X(uint8_t, tile_la, 0) X(int32_t, tile_rec, 0) X(int32_t, it_edge, 0) X(uint32_t, tile_sinfo, 0)   \
+    X(int32_t, pm_edge, 0) X(int32_t, pm_rec, 0) X(uint8_t, pm_lb, 0) X(uint8_t, pm_la, 0)                                      \
+    X(int32_t, pp_ptr, 0) X(int32_t, pp_idx, 0) X(int32_t, sg_ptr, 0)                                                           \
+    X(int32_t, lz_trk, 0) X(int32_t, lz_ptr, 0) X(int32_t, lz_edge, 0) X(int32_t, lz_pair, 0)
+
+namespace tab {                       // table ids, in list order: bt_plan::off[tab::kx] ...
+#define BT_TAB_ID(T, name, solver) name,
+enum : int { BT_PLAN_TABLES(BT_TAB_ID) kCount };
+#undef BT_TAB_ID
+}  // namespace tab
+constexpr int kNumTables = tab::kCount;
+
 }  // namespace bt
 
-namespace bt { struct PlanOffsets { size_t ab, ar, bc, pme, pmr, pmb, pml, ppp, ppi, sgp, bs, bss, c0, cams, cl, cp, dp, dpp, e0, fl, flp, fm, fp, fpf, fpm, fpp, fps, fri, fy, ite, kx, lc, lm, lp, lzt, lzp, lze, lzq, pi, pj, pm, ri, s0, sc, se, sl, slp, sn, sp, t0, tc, tc16, tc8, tf, tij, tkx, tla, tn, tnp, tp0, tps, trec, tsi, u, un, up; }; }
-
-struct bt_plan {
+// All of a plan but its vectors: what bt_plan::recycle resets in one assignment.  The scalars the kernels read live in `dev` only.
+struct bt_plan_scalars {
     bt_plan_info info{};
-    bt::PlanOffsets off{};        // byte offsets of the arrays inside the device buffer (ba_api.cpp)
+    std::array<size_t, bt::kNumTables> off{};   // byte offsets of the tables inside the device buffer (ba_api.cpp: upload_plan)
+    std::array<size_t, bt::kNumTables> len{};   // their element counts there, the tables the device writes included
     size_t dev_bytes = 0;          // bytes of the device buffer in use
     size_t pk_off = 0;             // packed edge list (kk << 32 | ii << 16 | jj, 8 bytes per edge) inside the device buffer, 0 = not kept
-    int n_act_words = 0, n_tile_ij = 0;   // sizes of act_bits / tile_ij (for shifted clones)
-    int cnt_nlev = 0, cnt_ndp = 0, cnt_npend = 0, cnt_nlazy = 0;   // sizes bind_pointers needs without the host arrays (shifted clones have none)
-    std::vector<int32_t> kx, trk_loc, act_rank;                    // trk_loc: host only
-    std::vector<int32_t> trk_win;                                  // track of patch trk_win_lo + i (-1: none): the window of patches the edges name
     int64_t trk_win_lo = 0;
-    mutable std::vector<int32_t> trk_of_patch;                     // the same over the whole patch buffer, expanded on request (bt_plan_array: tests)
-    std::vector<uint32_t> act_bits;
-    std::vector<char> stage;     // upload staging (kept with the object: ba_api.cpp)
-    std::vector<int32_t> pair_i, pair_j;
-    std::vector<int32_t> tile_trk0, tile_ntrk, tile_ncam, tile_cam0, tile_slot0, tile_nslot, tile_erow0;
-    std::vector<int32_t> tile_cams;
-    std::vector<int32_t> slot_edge, slot_pair;
-    std::vector<uint16_t> slot_lab;
-    std::vector<int32_t> tile_pair0, tile_npair, tile_pairs, tile_flags, tile_ij, tile_kx;
-    std::vector<uint16_t> tile_cut8, tile_cut16;
-    std::vector<uint8_t> slot_lp, tile_la;
-    std::vector<uint16_t> slot_code;
-    std::vector<int32_t> tile_rec, it_edge;
-    std::vector<uint32_t> tile_sinfo;
-    int em_ok = 0, em_lgs = -1, em_self = 0, st_ok = 0, st_min = 1 << 30, em_min = 1 << 30;
-    std::vector<int32_t> pm_edge, pm_rec;
-    std::vector<uint8_t> pm_lb, pm_la;
-    std::vector<int32_t> pp_ptr, pp_idx, sg_ptr;
-    std::vector<int32_t> lz_trk, lz_ptr, lz_edge, lz_pair;   // loose tracks (more than kTileCamHard free cameras)
-    int pm_ok = 0, sp_ok = 0, sg_n = 0, et_lgts = 0, trk_off = 0;
-    int wide = 0;                                             // more than kMaxFree free poses, or a factor too large for LDS as double: dense solve, no symbolic tables
-    int nlz = 0;                                              // loose tracks (set at upload; clones copy it)
-    int dev_id = 0;                                           // the device the tables were uploaded to
     // plans whose pm_edge is written on the device (plan_device.hip): the table's rounds, and what the kernels need of the host's analysis
     int dev_pm = 0;
     int dev_slots = 0;                                        // likewise the [slots][64] arrays and the wave cuts of a 64-track layout
     int dev_wpt = 0;                                          // ... and with them the tables of the wave-per-tile kernels (slot_code, tile_la, it_edge, tile_sinfo)
-    std::vector<int32_t> dev_off;                             // [m + 1]: first position of every track's edges in the grouped order
-    std::vector<int32_t> dev_pbase;                           // aligned slot layout (ba_plan.cpp): first slot of every (tile, local pair), as tile_pairs; empty: a track's s-th edge is its slot s
-    mutable std::vector<int32_t> dev_readback;                // bt_plan_array(pm_edge / pm_rec) of such a plan
-    std::vector<int32_t> dev_pair_of;                         // [nw * nw]: pair index of (i - f_lo, j - f_lo) or -1
     int64_t dev_f_lo = 0, dev_nw = 0;
     int64_t dev_q0 = 0;                                       // sharded: position of the rank's first edge in the device's sorted list
     long long pm_rounds = 0;
-    long long em_its = 0;
-    int max_tile_pairs = 0, max_tile_slots = 0;
-    std::vector<int32_t> col_ptr, row_idx, upd_ptr, upd, blk_col, upd_next;
-    std::vector<int32_t> perm, blk_src, lvl_ptr, lvl_cols, col_lvl, dp_ptr, dp, lvl_meta;
-    std::vector<int32_t> fz_pend_ptr, fz_pend, fz_lazy_ptr, fz_lazy, fz_yurg, fz_meta, fz_pmeta, bs_sync, fz_rowinfo, fz_pfirst, fz_psecond;   // fused schedule (k_solve_fused)
-    int fz_ok = 0, fzp_ok = 0;
-    int max_rows16 = 16;
-    long long e_all = 0;
     bt::WsLayout ws{};
-    void *dev_base = nullptr;   // one device allocation holding every array above (from the pool in ba_api.cpp)
+    void *dev_base = nullptr;   // one device allocation holding every table (from the pool in ba_api.cpp)
     // the stream the plan's kernels were last launched on: bt_plan_destroy records an event there, and the next plan that
     // reuses the device buffer makes its table upload wait for it (the tables must not change under queued kernels)
     mutable void *last_stream = nullptr;
     mutable bool launched = false;
-    // hipEvent_t behind a clone's copies on the plan stream (ba_api.cpp: mark_launch), else null.  Atomic: two host threads may
-    // launch the same fresh clone; whoever finds the event complete CLAIMS it (exchange) before handing it back to the pool —
-    // handed back twice, two later clones would share one event.
-    mutable std::atomic<void *> ready{nullptr};
     size_t dev_cap = 0;
     int64_t k_hi = -1;                                        // largest patch index the plan's tables hold (bt_plan_create_shifted_spec checks k_hi + dk < p_tot)
     void *spec_ev = nullptr;                                  // hipEvent_t behind the verdict of a speculative clone (bt_plan_spec_confirm), else null
@@ -222,30 +208,36 @@ struct bt_plan {
     int spec_epoch = 0;                                       // > 0: no event — the verdict is complete when spec_flag[2] holds this (bt_plan_spec_bind)
     void *spec_stream = nullptr;                              //   (the stream the comparison was launched on: what a poll that runs out of patience waits for)
     int spec_unbound = 0;                                     // made AHEAD of its list (bt_plan_preshift): no step before bt_plan_spec_bind
-    bt::PlanDev dev{};
+    bt::PlanDev dev{};            // the planner's scalars; upload_plan adds the table pointers
+};
+
+struct bt_plan : bt_plan_scalars {
+#define BT_TAB_VEC(T, name, solver) std::vector<T> name;
+    BT_PLAN_TABLES(BT_TAB_VEC)
+#undef BT_TAB_VEC
+    std::vector<int32_t> trk_loc;                                  // host only
+    std::vector<int32_t> trk_win;                                  // track of patch trk_win_lo + i (-1: none): the window of patches the edges name
+    mutable std::vector<int32_t> trk_of_patch;                     // the same over the whole patch buffer, expanded on request (bt_plan_array: tests)
+    std::vector<char> stage;     // upload staging (kept with the object: ba_api.cpp)
+    std::vector<int32_t> dev_off;                             // [m + 1]: first position of every track's edges in the grouped order
+    std::vector<int32_t> dev_pbase;                           // aligned slot layout (ba_plan.cpp): first slot of every (tile, local pair), as tile_pairs; empty: a track's s-th edge is its slot s
+    mutable std::vector<int32_t> dev_readback;                // bt_plan_array of a table the device wrote, and of the named figures
+    std::vector<int32_t> dev_pair_of;                         // [nw * nw]: pair index of (i - f_lo, j - f_lo) or -1
+    // hipEvent_t behind a clone's copies on the plan stream (ba_api.cpp: mark_launch), else null.  Atomic: two host threads may
+    // launch the same fresh clone; whoever finds the event complete CLAIMS it (exchange) before handing it back to the pool —
+    // handed back twice, two later clones would share one event.
+    mutable std::atomic<void *> ready{nullptr};
 
     // Back to the state of a new object, but with the vectors' capacity kept: destroyed plans are recycled
     // by bt_plan_create (ba_api.cpp), so that a plan per frame costs no heap traffic.
     void recycle() {
-        info = bt_plan_info{};
-        for (auto *v : {&kx, &trk_of_patch, &trk_win, &trk_loc, &pair_i, &pair_j, &tile_trk0, &tile_ntrk, &tile_ncam,
-                        &tile_cam0, &tile_slot0, &tile_nslot, &tile_erow0, &tile_cams, &slot_edge, &slot_pair,
-                        &tile_pair0, &tile_npair, &tile_pairs, &tile_flags, &tile_ij, &tile_kx, &col_ptr, &row_idx,
-                        &upd_ptr, &upd, &blk_col, &upd_next, &perm, &blk_src, &lvl_ptr, &lvl_cols, &col_lvl, &dp_ptr,
-                        &dp, &lvl_meta, &fz_pend_ptr, &fz_pend, &fz_lazy_ptr, &fz_lazy, &fz_yurg, &fz_meta, &fz_pmeta,
-                        &bs_sync, &fz_rowinfo, &fz_pfirst, &fz_psecond})
-            v->clear();
-        tile_cut8.clear(); tile_cut16.clear();
-        pm_edge.clear(); pm_rec.clear(); pm_lb.clear(); pm_la.clear(); pp_ptr.clear(); pp_idx.clear(); sg_ptr.clear(); pm_ok = 0; sp_ok = 0; pm_rounds = 0; wide = 0; nlz = 0;
-        dev_pbase.clear(); lz_trk.clear(); lz_ptr.clear(); lz_edge.clear(); lz_pair.clear();
-        slot_lab.clear(); slot_lp.clear(); tile_la.clear(); slot_code.clear(); tile_rec.clear(); it_edge.clear(); tile_sinfo.clear(); em_ok = 0; st_ok = 0; em_its = 0; em_lgs = -1; act_bits.clear(); act_rank.clear(); stage.clear();
-        max_tile_pairs = max_tile_slots = 0;
-        fz_ok = fzp_ok = 0;
-        max_rows16 = 16;
-        ws = bt::WsLayout{};
-        dev_base = nullptr; dev_cap = 0;
-        last_stream = nullptr; launched = false; ready = nullptr; k_hi = -1; spec_ev = nullptr; spec_flag = nullptr; spec_unbound = 0; spec_epoch = 0; spec_stream = nullptr;
-        dev = bt::PlanDev{};
+        static_cast<bt_plan_scalars &>(*this) = bt_plan_scalars{};
+        ready = nullptr;
+#define BT_TAB_CLEAR(T, name, solver) name.clear();
+        BT_PLAN_TABLES(BT_TAB_CLEAR)
+#undef BT_TAB_CLEAR
+        for (auto *v : {&trk_loc, &trk_win, &trk_of_patch, &dev_off, &dev_pbase, &dev_readback, &dev_pair_of}) v->clear();
+        stage.clear();
     }
 };
 

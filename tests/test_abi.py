@@ -52,6 +52,34 @@ def test_plan_info_struct_matches_header():
     assert names == [n for n, _ in _lib.BaArgs._fields_]
 
 
+def test_plan_tables_match_the_binding():
+    """BT_PLAN_TABLES (csrc/ba_plan.hpp), the one list of the tables a plan uploads: every table is in PLAN_ARRAYS with its element
+    type, and bt_plan_array answers it with the host vector on a host-only plan that has loose tracks."""
+    from batrack_amd.plan import Plan, PLAN_ARRAYS, _NP_TYPES
+    from edge_problems import hub_graph
+    src = open(os.path.join(ROOT, "batrack_amd", "csrc", "ba_plan.hpp")).read()
+    body = re.search(r"#define BT_PLAN_TABLES\(X\)((?:[^\n]*\\\n)*[^\n]*)", src).group(1)
+    tables = re.findall(r"X\((\w+), (\w+), [01]\)", body)
+    assert len(tables) == 66 and len({n for _, n in tables}) == 66
+    ctype = {"int32_t": np.int32, "uint32_t": np.uint32, "uint16_t": np.uint16, "uint8_t": np.uint8}
+    for t, name in tables:
+        assert name in PLAN_ARRAYS, name
+        assert np.dtype(_NP_TYPES.get(name, np.int32)) == np.dtype(ctype[t]), name
+    d, hubs = hub_graph(3)
+    pl = Plan(d["ii"], d["jj"], d["kk"], d["poses"].shape[0], d["patches"].shape[0], 1, upload=False)
+    A = {name: pl.array(name) for _, name in tables}         # (KeyError: a table bt_plan_array does not answer)
+    assert len(A["kx"]) == pl.m and len(A["pair_i"]) == len(A["pair_j"]) == pl.pairs and len(A["tile_trk0"]) == pl.tiles
+    assert len(A["slot_edge"]) == pl.slots * 64 and len(A["act_bits"]) == (pl.p_tot + 31) // 32
+    # the loose tracks' tables: their tracks, every edge of each, and the edges' camera pairs
+    assert sorted(A["kx"][A["lz_trk"]]) == sorted(hubs)
+    ptr, edge, pair = A["lz_ptr"], A["lz_edge"], A["lz_pair"]
+    assert len(ptr) == 4 and ptr[0] == 0 and ptr[-1] == len(edge) == len(pair)
+    for l, k in enumerate(A["kx"][A["lz_trk"]]):
+        assert sorted(edge[ptr[l]:ptr[l + 1]]) == list(np.flatnonzero(d["kk"] == k))
+    assert (A["pair_i"][pair] == d["ii"][edge]).all() and (A["pair_j"][pair] == d["jj"][edge]).all()
+    pl.close()
+
+
 def test_error_codes_not_crashes():
     L = _lib.lib()
     h = ctypes.c_void_p()
