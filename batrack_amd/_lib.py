@@ -8,7 +8,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip"]
+SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip"]
 HEADERS = ["ba_kernels.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
@@ -22,7 +22,7 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
           BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
                            "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
                            "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward, or more than 8192 cells wide in "
-                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene)"}
+                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene; world tracks: a window of more than 2^20 frames)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -251,6 +251,8 @@ def lib():
         f.argtypes = [vp] * nptr + [i64, i32, vp]
     L.bt_reproject.restype = i32
     L.bt_reproject.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    L.bt_world_tracks.restype = i32
+    L.bt_world_tracks.argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp]
     L.bt_ga_forward.restype = i32
     L.bt_ga_forward.argtypes = [vp, vp, vp, i32, vp]
     L.bt_ga_backward.restype = i32

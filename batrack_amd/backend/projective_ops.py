@@ -122,6 +122,61 @@ def point_cloud(poses, patches, intrinsics, ix):
     return poses[:, ix, None, None].inv() * iproj(patches, intrinsics[:, ix])
 
 
+def world_tracks(poses, patches, intrinsics, ix, patches_local, local_weights, m, *, points=None, world=None):
+    """The end of the reference's per-frame update() (batrack.py:891-895, update_point_cloud :821-854) for the first `m`
+    tracks in one launch of bt_world_tracks (include/batrack_projective.h holds the specification): the world point of every
+    track, its 3-D trajectory over the S_local frames around its own, and — IN PLACE — the re-projection of the live tracks'
+    world points into `patches_local`.  Not one of the reference's names: there the computation is spelt out in the caller.
+
+    poses: SE3 or tensor [1, N, 7] / [N, 7]; patches [1, N*M, 3, p, p]; intrinsics [1, N, 4]; ix [>= m] int64;
+    patches_local [1, N*M, S_local, 3] or [N, M, S_local, 3] (contiguous: it is written through); local_weights with
+    N*M*S_local elements; points / world: optional buffers to write into ([>= m, 3] and N*M*S_local*3 elements).
+    Returns (points [m, 3], world [1, N*M, S_local, 3]); rows of `world` past m keep what the buffer held (zeros when
+    allocated here).  float32 GPU tensors only."""
+    from .. import _lib
+    P = poses.data if hasattr(poses, "data") and not isinstance(poses, torch.Tensor) else poses
+    for name, t in (("poses", P), ("patches", patches), ("intrinsics", intrinsics), ("ix", ix), ("patches_local", patches_local),
+                    ("local_weights", local_weights), ("points", points), ("world", world)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"world_tracks: `{name}` must be a tensor on the GPU (there is no CPU fallback)")
+        if t.dtype != (torch.int64 if name == "ix" else torch.float32):
+            raise RuntimeError(f"world_tracks: `{name}` must be {'int64' if name == 'ix' else 'float32'}")
+    if not patches_local.is_contiguous() or patches_local.shape[-1] != 3 or patches_local.dim() < 3:
+        raise RuntimeError("world_tracks: `patches_local` must be contiguous [..., S_local, 3]: it is updated in place")
+    for name, t in (("points", points), ("world", world)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"world_tracks: `{name}` must be contiguous: it is written through")
+    P = P.reshape(-1, 7).contiguous()
+    N, S = P.shape[0], patches_local.shape[-2]
+    pat = patches.reshape(-1, *patches.shape[-3:]).contiguous()
+    NM, m = pat.shape[0], int(m)
+    K = intrinsics.reshape(-1, 4).contiguous()
+    pl = patches_local.view(NM, S, 3)
+    lw = local_weights.reshape(NM, S).contiguous()
+    ixc = ix.reshape(-1).contiguous()
+    if not 0 <= m <= min(NM, ixc.numel()):
+        raise RuntimeError(f"world_tracks: m = {m} tracks do not fit the buffer of {NM} patches / {ixc.numel()} indices")
+    if points is None:
+        points = torch.empty(m, 3, dtype=torch.float32, device=pat.device)
+    elif points.numel() < 3 * m:
+        raise RuntimeError("world_tracks: `points` is shorter than m rows")
+    if world is None:
+        world = torch.zeros(1, NM, S, 3, dtype=torch.float32, device=pat.device)
+    elif world.numel() != NM * S * 3:
+        raise RuntimeError("world_tracks: `world` must hold N*M*S_local*3 elements")
+    ops = _lib.torch_ops()
+    if ops is not None:
+        ops.world_tracks(P, pat, K, ixc, pl, lw, m, points, world)
+    else:
+        st = torch.cuda.current_stream(pat.device).cuda_stream
+        _lib.check(_lib.lib().bt_world_tracks(P.data_ptr(), N, K.data_ptr(), pat.data_ptr(), NM, pat.shape[-1] * pat.shape[-2],
+                                              ixc.data_ptr(), pl.data_ptr(), lw.data_ptr(), S, m, points.data_ptr(),
+                                              world.data_ptr(), st), "bt_world_tracks")
+    return points.view(-1, 3)[:m], world.view(1, NM, S, 3)
+
+
 def flow_mag(poses, patches, intrinsics, ii, jj, kk, beta=0.3):
     """Blend of full-motion and translation-only flow magnitude, for keyframe selection     (:112-122)."""
     c0 = transform(poses, patches, intrinsics, ii, ii, kk)

@@ -19,6 +19,10 @@
 //       the prior and the 2-D targets possibly strided views): shape checks, the views the ABI needs, the two output
 //       tensors and the step in one operator call — the Python wrapper's dozen tensor operations cost more host time
 //       (28 us a call) than a structure-only step takes on the GPU (9 us)
+//   batrack_hip::world_tracks(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ix, Tensor(a!) patches_local,
+//                             Tensor local_weights, int m, Tensor(b!)? points=None, Tensor(c!)? world=None) -> ()
+//       bt_world_tracks (include/batrack_projective.h): poses [N, 7], patches [N*M, 3, p, p], intrinsics [N, 4], ix int64,
+//       patches_local [N*M, S_local, 3] in/out, local_weights [N*M, S_local], points [>= m, 3], world [N*M, S_local, 3]
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -28,6 +32,7 @@
 #include <vector>
 
 #include "../../include/batrack_ba.h"
+#include "../../include/batrack_projective.h"
 
 namespace {
 
@@ -141,6 +146,43 @@ std::tuple<at::Tensor, at::Tensor> ba_droid(int64_t plan, const at::Tensor &ws, 
     return {poses_out, patches_out.view({1, p_tot, 3, 1, 1})};
 }
 
+void world_tracks(const at::Tensor &poses, const at::Tensor &patches, const at::Tensor &intrinsics, const at::Tensor &ix,
+                  const at::Tensor &patches_local, const at::Tensor &local_weights, int64_t m, const c10::optional<at::Tensor> &points,
+                  const c10::optional<at::Tensor> &world) {
+    const char *op = "batrack_hip::world_tracks: ";
+    const float *P = f32(poses, "poses"), *pat = f32(patches, "patches"), *K = f32(intrinsics, "intrinsics");
+    float *pl = const_cast<float *>(f32(patches_local, "patches_local"));
+    const float *lw = f32(local_weights, "local_weights");
+    TORCH_CHECK(ix.is_cuda() && ix.scalar_type() == at::kLong && ix.is_contiguous(), op, "`ix` must be a contiguous int64 GPU tensor");
+    for (const at::Tensor *t : {&poses, &patches, &intrinsics, &patches_local, &local_weights})
+        TORCH_CHECK(t->is_contiguous() && t->device() == poses.device(), op, "tensors must be contiguous and on one device");
+    TORCH_CHECK(ix.device() == poses.device(), op, "tensors must be on one device");
+    TORCH_CHECK(poses.dim() == 2 && poses.size(1) == 7, op, "poses must be [N, 7]");
+    const int64_t N = poses.size(0);
+    TORCH_CHECK(intrinsics.dim() == 2 && intrinsics.size(0) == N && intrinsics.size(1) == 4, op, "intrinsics must be [N, 4]");
+    TORCH_CHECK(patches.dim() == 4 && patches.size(1) == 3 && patches.size(2) == patches.size(3), op, "patches must be [N*M, 3, p, p]");
+    const int64_t NM = patches.size(0);
+    TORCH_CHECK(patches_local.dim() == 3 && patches_local.size(0) == NM && patches_local.size(2) == 3, op,
+                "patches_local must be [N*M, S_local, 3] over the patch buffer");
+    const int64_t S = patches_local.size(1);
+    TORCH_CHECK(local_weights.numel() == NM * S, op, "local_weights must be [N*M, S_local]");
+    TORCH_CHECK(m >= 0 && m <= NM && ix.numel() >= m, op, "m tracks must fit the patch buffer and `ix`");
+    float *pts = nullptr, *wld = nullptr;
+    if (points.has_value()) {
+        TORCH_CHECK(points->is_contiguous() && points->device() == poses.device() && points->numel() >= 3 * m, op,
+                    "points must be a contiguous [>= m, 3] tensor");
+        pts = const_cast<float *>(f32(*points, "points"));
+    }
+    if (world.has_value()) {
+        TORCH_CHECK(world->is_contiguous() && world->device() == poses.device() && world->numel() == NM * S * 3, op,
+                    "world must be a contiguous [N*M, S_local, 3] tensor");
+        wld = const_cast<float *>(f32(*world, "world"));
+    }
+    const int rc = bt_world_tracks(P, N, K, pat, NM, patches.size(2) * patches.size(3), ix.data_ptr<int64_t>(), pl, lw, S, m, pts, wld,
+                                   c10::hip::getCurrentHIPStream(poses.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_world_tracks failed with status ", rc);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -153,4 +195,6 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("ba_droid(int plan, Tensor ws, Tensor poses, Tensor patches, Tensor patches_monodisp, Tensor intrinsics, Tensor targets_2d, "
           "Tensor weights, float[] bounds, float lmbda, float ep, float alpha, int loss, bool structure_only, "
           "Tensor? lmbda_per_track=None) -> (Tensor, Tensor)", &ba_droid);
+    m.def("world_tracks(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ix, Tensor(a!) patches_local, Tensor local_weights, "
+          "int m, Tensor(b!)? points=None, Tensor(c!)? world=None) -> ()", &world_tracks);
 }

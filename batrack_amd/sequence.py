@@ -11,7 +11,7 @@ live on `device`; nothing here is specific to the GPU except the `ba` passed in.
 
 Out of scope (not restated): image preprocessing, patch selection, the tracker network, the
 motion-magnitude keyframe removal (`keyframe`, batrack.py:1026-1071 — `keyframe_simple` is used,
-as in the reference when `use_keyframe` is off), point-cloud export, visualisers.
+as in the reference when `use_keyframe` is off), visualisers.
 """
 import dataclasses
 import time
@@ -41,6 +41,7 @@ class SlamConfig:
     kf_stride: int = 2
     num_init: int = 12
     init_updates: int = 12            # batrack.py:990-991
+    UPDATE_POINT_CLOUD: bool = False  # not a key of the reference's file: it always runs the step (see WindowedBA)
 
 
 class SyntheticObservations:
@@ -108,7 +109,15 @@ class SyntheticObservations:
 class WindowedBA:
     """Sliding-window sparse SLAM back end around `ba` (same attribute names as the reference's
     BATRACK object where they exist: n, m, M, N, poses_, patches_, ii, jj, kk, targets_3d,
-    weights, weights_pose)."""
+    weights, weights_pose).
+
+    The reference ends EVERY update() with the world-frame point cloud, the tracks' 3-D trajectories and the overwrite of
+    the live tracks' `patches_local` by the re-projection of their world point (batrack.py:891-895, :821-854).  Here that
+    step runs only with `cfg.UPDATE_POINT_CLOUD` — one `pops.world_tracks` launch over the first `m` tracks, GPU state
+    only — and the object then owns `trajs_3d_world_` [N, M, S_local, 3] and `points_` [N*M, 3] (batrack.py:87,94).  It is
+    off by default because the recorded trajectories, the ATE figures and the CPU replay against the oracle were made
+    without it: with it off nothing is allocated or computed, and the depth prior of a track stays the tracker's
+    disparity for the track's whole life, where the reference hands a live track its current estimate."""
 
     def __init__(self, obs, ba, cfg=None, device="cpu", sync=None, prefetch=None, se3=SE3):
         """se3: the pose class (default: the HIP-backed batrack_amd.backend.lietorch.SE3, GPU tensors only; the CPU-side
@@ -139,6 +148,10 @@ class WindowedBA:
         self.patches_local_static_ = torch.ones(self.N, self.M, self.S_local, 1, **f32)
         self.patches_local_weights_ = torch.zeros(self.N, self.M, self.S_local, 1, **f32)
         self.patches_valid_ = torch.zeros(self.N, self.M, **f32)
+        if c.UPDATE_POINT_CLOUD:
+            self.trajs_3d_world_ = torch.zeros(self.N, self.M, self.S_local, 3, **f32)         # batrack.py:87
+            self.points_ = torch.zeros(self.N * self.M, 3, **f32)                              # batrack.py:94
+            self.ix = torch.arange(self.N * self.M, **i64) // self.M                           # a track's source frame (index_)
         self.tstamps_ = torch.zeros(self.N, **i64)
         self.tlist, self.counter = [], 0
         self.ii, self.jj, self.kk = (torch.zeros(0, **i64) for _ in range(3))
@@ -271,6 +284,14 @@ class WindowedBA:
         self.poses_[:] = Gs.vec().reshape(self.N, 7)
         if c.USE_MAP_FILTERING:
             self.map_point_filtering()
+        if c.UPDATE_POINT_CLOUD:
+            self.update_point_cloud()
+
+    # ---- batrack.py:891-895, 821-854
+    def update_point_cloud(self):
+        """`points_`, `trajs_3d_world_` and the live tracks' `patches_local_` for the first `m` tracks, in one launch."""
+        pops.world_tracks(self.SE3(self.poses), self.patches, self.intrinsics, self.ix, self.patches_local_,
+                          self.patches_local_weights_, self.m, points=self.points_, world=self.trajs_3d_world_)
 
     def _prefetch(self, n_at_update):
         """Hand the edge list of the update() that will run with `n_at_update` frames to the plan builder."""
