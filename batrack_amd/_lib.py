@@ -8,11 +8,11 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip"]
+SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip"]
 HEADERS = ["ba_kernels.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
-           os.path.join("..", "..", "include", "batrack_depth.h")]
+           os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -22,7 +22,8 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
           BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
                            "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
                            "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward, or more than 8192 cells wide in "
-                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene; world tracks: a window of more than 2^20 frames)"}
+                           "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene; world tracks: a window of more than 2^20 frames; "
+                           "correlation lookup: more than 512 channels, a radius above 7, more than 8 levels, a map side above 32768, or more than 2^31 - 1 (frame, query, level) triples)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -277,6 +278,14 @@ def lib():
     L.bt_mono_align_workspace_bytes.argtypes = [i64, i64, i32]
     L.bt_mono_align.restype = i32
     L.bt_mono_align.argtypes = [vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.bt_corr_pyramid_bytes.restype = ctypes.c_size_t
+    L.bt_corr_pyramid_bytes.argtypes = [i64, i64, i64, i64, i32]
+    L.bt_corr_pyramid.restype = i32
+    L.bt_corr_pyramid.argtypes = [vp, i64, i64, i64, i64, i32, vp, vp]
+    L.bt_corr_lookup.restype = i32
+    L.bt_corr_lookup.argtypes = [vp, i64, i64, i64, i64, i32, i32, vp, vp, i64, i64, vp, vp]
+    L.bt_config_corr_lookup_layout.restype = i32
+    L.bt_config_corr_lookup_layout.argtypes = [i32]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

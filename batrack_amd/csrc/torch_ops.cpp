@@ -23,6 +23,11 @@
 //                             Tensor local_weights, int m, Tensor(b!)? points=None, Tensor(c!)? world=None) -> ()
 //       bt_world_tracks (include/batrack_projective.h): poses [N, 7], patches [N*M, 3, p, p], intrinsics [N, 4], ix int64,
 //       patches_local [N*M, S_local, 3] in/out, local_weights [N*M, S_local], points [>= m, 3], world [N*M, S_local, 3]
+//   batrack_hip::corr_pyramid(Tensor fmaps, int levels) -> Tensor
+//       bt_corr_pyramid (include/batrack_corr.h): fmaps [..., C, H, W] -> the packed channels-last pyramid, one 1-D tensor
+//   batrack_hip::corr_lookup(Tensor pyramid, int[] shape, int levels, int radius, Tensor targets, Tensor coords) -> Tensor
+//       bt_corr_lookup: shape = [S', C, H, W] of the maps the pyramid was made from, targets [..., N, C], coords [..., N, 2]
+//       (the strided view `coords3[..., :2]` is read in place) -> [..., N, levels * (2 radius + 1)^2]
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -32,6 +37,7 @@
 #include <vector>
 
 #include "../../include/batrack_ba.h"
+#include "../../include/batrack_corr.h"
 #include "../../include/batrack_projective.h"
 
 namespace {
@@ -183,6 +189,52 @@ void world_tracks(const at::Tensor &poses, const at::Tensor &patches, const at::
     TORCH_CHECK(rc == BT_OK, op, "bt_world_tracks failed with status ", rc);
 }
 
+at::Tensor corr_pyramid(const at::Tensor &fmaps, int64_t levels) {
+    const char *op = "batrack_hip::corr_pyramid: ";
+    (void)f32(fmaps, "fmaps");
+    TORCH_CHECK(fmaps.dim() >= 4 && fmaps.is_contiguous(), op, "fmaps must be a contiguous [..., C, H, W] tensor");
+    const int64_t n = fmaps.dim(), C = fmaps.size(n - 3), H = fmaps.size(n - 2), W = fmaps.size(n - 1);
+    const int64_t S = C * H * W > 0 ? fmaps.numel() / (C * H * W) : 0;
+    const size_t bytes = bt_corr_pyramid_bytes(S, C, H, W, (int32_t)levels);
+    at::Tensor pyr = at::empty({(int64_t)(bytes / sizeof(float))}, fmaps.options());
+    const int rc = bt_corr_pyramid(fmaps.data_ptr<float>(), S, C, H, W, (int32_t)levels, pyr.data_ptr<float>(),
+                                   c10::hip::getCurrentHIPStream(fmaps.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_corr_pyramid failed with status ", rc);
+    return pyr;
+}
+
+at::Tensor corr_lookup(const at::Tensor &pyramid, c10::ArrayRef<int64_t> shape, int64_t levels, int64_t radius,
+                       const at::Tensor &targets, const at::Tensor &coords) {
+    const char *op = "batrack_hip::corr_lookup: ";
+    const float *pyr = f32(pyramid, "pyramid"), *tg = f32(targets, "targets");
+    (void)f32(coords, "coords");
+    TORCH_CHECK(shape.size() == 4, op, "shape = [S', C, H, W] of the feature maps");
+    const int64_t S = shape[0], C = shape[1], H = shape[2], W = shape[3];
+    TORCH_CHECK(pyramid.is_contiguous() && pyramid.numel() * sizeof(float) == bt_corr_pyramid_bytes(S, C, H, W, (int32_t)levels)
+                && pyramid.numel() > 0, op, "`pyramid` is not the pyramid of maps of this shape and level count");
+    TORCH_CHECK(targets.dim() >= 2 && targets.is_contiguous() && targets.size(-1) == C, op, "targets must be contiguous [..., N, C]");
+    const int64_t N = targets.size(-2);
+    TORCH_CHECK(targets.numel() == S * N * C, op, "targets must hold S' * N vectors");
+    TORCH_CHECK(coords.dim() == targets.dim() && coords.size(-1) == 2 && coords.numel() == S * N * 2, op, "coords must be [..., N, 2]");
+    TORCH_CHECK(targets.device() == pyramid.device() && coords.device() == pyramid.device(), op, "tensors must be on one device");
+    // (x, y) pairs a constant number of floats apart are read in place: a contiguous tensor (2) or a `[..., :2]` view (3)
+    at::Tensor cd = coords;
+    int64_t cs = cd.stride(-2);
+    bool flat = cd.stride(-1) == 1 && cs >= 2;
+    for (int64_t k = cd.dim() - 3, run = cs * N; flat && k >= 0; run *= cd.size(k), --k)
+        flat = cd.size(k) == 1 || cd.stride(k) == run;
+    if (!flat || S * N <= 1) { cd = coords.contiguous(); cs = 2; }
+    std::vector<int64_t> osz(coords.sizes().begin(), coords.sizes().end());
+    const int64_t d = 2 * radius + 1;
+    osz.back() = levels * d * d;
+    at::Tensor out = at::empty(osz, targets.options());
+    if (N == 0) return out;
+    const int rc = bt_corr_lookup(pyr, S, C, H, W, (int32_t)levels, (int32_t)radius, tg, cd.data_ptr<float>(), cs, N, out.data_ptr<float>(),
+                                  c10::hip::getCurrentHIPStream(pyramid.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_corr_lookup failed with status ", rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -197,4 +249,6 @@ TORCH_LIBRARY(batrack_hip, m) {
           "Tensor? lmbda_per_track=None) -> (Tensor, Tensor)", &ba_droid);
     m.def("world_tracks(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ix, Tensor(a!) patches_local, Tensor local_weights, "
           "int m, Tensor(b!)? points=None, Tensor(c!)? world=None) -> ()", &world_tracks);
+    m.def("corr_pyramid(Tensor fmaps, int levels) -> Tensor", &corr_pyramid);
+    m.def("corr_lookup(Tensor pyramid, int[] shape, int levels, int radius, Tensor targets, Tensor coords) -> Tensor", &corr_lookup);
 }
