@@ -174,9 +174,27 @@ __global__ __launch_bounds__(CL_THREADS) void k_corr_lookup(const float *__restr
             const bool ok = y >= 0 && y < Hl && x >= 0 && x < Wl;
             float acc = 0.0f;
             if (ok) {
+                // 16 interleaved partial sums (channel c goes to sum c % 16), added pairwise: one chain of 128 fused
+                // multiply-adds rounds three times as far from the exact dot product as the other kernels' sums do
                 const float4 *row = reinterpret_cast<const float4 *>(base + ((size_t)y * Wl + x) * C);
-#pragma unroll 8
-                for (int c = 0; c < C / 4; ++c) acc = corr_dot4(row[c], reinterpret_cast<const float4 *>(tg)[c], acc);
+                const float4 *t4 = reinterpret_cast<const float4 *>(tg);
+                float a[16] = {};
+#pragma unroll 2
+                for (int c = 0; c < C / 4; c += 4) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float4 v = row[c + u], t = t4[c + u];
+                        a[4 * u + 0] = fmaf(v.x, t.x, a[4 * u + 0]);
+                        a[4 * u + 1] = fmaf(v.y, t.y, a[4 * u + 1]);
+                        a[4 * u + 2] = fmaf(v.z, t.z, a[4 * u + 2]);
+                        a[4 * u + 3] = fmaf(v.w, t.w, a[4 * u + 3]);
+                    }
+                }
+#pragma unroll
+                for (int o = 8; o >= 1; o >>= 1)
+#pragma unroll
+                    for (int k = 0; k < o; ++k) a[k] += a[k + o];
+                acc = a[0];
             }
             dot = acc / sqrt_c;                     // position = lane
         }

@@ -15,6 +15,10 @@
  *             A tap outside the map contributes exactly 0 and its feature row is not read; a tap inside the map is
  *             multiplied by its weight even where that weight is 0 (a NaN feature row shows wherever the reference's
  *             grid_sample would show it, and nowhere else).
+ *             Coordinates may be any float.  The integer part is clamped far outside every map before the positions are
+ *             formed, so a finite coordinate however far away (+-3e9, +-(1e6 +- 0.5), 2^24 + 1) gives exactly 0.  A
+ *             coordinate that is +-inf or NaN has a NaN fraction: every output of its query is NaN, at every level, and
+ *             no other query is touched — what the volume formulation gives (tests/test_gpu_corr_limits.py).
  *
  * bt_corr_pyramid writes all L levels CHANNELS-LAST into one packed buffer: level l is [S', H_l, W_l, C] float32 and
  * starts at float offset  C * S' * sum_{k<l} H_k W_k;  bt_corr_pyramid_bytes gives the buffer's size (0 for arguments
@@ -24,6 +28,11 @@
  * coords + k * coord_stride floats (coord_stride >= 2: 2 for a contiguous [S', N, 2] tensor, 3 for the tracker's
  * `coords[..., :2]` view of a [S', N, 3] tensor); out [S', N, L*d*d] float32 contiguous, every element written.
  * float32 accumulation with fused multiply-adds in a fixed order, no atomics, no workspace: a call repeats bit for bit.
+ * Summation order of a dot product over the C channels, per kernel (csrc/corr_lookup.hip): the generic kernel, 16 lanes
+ * each with one chain of 4 * ceil(C / 64) fused multiply-adds, then added pairwise across the lanes; lanes across channels
+ * (C = 128), 32 lanes x a chain of 4, added pairwise; lane = position (C = 128), 16 interleaved chains of 8 in one lane,
+ * added pairwise.  Measured, not guaranteed: at the shapes of tests/test_gpu_corr_limits.py every kernel stays within twice
+ * the float32 rounding error of the formulas above evaluated in numpy.
  *
  * All pointers are DEVICE pointers; `stream` is a hipStream_t as void*.  Returns
  *   BT_EINVAL        a null pointer, a non-positive size, C not a multiple of 4, levels < 1, radius < 0, coord_stride < 2,

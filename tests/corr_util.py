@@ -125,3 +125,60 @@ def load_case(c):
     spec = CASES[c]
     fmaps, targets, coords3 = make_inputs(**spec)
     return fmaps[0], targets[0], coords3[0], spec
+
+
+# ---------------------------------------------------------------------------------- inputs at the limits (the *_limits tests)
+def limit_inputs(seed, S, C, H, W, N):
+    """make_inputs for any N >= 1: generated with at least N_SPECIAL queries and cut to the first N, so that the special
+    queries come first — 0 on (0, 0), 1 on (W-1, H-1), 2 far outside, 3 .. on quarter-pixel positions.  Returns
+    fmaps [S,C,H,W], targets [S,N,C], coords [S,N,2], float32 values as float64 arrays."""
+    fmaps, targets, coords3 = make_inputs(seed, S, C, H, W, max(N, N_SPECIAL))
+    return fmaps[0], targets[0, :, :N], coords3[0, :, :N, :2]
+
+
+def edge_queries(H, W, r):
+    """Coordinates a network can put out, as a list of (kind, x, y) with x, y float32 values:
+    'nonfinite' — +inf, -inf or NaN in x, in y or in both (every output is NaN);  'far' — +-3e9, +-(1e6 +- 0.5), 2^24 + 1
+    (every output is exactly 0);  'zero' — -0.0 and 1e-30 (the query on (0, 0), up to the gate);  'edge' — the integer
+    positions W-1, W-1+r, W+r, -r, -r-1 and the same on y, the other coordinate inside the map (W+r and -r-1 are the first
+    whose level-0 window is wholly outside: `outside` below)."""
+    inf, nan, f = np.inf, np.nan, lambda v: float(np.float32(v))
+    q = []
+    for v in (inf, -inf, nan):
+        q += [("nonfinite", v, 5.0), ("nonfinite", 5.0, v), ("nonfinite", v, v)]
+    q += [("nonfinite", inf, nan), ("nonfinite", -inf, inf)]
+    for v in (3e9, -3e9, 1e6 + 0.5, 1e6 - 0.5, -(1e6 + 0.5), -(1e6 - 0.5), 2.0 ** 24 + 1):
+        q += [("far", f(v), 5.0), ("far", 5.0, f(v)), ("far", f(v), f(v))]
+    q += [("far", f(3e9), f(-3e9))]
+    q += [("zero", -0.0, -0.0), ("zero", f(1e-30), f(1e-30)), ("zero", -0.0, f(1e-30))]
+    for v in (W - 1, W - 1 + r, -r):
+        q += [("edge", float(v), 5.0)]
+    for v in (H - 1, H - 1 + r, -r):
+        q += [("edge", 5.0, float(v))]
+    for v in (W + r, -r - 1):
+        q += [("outside", float(v), 5.0)]
+    for v in (H + r, -r - 1):
+        q += [("outside", 5.0, float(v))]
+    q += [("outside", float(W + r), float(-r - 1))]
+    return q
+
+
+def planted_inputs(seed, S, C, H, W, N, r):
+    """limit_inputs with edge_queries(H, W, r) planted from query N_SPECIAL on in every frame.  Returns fmaps, targets,
+    coords [S,N,2] (float64 arrays of float32 values), kinds [N] (the query's kind, '' for the others), and `calm`: coords
+    with every planted query on (5, 5)."""
+    fmaps, targets, coords = limit_inputs(seed, S, C, H, W, N)
+    q = edge_queries(H, W, r)
+    assert N >= N_SPECIAL + len(q)
+    kinds = np.array([""] * N, dtype=object)
+    calm = coords.copy()
+    for k, (kind, x, y) in enumerate(q, N_SPECIAL):
+        coords[:, k], calm[:, k], kinds[k] = (x, y), (5.0, 5.0), kind
+    return fmaps, targets, coords, kinds, calm
+
+
+def volume_lookup_cpu64(fmaps, targets, coords, L, r):
+    """volume_lookup on the CPU in float64, numpy in and out: [S,C,H,W], [S,N,C], [S,N,2] -> [S,N,L*(2r+1)^2]."""
+    import torch
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))[None]
+    return volume_lookup(t(fmaps), t(targets), t(coords), L, r)[0].numpy()

@@ -186,3 +186,38 @@ def test_import_surface():
             "assert 'oracle' not in sys.modules and _lib._lib is None and _lib._torch_ops is None; print('ok')")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+
+
+@pytest.mark.parametrize("C,r,L,H,W", [(16, 3, 4, 48, 64), (16, 4, 3, 45, 61), (8, 7, 3, 4, 4), (8, 3, 4, 8, 8), (8, 2, 1, 1, 37)])
+def test_restatement_agrees_with_the_volume_formulation_on_the_edge_inputs(C, r, L, H, W):
+    """What tests/test_gpu_corr_limits.py leans on.  On the planted coordinates of corr_util.edge_queries the float64
+    restatement and the float64 volume formulation agree to 1e-12 wherever both are defined (finite coordinates, levels
+    more than one pixel high and wide); a level one pixel high or wide is NaN in the volume formulation (it divides by
+    W_l - 1 = 0) and finite in the restatement; a query with a non-finite coordinate is NaN in every output of the volume
+    formulation; a far query is exactly 0 in both; the first integer positions wholly outside are exactly 0 at level 0."""
+    S, N, d = 2, 64, 2 * r + 1
+    fmaps, targets, coords, kinds, calm = corr_util.planted_inputs(41 + C + H, S, C, H, W, N, r)
+    nonfinite = kinds == "nonfinite"
+    assert np.array_equal(nonfinite, ~np.isfinite(coords).all((0, 2))) and nonfinite.sum() == 11
+    with np.errstate(all="ignore"):
+        vol = corr_util.volume_lookup_cpu64(fmaps, targets, coords, L, r).reshape(S, N, L, d * d)
+    ref = corr_util.np_corr_lookup(fmaps, targets, np.where(nonfinite[None, :, None], calm, coords), L, r).reshape(S, N, L, d * d)
+    assert np.isfinite(ref).all()
+    sizes = corr_util.level_sizes(H, W, L)
+    thin = np.array([min(h, w) == 1 for h, w in sizes])              # levels one pixel high or wide
+    assert thin.any() == (min(sizes[-1]) == 1)
+    assert np.isnan(vol[:, :, thin]).all()                            # every output of such a level, for every query
+    assert np.isnan(vol[:, nonfinite]).all()                          # at every level
+    assert not np.isnan(vol[:, ~nonfinite][:, :, ~thin]).any()
+    both = vol[:, ~nonfinite][:, :, ~thin], ref[:, ~nonfinite][:, :, ~thin]
+    if both[0].size:
+        assert np.abs(both[0] - both[1]).max() <= 1e-12, np.abs(both[0] - both[1]).max()
+    far = kinds == "far"
+    assert far.sum() == 22 and not ref[:, far].any() and not vol[:, far][:, :, ~thin].any()
+    assert not ref[:, 2, 0].any()                                     # (-40, -40): exactly 0 at level 0, for any r <= 7
+    assert not ref[:, kinds == "outside", 0].any() and (kinds == "outside").sum() == 5
+    if min(H, W) > 5:                                                 # (the other coordinate, 5, is inside the map)
+        assert ref[:, kinds == "edge"].any(-1).all()                  # the last positions whose window still meets the map
+    zero = np.where((kinds == "zero")[None, :, None], 0.0, coords)     # -0.0 and 1e-30 are 0 up to 1e-30 x a correlation
+    at0 = corr_util.np_corr_lookup(fmaps, targets, np.where(nonfinite[None, :, None], calm, zero), L, r).reshape(ref.shape)
+    assert np.abs(at0 - ref).max() <= 1e-28 and (kinds == "zero").sum() == 3

@@ -106,3 +106,52 @@ def test_point_cloud_step_is_off_by_default():
     cfg = SlamConfig(PATCHES_PER_FRAME=8, BUFFER_SIZE=5, UPDATE_POINT_CLOUD=True)
     w = WindowedBA(obs, ba=None, cfg=cfg)
     assert w.trajs_3d_world_.shape == (5, 8, w.S_local, 3) and w.points_.shape == (40, 3)
+
+
+INPUT_KEYS = ("poses", "intrinsics", "patches", "ix", "patches_local", "local_weights")
+
+
+def _sha(d):
+    import hashlib
+    h = hashlib.sha256()
+    for k in INPUT_KEYS:
+        h.update(np.ascontiguousarray(d[k]).tobytes())
+    return h.hexdigest()
+
+
+@pytest.mark.parametrize("args,seed,sha", [
+    ((51, 256, 12, 50), 307, "aefaad1c7fa71aa307178e79544f5fb2449c319b3a87d7dd30763828b2685382"),
+    ((12, 16, 4, 11), 5, "9680e07ac24658a8c4e0544265ad961bb0d140145abd145a7bf18f35487b378d")])
+def test_random_inputs_defaults_are_unchanged(args, seed, sha):
+    """The arrays random_inputs gave before it took `S_local=` and `p=` (their sha256, recorded then), bit for bit; the new
+    arguments at the values the defaults stand for give the same arrays, and `p=` changes the patches alone."""
+    d = world_util.random_inputs(*args, seed=seed)
+    assert _sha(d) == sha and d["m"] == args[3] * args[1]
+    assert d["patches"].shape == (args[0] * args[1], 3, 1, 1) and d["patches_local"].shape[1] == 2 * args[2] - 1
+    same = world_util.random_inputs(*args, seed=seed, S_local=2 * args[2] - 1)
+    assert _sha(same) == sha
+    p3 = world_util.random_inputs(*args, seed=seed, p=3)
+    assert all(np.array_equal(p3[k], d[k]) for k in INPUT_KEYS if k != "patches")
+    assert np.array_equal(p3["patches"][:, :, 1, 1], d["patches"][:, :, 0, 0])
+    even = world_util.random_inputs(*args, seed=seed, S_local=8)
+    assert even["patches_local"].shape == (args[0] * args[1], 8, 3) and even["local_weights"].shape == (args[0] * args[1], 8)
+    assert all(np.array_equal(even[k], d[k]) for k in ("poses", "intrinsics", "patches", "ix"))
+
+
+@pytest.mark.parametrize("p", [2, 3, 64])
+def test_specification_picks_the_centre_of_decoy_filled_patches(p):
+    """Every pixel but (p/2, p/2) of the p x p patches is a decoy in +-1000: the restatement's result equals the p = 1
+    result bit for bit, in float32 and in float64, and a neighbouring pixel taken for the centre moves it by far more than
+    any gate."""
+    one = world_util.random_inputs(12, 16, 4, 11, seed=5)
+    dec = world_util.random_inputs(12, 16, 4, 11, seed=5, p=p)
+    assert dec["patches"].shape == (192, 3, p, p)
+    off = np.ones((p, p), bool)
+    off[p // 2, p // 2] = False
+    assert np.abs(dec["patches"][..., off]).max() > 900 and (np.abs(dec["patches"][..., off]) > 1.5).mean() > 0.99
+    for dt in (np.float32, np.float64):
+        run = lambda d: world_util.np_world_tracks(*(d[k] if k == "ix" else d[k].astype(dt) for k in INPUT_KEYS), d["m"])[:3]
+        a, b = run(one), run(dec)
+        assert all(x.dtype == dt and np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+        wrong = dict(dec, patches=np.roll(dec["patches"], 1, axis=-1))          # the pixel left of the centre in its place
+        assert world_util.rel_err(run(wrong)[0], a[0].astype(np.float64)) > 0.1     # the measure saturates near 1; gates are ~1e-6

@@ -86,7 +86,7 @@ def uv_err(got, ref):
     return float((np.abs(got[tame].astype(np.float64) - ref[tame]) / (100.0 + np.abs(ref[tame]))).max()), float(tame.mean())
 
 
-def random_inputs(N, M, S_slam, n, seed, live_frac=0.7):
+def random_inputs(N, M, S_slam, n, seed, live_frac=0.7, S_local=None, p=None):
     """Seeded float32 inputs at a user's size, numpy.  The camera circles (radius 0.3, 0.02 a frame) and sways in front of
     the scene through the whole buffer, disparities in [0.2, 1]: |t| <= 0.7 and |t| / d <= 3.5 as in fixture case (a).  The
     rounding of a float32 evaluation is a few ulp of the intermediate magnitudes |t|, |t| / d, which the measure
@@ -94,9 +94,12 @@ def random_inputs(N, M, S_slam, n, seed, live_frac=0.7):
     measured at (measured on the GPU: with the camera 4 units from the origin the older composed operations themselves are
     2.8e-6 from a float64 evaluation, 30 x e32).  Tracks lie in front of every camera of their window (camera-frame depth
     > 0.5, away from the 1e-2 clamp), about `live_frac` of them are live, a quarter of the other tracks' slots were never
-    filled.  Returns a dict with the arguments of the C entry point and m = n * M."""
+    filled.  `S_local`: any window length in place of 2 * S_slam - 1, even ones included.  `p`: p x p patches whose centre pixel
+    (p/2, p/2) is the track and whose every other pixel is a decoy in +-1000 (a wrong centre index or plane stride moves the
+    result by far more than any gate); drawn after everything else, so that the other arrays do not depend on it.  Returns
+    a dict with the arguments of the C entry point and m = n * M."""
     rng = np.random.default_rng(seed)
-    S, NM = 2 * S_slam - 1, N * M
+    S, NM = (2 * S_slam - 1 if S_local is None else int(S_local)), N * M
     s = np.arange(N)[:, None]
     th = s / 15.0                                                                       # a circle of radius 0.3: 0.02 a frame
     centre = np.concatenate([0.3 * np.sin(th), 0.05 * np.sin(0.7 * s), 0.3 * (1.0 - np.cos(th))], 1)
@@ -113,7 +116,12 @@ def random_inputs(N, M, S_slam, n, seed, live_frac=0.7):
     w[~live] = 0.0
     pl[(rng.random((NM, S)) < 0.25) & ~live[:, None]] = 0.0
     f = lambda a: np.ascontiguousarray(a, np.float32)
-    return dict(poses=f(np.concatenate([t, q], 1)), intrinsics=f(K), patches=f(patches).reshape(NM, 3, 1, 1),
+    patches = patches.reshape(NM, 3, 1, 1)
+    if p is not None:
+        track = patches[..., 0, 0]
+        patches = rng.uniform(-1000.0, 1000.0, (NM, 3, p, p))
+        patches[:, :, p // 2, p // 2] = track
+    return dict(poses=f(np.concatenate([t, q], 1)), intrinsics=f(K), patches=f(patches),
                 ix=(np.arange(NM) // M).astype(np.int64), patches_local=f(pl), local_weights=f(w), m=n * M)
 
 
