@@ -6,8 +6,10 @@
 //   k_de_pick     one workgroup, one wave per selection: the digit that holds the remaining rank, narrowing (prefix, rank); after
 //                 the last pass the medians and their ratio (numpy's median: an even count takes the float64 mean of the two
 //                 middle elements).
-//   k_de_sums     least-squares scaling: per-workgroup float64 sums of 1, p, p^2, g, p g;  k_de_solve: their fixed-order total and
-//                 the 2x2 normal equations (minimum-norm solution when singular, as np.linalg.lstsq).
+//   k_de_sums     least-squares scaling: per-workgroup count, means and centred second moments of (p, g) in float64, each thread's
+//                 sums taken about its first valid element and merged pairwise (Chan et al.) in a fixed order;  k_de_solve: the
+//                 same merge over the workgroups, s = Cpg / Cpp, t = mean g - s mean p, the rank decision from det = n Cpp
+//                 (minimum-norm solution when singular, as np.linalg.lstsq).
 //   k_de_metrics  scaling, clamping and the eight metrics' per-element terms in float64; per-workgroup float64 partials;
 //   k_de_final    their fixed-order total.  No float atomics anywhere: a call is bit-for-bit repeatable.
 // Workgroups hand results to each other only at kernel boundaries; everything is enqueued on the caller's stream.
@@ -166,48 +168,94 @@ __device__ __forceinline__ double block_sum_d(double v, double *red) {     // bl
     return t;                                                              // valid in thread 0
 }
 
+// least-squares scaling: count, means and centred second moments of the valid (p, g).  The raw sums of p^2 and p g would leave
+// det = Spp n - Sp^2 to cancel on a pred of small relative spread; these do not.
+struct Mom {
+    double n, mp, mg, cpp, cpg;                  // count, mean p, mean g, sum (p - mp)^2, sum (p - mp)(g - mg)
+};
+
+// a then b as one set (Chan, Golub, LeVeque); an empty side leaves the other as it is
+__device__ __forceinline__ Mom merge(const Mom &a, const Mom &b) {
+#pragma clang fp contract(off)
+    if (b.n == 0.0) return a;
+    if (a.n == 0.0) return b;
+    Mom r;
+    r.n = a.n + b.n;
+    const double w = b.n / r.n, aw = a.n * w, dp = b.mp - a.mp, dg = b.mg - a.mg;
+    r.mp = a.mp + dp * w;
+    r.mg = a.mg + dg * w;
+    r.cpp = a.cpp + b.cpp + dp * dp * aw;
+    r.cpg = a.cpg + b.cpg + dp * dg * aw;
+    return r;
+}
+
+__device__ __forceinline__ Mom block_merge(Mom v, Mom *red) {             // blockDim.x <= 1024; fixed order, the lower lane first
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {
+        Mom u;
+        u.n = __shfl_xor(v.n, o); u.mp = __shfl_xor(v.mp, o); u.mg = __shfl_xor(v.mg, o);
+        u.cpp = __shfl_xor(v.cpp, o); u.cpg = __shfl_xor(v.cpg, o);
+        v = (lane & o) ? merge(u, v) : merge(v, u);
+    }
+    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int i = 1; i < nw; ++i) v = merge(v, red[i]);
+    return v;                                                              // valid in thread 0
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(kSumThreads) void k_de_sums(const float *gt, const float *pred, const uint8_t *mask, int64_t n, float dmin,
                                                          float dmax, unsigned char *ws) {
 #pragma clang fp contract(off)
-    __shared__ double red[16];
-    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    __shared__ Mom red[16];
+    // per thread: sums about its first valid element (p0, g0), which lies within the data's spread of their mean
+    double c = 0.0, p0 = 0.0, g0 = 0.0, s1 = 0.0, s2 = 0.0, sg = 0.0, spg = 0.0;
     for_elems<VEC>(gt, pred, mask, n, [&](float g, float p, bool m) {
         if (m && g > dmin && g < dmax) {
-            const double gd = g, pd = p;
-            s[0] += 1.0; s[1] += pd; s[2] += pd * pd; s[3] += gd; s[4] += pd * gd;
+            if (c == 0.0) { p0 = p; g0 = g; }
+            const double dp = (double)p - p0, dg = (double)g - g0;
+            c += 1.0; s1 += dp; s2 += dp * dp; sg += dg; spg += dp * dg;
         }
     });
-    double *out = partials(ws) + (size_t)blockIdx.x * kParts;
-    for (int q = 0; q < 5; ++q) {
-        const double t = block_sum_d(s[q], red);
-        if (threadIdx.x == 0) out[q] = t;
+    Mom v = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (c > 0.0) {
+        v.n = c;
+        v.mp = p0 + s1 / c;
+        v.mg = g0 + sg / c;
+        v.cpp = s2 - s1 * s1 / c;
+        v.cpg = spg - s1 * sg / c;
+    }
+    v = block_merge(v, red);
+    if (threadIdx.x == 0) {
+        double *out = partials(ws) + (size_t)blockIdx.x * kParts;
+        out[0] = v.n; out[1] = v.mp; out[2] = v.mg; out[3] = v.cpp; out[4] = v.cpg;
     }
 }
 
 __global__ __launch_bounds__(256) void k_de_solve(unsigned char *ws, int nb) {
 #pragma clang fp contract(off)
-    __shared__ double red[16];
-    __shared__ double tot[5];
+    __shared__ Mom red[16];
     const double *part = partials(ws);
-    for (int q = 0; q < 5; ++q) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < nb; b += blockDim.x) v += part[(size_t)b * kParts + q];
-        v = block_sum_d(v, red);
-        if (threadIdx.x == 0) tot[q] = v;
+    Mom v = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+        const double *q = part + (size_t)b * kParts;
+        v = merge(v, Mom{q[0], q[1], q[2], q[3], q[4]});
     }
-    __syncthreads();
+    v = block_merge(v, red);
     if (threadIdx.x != 0) return;
-    // A = [p, 1]:  A^T A = [[Spp, Sp], [Sp, n]],  A^T g = (Spg, Sg)
-    const double n = tot[0], sp = tot[1], spp = tot[2], sg = tot[3], spg = tot[4];
-    const double a = spp, b = sp, d = n, tr = a + d, det = a * d - b * b;
+    // A = [p, 1]:  A^T A = [[Spp, Sp], [Sp, n]],  A^T g = (Spg, Sg);  det(A^T A) = n Cpp, without the cancellation of Spp n - Sp^2
+    const double n = v.n, sp = n * v.mp, spp = v.cpp + sp * v.mp, sg = n * v.mg, spg = v.cpg + sp * v.mg;
+    const double a = spp, b = sp, d = n, tr = a + d, det = n * v.cpp;
     const double disc = tr * tr / 4.0 - det;
     const double lmax = tr / 2.0 + sqrt(disc > 0.0 ? disc : 0.0);
     const double rc = 2.220446049250313e-16 * (n > 2.0 ? n : 2.0);        // np.linalg.lstsq(rcond=None): eps * max(M, N)
     double s = 0.0, t = 0.0;
     if (det > rc * rc * lmax * lmax) {                                     // sigma_min > rcond * sigma_max
-        s = (d * spg - b * sg) / det;
-        t = (a * sg - b * spg) / det;
+        s = v.cpg / v.cpp;
+        t = v.mg - s * v.mp;
     } else if (lmax > 0.0) {                                               // rank 1: the minimum-norm solution v (v . A^T g) / lambda_max
         double v0 = b, v1 = lmax - a;
         const double u0 = lmax - d, u1 = b;

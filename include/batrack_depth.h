@@ -30,14 +30,19 @@ int64_t bt_depth_metrics_workspace_bytes(int64_t n);
  *   valid = mask & (gt > depth_min) & (gt < depth_max)          (mask NULL: every element; a nonzero byte is true)
  * scaling BT_DEPTH_SCALE_MEDIAN: pred *= median(gt_v) / median(pred_v), numpy's median (exact selection; an even count takes
  *   the float64 mean of the two middle elements) by radix select on the order-preserving key of the float32 values;
- * BT_DEPTH_SCALE_LSTSQ: pred = s pred + t, (s, t) the least-squares fit of gt by [pred, 1] from float64 sums of 1, p, p^2, g,
- *   p g; a singular system (in np.linalg.lstsq's sense, rcond = eps * max(count, 2)) gets the minimum-norm solution;
+ * BT_DEPTH_SCALE_LSTSQ: pred = s pred + t, (s, t) the least-squares fit of gt by [pred, 1] from the count, the means and the
+ *   centred second moments Cpp = sum (p - mean p)^2, Cpg = sum (p - mean p)(g - mean g) in float64 (merged pairwise in a fixed
+ *   order): s = Cpg / Cpp, t = mean g - s mean p, so a pred of small relative spread loses nothing to cancellation; a singular
+ *   system (in np.linalg.lstsq's sense, sigma_min <= rcond sigma_max with rcond = eps * max(count, 2), decided from
+ *   det = count Cpp) gets the minimum-norm solution;
  * BT_DEPTH_SCALE_NONE: no scaling.
  * Then pred is clamped to [depth_min, depth_max] and every per-element operation runs in float64 on the float32 inputs.
  * out [11] (device, float64): abs_rel, sq_rel, log10, rmse, rmse_log, a1, a2, a3 (the reference's order), then the valid count,
  * the ratio (median) or s (lstsq) or 1, and t (lstsq) or 0.  An empty valid set gives NaN for the eight metrics (BT_OK); a NaN
  * among the valid preds propagates as numpy propagates it.  Sums are per-workgroup float64 partials reduced in a fixed order:
- * a call is bit-for-bit repeatable.  `workspace`: bt_depth_metrics_workspace_bytes(n) bytes, 256-byte aligned.  n > 2^31 - 1:
+ * a call is bit-for-bit repeatable.  The median's key takes -0 and +0 for one value and decodes it as +0, where numpy returns
+ * whichever zero sits in the middle: the sign of a median that is zero is not pinned.  `workspace`:
+ * bt_depth_metrics_workspace_bytes(n) bytes, 16-byte aligned (BT_EINVAL otherwise), contents arbitrary.  n > 2^31 - 1:
  * BT_EUNSUPPORTED, checked before anything is enqueued.  Enqueued on `stream`. */
 int bt_depth_metrics(const float *gt, const float *pred, const uint8_t *mask, int64_t n, float depth_min, float depth_max,
                      int32_t scaling, void *workspace, double *out, void *stream);

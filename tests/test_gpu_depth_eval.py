@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from depth_util import np_depth_metrics
+from depth_util import check_gates, np_depth_metrics
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,13 +39,6 @@ def metrics(gt, pred, mask=None, dmin=1e-2, dmax=1e2, scaling="median"):
     t = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32), device=DEV)
     m = None if mask is None else (mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask, bool), device=DEV))
     return depth_metrics(t(gt), t(pred), m, dmin, dmax, scaling)
-
-
-def check_gates(r, ref, count, scaling):
-    assert r[8] == count
-    np.testing.assert_allclose(r[:5], ref[:5], rtol=1e-9)
-    tol = 1.0 / count if scaling == "lstsq" else 0.0
-    assert np.abs(r[5:8] - ref[5:8]).max() <= tol, (r[5:8], ref[5:8])
 
 
 # ---------------------------------------------------------------------- bt_depth_metrics
