@@ -93,7 +93,12 @@ int64_t bt_mono_align_workspace_bytes(int64_t T, int64_t hw, int32_t dtype);
  * `mono` [T, hw] float32, `metric` [T, hw] D, `depth_out` [T, hw] D: device, contiguous.  Optional (NULL: not written), in D:
  * frame_scale [T] (s), frame_shift [T] (c), aligns [3] (a_s, a_c, n); med_index [1] int64 (k).  The whole computation is one fixed
  * sequence of launches on `stream`: the medians, k and n stay in device state (integer atomics only: a call repeats bit for bit).
- * `workspace`: bt_mono_align_workspace_bytes(T, hw, dtype) bytes, 16-byte aligned, contents arbitrary.  BT_EINVAL for T < 1,
+ * The optional outputs are independent: any of the 16 patterns of NULL gives the same depth_out and the same values in the
+ * outputs that are present.  mono, metric and depth_out need their element's alignment only: 16-byte aligned pointers (with
+ * hw % 4 == 0 for the per-frame passes) take 16-byte loads and stores, any other the scalar kernels, with the same bits.  The
+ * call reads mono and metric and writes nothing but the outputs' own elements and the workspace.
+ * `workspace`: bt_mono_align_workspace_bytes(T, hw, dtype) bytes, 16-byte aligned, contents arbitrary (what an earlier call left,
+ * of this or another T, included: every call clears what it reads).  BT_EINVAL for T < 1,
  * hw < 1, a bad dtype, a NULL mono / metric / depth_out / workspace, a pointer not aligned to its element, or an output or the
  * workspace that overlaps an input (or the workspace an output); BT_EUNSUPPORTED for T * hw > 2^31 - 1; both before anything is
  * enqueued. */
