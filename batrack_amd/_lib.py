@@ -8,11 +8,12 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip"]
+SOURCES = ["ba_kernels.hip", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip"]
 HEADERS = ["ba_kernels.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
-           os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h")]
+           os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
+           os.path.join("..", "..", "include", "batrack_observe.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -23,7 +24,8 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
                            "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
                            "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward, or more than 8192 cells wide in "
                            "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene; world tracks: a window of more than 2^20 frames; "
-                           "correlation lookup: more than 512 channels, a radius above 7, more than 8 levels, a map side above 32768, or more than 2^31 - 1 (frame, query, level) triples)"}
+                           "correlation lookup: more than 512 channels, a radius above 7, more than 8 levels, a map side above 32768, or more than 2^31 - 1 (frame, query, level) triples; "
+                           "window observations: a window of more than 64 frames, 2^24 or more scores, or window buffers of 2^31 or more slots)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -55,6 +57,16 @@ class GaArgs(ctypes.Structure):                       # == bt_ga_args in include
 
 class GaWeights(ctypes.Structure):                    # == bt_ga_weights
     _fields_ = [(n, ctypes.c_float) for n in ("spatial", "rigid", "pts3d", "cam_smooth", "scale_smooth")] + [("smooth_mode", ctypes.c_int32)]
+
+
+class ObserveArgs(ctypes.Structure):                 # == bt_observe_args in include/batrack_observe.h
+    _fields_ = ([(n, ctypes.c_int64) for n in ("S", "Sp", "Nq", "E", "n", "M", "N", "kf_stride", "S_local", "H", "W", "interp_w",
+                                               "interp_h", "padding", "min_track_len")] +
+                [(n, ctypes.c_int32) for n in ("has_vis_threshold", "is_initialized")] +
+                [(n, ctypes.c_double) for n in ("wd", "ht", "vis_threshold", "static_quantile", "static_threshold")] +
+                [(n, ctypes.c_void_p) for n in ("traj", "depth", "vis", "dyn", "queries", "dmaps", "ii", "jj", "kk", "patches_valid",
+                                                "patches_local", "local_monodisp", "local_vis", "local_static", "local_weights",
+                                                "targets_3d", "weights", "weights_pose", "query_disp")])
 
 
 def kernel_sources_sha16():
@@ -286,6 +298,10 @@ def lib():
     L.bt_corr_lookup.argtypes = [vp, i64, i64, i64, i64, i32, i32, vp, vp, i64, i64, vp, vp]
     L.bt_config_corr_lookup_layout.restype = i32
     L.bt_config_corr_lookup_layout.argtypes = [i32]
+    L.bt_observe_workspace_bytes.restype = ctypes.c_size_t
+    L.bt_observe_workspace_bytes.argtypes = []
+    L.bt_observe_window.restype = i32
+    L.bt_observe_window.argtypes = [ctypes.POINTER(ObserveArgs), vp, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

@@ -28,6 +28,16 @@
 //   batrack_hip::corr_lookup(Tensor pyramid, int[] shape, int levels, int radius, Tensor targets, Tensor coords) -> Tensor
 //       bt_corr_lookup: shape = [S', C, H, W] of the maps the pyramid was made from, targets [..., N, C], coords [..., N, 2]
 //       (the strided view `coords3[..., :2]` is read in place) -> [..., N, levels * (2 radius + 1)^2]
+//   batrack_hip::observe_window(Tensor traj, Tensor depth, Tensor vis, Tensor dyn, Tensor queries, Tensor? dmaps, Tensor ii, Tensor jj,
+//                               Tensor kk, Tensor(a!) patches_valid, Tensor(b!) patches_local, Tensor(c!)? local_monodisp,
+//                               Tensor(d!)? local_vis, Tensor(e!)? local_static, Tensor(f!)? local_weights, Tensor(g!) workspace,
+//                               int n, int Sp, int kf_stride, int H, int W, float wd, float ht, int padding, float? vis_threshold,
+//                               float static_quantile, float static_threshold, int min_track_len, bool is_initialized,
+//                               int interp_w, int interp_h) -> (Tensor, Tensor, Tensor, Tensor)
+//       bt_observe_window (include/batrack_observe.h): traj [S, Nq, 2], depth / vis / dyn [S, Nq], queries [Nq, 3], dmaps [Sp, H, W],
+//       ii / jj / kk [Nq*Sp] int64, patches_valid [N, M], patches_local [N*M, S_local, 3], the other window buffers [N*M, S_local],
+//       workspace: bt_observe_workspace_bytes() bytes -> targets_3d [E, 3], weights [E, 2], weights_pose [E, 2], query_disp [Nq]
+//       (query_disp is empty without dmaps)
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -38,6 +48,7 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_corr.h"
+#include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
 
 namespace {
@@ -235,6 +246,65 @@ at::Tensor corr_lookup(const at::Tensor &pyramid, c10::ArrayRef<int64_t> shape, 
     return out;
 }
 
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> observe_window(
+        const at::Tensor &traj, const at::Tensor &depth, const at::Tensor &vis, const at::Tensor &dyn, const at::Tensor &queries,
+        const c10::optional<at::Tensor> &dmaps, const at::Tensor &ii, const at::Tensor &jj, const at::Tensor &kk,
+        const at::Tensor &patches_valid, const at::Tensor &patches_local, const c10::optional<at::Tensor> &local_monodisp,
+        const c10::optional<at::Tensor> &local_vis, const c10::optional<at::Tensor> &local_static,
+        const c10::optional<at::Tensor> &local_weights, const at::Tensor &workspace, int64_t n, int64_t Sp, int64_t kf_stride, int64_t H,
+        int64_t W, double wd, double ht, int64_t padding, c10::optional<double> vis_threshold, double static_quantile,
+        double static_threshold, int64_t min_track_len, bool is_initialized, int64_t interp_w, int64_t interp_h) {
+    const char *op = "batrack_hip::observe_window: ";
+    bt_observe_args a{};
+    a.traj = f32(traj, "traj"); a.depth = f32(depth, "depth"); a.vis = f32(vis, "vis"); a.dyn = f32(dyn, "dyn");
+    a.queries = f32(queries, "queries");
+    a.patches_valid = const_cast<float *>(f32(patches_valid, "patches_valid"));
+    a.patches_local = const_cast<float *>(f32(patches_local, "patches_local"));
+    const auto dev = traj.device();
+    for (const at::Tensor *t : {&traj, &depth, &vis, &dyn, &queries, &patches_valid, &patches_local, &ii, &jj, &kk, &workspace})
+        TORCH_CHECK(t->is_contiguous() && t->device() == dev, op, "tensors must be contiguous and on one device");
+    TORCH_CHECK(traj.dim() == 3 && traj.size(2) == 2, op, "traj must be [S, Nq, 2]");
+    const int64_t S = traj.size(0), Nq = traj.size(1);
+    for (const at::Tensor *t : {&depth, &vis, &dyn})
+        TORCH_CHECK(t->numel() == S * Nq, op, "depth, vis and dyn must be [S, Nq]");
+    TORCH_CHECK(queries.numel() == 3 * Nq, op, "queries must be [Nq, 3]");
+    TORCH_CHECK(Sp >= 0 && Sp <= S, op, "Sp frames of the window must fit its padded length S");
+    const int64_t E = Nq * Sp;
+    for (const at::Tensor *t : {&ii, &jj, &kk})
+        TORCH_CHECK(t->scalar_type() == at::kLong && t->numel() == E, op, "ii, jj, kk must be int64 of Nq*Sp edges");
+    TORCH_CHECK(patches_valid.dim() == 2, op, "patches_valid must be [N, M]");
+    const int64_t N = patches_valid.size(0), M = patches_valid.size(1);
+    TORCH_CHECK(patches_local.dim() == 3 && patches_local.size(0) == N * M && patches_local.size(2) == 3, op,
+                "patches_local must be [N*M, S_local, 3]");
+    const int64_t S_local = patches_local.size(1);
+    float **opt[4] = {&a.local_monodisp, &a.local_vis, &a.local_static, &a.local_weights};
+    const c10::optional<at::Tensor> *ot[4] = {&local_monodisp, &local_vis, &local_static, &local_weights};
+    for (int i = 0; i < 4; ++i)
+        if (ot[i]->has_value()) {
+            const at::Tensor &t = **ot[i];
+            TORCH_CHECK(t.is_contiguous() && t.device() == dev && t.numel() == N * M * S_local, op, "a window buffer must be contiguous [N*M, S_local]");
+            *opt[i] = const_cast<float *>(f32(t, "window buffer"));
+        }
+    if (dmaps.has_value()) {
+        TORCH_CHECK(dmaps->is_contiguous() && dmaps->device() == dev && dmaps->numel() == Sp * H * W, op, "dmaps must be contiguous [Sp, H, W]");
+        a.dmaps = f32(*dmaps, "dmaps");
+    }
+    TORCH_CHECK(workspace.is_cuda() && workspace.numel() * workspace.element_size() >= (int64_t)bt_observe_workspace_bytes(), op,
+                "the workspace is smaller than bt_observe_workspace_bytes()");
+    at::Tensor targets = at::empty({E, 3}, traj.options()), weights = at::empty({E, 2}, traj.options()),
+               weights_pose = at::empty({E, 2}, traj.options()), query_disp = at::empty({a.dmaps ? Nq : 0}, traj.options());
+    a.targets_3d = targets.data_ptr<float>(); a.weights = weights.data_ptr<float>(); a.weights_pose = weights_pose.data_ptr<float>();
+    a.query_disp = a.dmaps ? query_disp.data_ptr<float>() : nullptr;
+    a.ii = ii.data_ptr<int64_t>(); a.jj = jj.data_ptr<int64_t>(); a.kk = kk.data_ptr<int64_t>();
+    a.S = S; a.Sp = Sp; a.Nq = Nq; a.E = E; a.n = n; a.M = M; a.N = N; a.kf_stride = kf_stride; a.S_local = S_local; a.H = H; a.W = W;
+    a.interp_w = interp_w; a.interp_h = interp_h; a.padding = padding; a.min_track_len = min_track_len;
+    a.has_vis_threshold = vis_threshold.has_value() ? 1 : 0; a.is_initialized = is_initialized ? 1 : 0;
+    a.wd = wd; a.ht = ht; a.vis_threshold = vis_threshold.value_or(0.0); a.static_quantile = static_quantile; a.static_threshold = static_threshold;
+    const int rc = bt_observe_window(&a, workspace.data_ptr(), c10::hip::getCurrentHIPStream(dev.index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_observe_window failed with status ", rc);
+    return {targets, weights, weights_pose, query_disp};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -249,6 +319,11 @@ TORCH_LIBRARY(batrack_hip, m) {
           "Tensor? lmbda_per_track=None) -> (Tensor, Tensor)", &ba_droid);
     m.def("world_tracks(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ix, Tensor(a!) patches_local, Tensor local_weights, "
           "int m, Tensor(b!)? points=None, Tensor(c!)? world=None) -> ()", &world_tracks);
+    m.def("observe_window(Tensor traj, Tensor depth, Tensor vis, Tensor dyn, Tensor queries, Tensor? dmaps, Tensor ii, Tensor jj, Tensor kk, "
+          "Tensor(a!) patches_valid, Tensor(b!) patches_local, Tensor(c!)? local_monodisp, Tensor(d!)? local_vis, Tensor(e!)? local_static, "
+          "Tensor(f!)? local_weights, Tensor(g!) workspace, int n, int Sp, int kf_stride, int H, int W, float wd, float ht, int padding, "
+          "float? vis_threshold, float static_quantile, float static_threshold, int min_track_len, bool is_initialized, int interp_w, "
+          "int interp_h) -> (Tensor, Tensor, Tensor, Tensor)", &observe_window);
     m.def("corr_pyramid(Tensor fmaps, int levels) -> Tensor", &corr_pyramid);
     m.def("corr_lookup(Tensor pyramid, int[] shape, int levels, int radius, Tensor targets, Tensor coords) -> Tensor", &corr_lookup);
 }

@@ -91,6 +91,23 @@ class SyntheticObservations:
         vis = (Z > 0.2) & (self._rng.random(E) >= self.drop_frac)
         return t3, vis, ~self.dynamic[kk]
 
+    def predict_window(self, kk, jj, S):
+        """The draws of `predict` for the window's edges (track-major: all frames of a track together), shaped as the
+        tracker network returns them for a window padded to S frames — traj [1,S,Nq,2] in full-image pixels, depth
+        [1,S,Nq,1] (the reciprocal of predict's disparity), vis [1,S,Nq] (1 / 0), dyn [1,S,Nq] (1 for a moving track) —
+        plus queries [1,Nq,3] = (frame within the window, x, y) of the tracks, as `get_queries` (batrack.py:459-480).  The
+        padded frames repeat the last one (batrack.py:692-694).  numpy, float32."""
+        t3, vis, static = self.predict(kk, jj)
+        lo = int(jj.min())
+        Sp = int(jj.max()) - lo + 1
+        Nq = kk.shape[0] // Sp
+        pad = lambda a: np.concatenate([a] + [a[-1:]] * (S - Sp)).astype(np.float32)[None]
+        fr = lambda a: np.swapaxes(a.reshape(Nq, Sp, *a.shape[1:]), 0, 1)
+        q = kk.reshape(Nq, Sp)[:, 0]
+        queries = np.concatenate([(q // self.M - lo)[:, None], self.xy[q]], 1).astype(np.float32)[None]
+        return (pad(fr(t3[:, :2])), pad(fr(1.0 / t3[:, 2:])), pad(fr(vis.astype(np.float64))),
+                pad(fr(1.0 - static.astype(np.float64))), queries)
+
     def depth_map(self, f):
         """Stand-in for the mono-depth network's map of frame f (`depth` of BATRACK.__call__, batrack.py:937; what
         `get_results(dmaps=...)` stores): a smooth positive field [ht, wd, 1], float32.  It is not the surface the tracks lie
@@ -119,8 +136,13 @@ class WindowedBA:
     without it: with it off nothing is allocated or computed, and the depth prior of a track stays the tracker's
     disparity for the track's whole life, where the reference hands a live track its current estimate."""
 
-    def __init__(self, obs, ba, cfg=None, device="cpu", sync=None, prefetch=None, se3=SE3):
-        """se3: the pose class (default: the HIP-backed batrack_amd.backend.lietorch.SE3, GPU tensors only; the CPU-side
+    def __init__(self, obs, ba, cfg=None, device="cpu", sync=None, prefetch=None, se3=SE3, observer=None):
+        """observer: optional function with the signature of `batrack_amd.frontend.observe.window_observations`.  With it,
+        `predict_target` hands the observation model's window tensors (`obs.predict_window`) and the window's depth maps
+        to it and appends what it returns: the step between the tracker and the BA then runs where the observer runs, and
+        the object also owns `patches_monodisp_` [N, M, 1] and `patches_local_monodisp_` (batrack.py:80,85).  Without it
+        (the default) the labels come from the observation model on the host, as they always have.
+        se3: the pose class (default: the HIP-backed batrack_amd.backend.lietorch.SE3, GPU tensors only; the CPU-side
         tests of this loop pass the test oracle's torch formulas (SE3Ref) together with the oracle `ba`).
         prefetch: optional `batrack_amd.backend.ba.prefetch_plan`; it is called where the reference knows the
         edge list of the coming update() — after `append_factors` (before the tracker pass that `predict_target`
@@ -152,6 +174,11 @@ class WindowedBA:
             self.trajs_3d_world_ = torch.zeros(self.N, self.M, self.S_local, 3, **f32)         # batrack.py:87
             self.points_ = torch.zeros(self.N * self.M, 3, **f32)                              # batrack.py:94
             self.ix = torch.arange(self.N * self.M, **i64) // self.M                           # a track's source frame (index_)
+        self.observer = observer
+        if observer is not None:
+            self.patches_monodisp_ = torch.zeros(self.N, self.M, 1, **f32)                     # batrack.py:85
+            self.patches_local_monodisp_ = torch.zeros(self.N, self.M, self.S_local, 1, **f32)  # batrack.py:80
+            self._dmaps = {}
         self.tstamps_ = torch.zeros(self.N, **i64)
         self.tlist, self.counter = [], 0
         self.ii, self.jj, self.kk = (torch.zeros(0, **i64) for _ in range(3))
@@ -213,6 +240,8 @@ class WindowedBA:
 
     # ---- batrack.py:760-795 (labels from the synthetic observation model)
     def predict_target(self):
+        if self.observer is not None:
+            return self._observe_target()
         kk, jj = self._kk_new.cpu().numpy(), self._jj_new.cpu().numpy()
         t3, vis, static = self.obs.predict(kk, jj)
         S = min(self.n, self.cfg.S_slam)
@@ -233,6 +262,32 @@ class WindowedBA:
         self.weights = torch.cat([self.weights, w_t], 1)
         self.weights_pose = torch.cat([self.weights_pose, torch.as_tensor(wp, **f32)[None]], 1)
         self.update_local(t3_t, w_t, torch.as_tensor(vis, device=self.device)[None], torch.as_tensor(static, device=self.device)[None])
+
+    # ---- batrack.py:760-818 through the observer: get_window_trajs, predict_target and update_local in one call
+    def _observe_target(self):
+        from .frontend.observe import ObserveConfig
+        c = self.cfg
+        Sp = min(self.n, c.S_slam)
+        lo = self.n - Sp
+        up = lambda a: torch.as_tensor(a, dtype=torch.float32, device=self.device)
+        window = [up(a) for a in self.obs.predict_window(self._kk_new.cpu().numpy(), self._jj_new.cpu().numpy(), c.S_slam)]
+        for f in range(lo, self.n):
+            if f not in self._dmaps:
+                self._dmaps[f] = up(self.obs.depth_map(f)[..., 0])
+        for f in [f for f in self._dmaps if f < lo]:
+            del self._dmaps[f]
+        dmaps = torch.stack([self._dmaps[f] for f in range(lo, self.n)])
+        t3, w, wp, qd = self.observer(*window, dmaps, self._kk_new // self.M, self._jj_new, self._kk_new,
+                                      patches_valid=self.patches_valid_, patches_local=self.patches_local_,
+                                      local_monodisp=self.patches_local_monodisp_, local_vis=self.patches_local_vis_,
+                                      local_static=self.patches_local_static_, local_weights=self.patches_local_weights_,
+                                      n=self.n, window=Sp, kf_stride=c.kf_stride, wd=self.wd, ht=self.ht,
+                                      cfg=ObserveConfig(MIN_TRACK_LEN=c.MIN_TRACK_LEN), is_initialized=self.is_initialized,
+                                      interp_shape=None)
+        self.patches_monodisp_[lo:self.n:c.kf_stride] = qd.view(-1, self.M, 1)                 # batrack.py:687-689
+        self.targets_3d = torch.cat([self.targets_3d, t3], 1)
+        self.weights = torch.cat([self.weights, w], 1)
+        self.weights_pose = torch.cat([self.weights_pose, wp], 1)
 
     # ---- batrack.py:632-663
     def update_local(self, target_3d, weights, vis_e, static_e):
