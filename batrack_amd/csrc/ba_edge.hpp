@@ -1,4 +1,4 @@
-// ba_edge.hpp — device helpers shared by the tile kernels (ba_kernels.hip) and the wave-per-tile
+// ba_edge.hpp — device helpers shared by the tile kernels (ba_tile.hip) and the wave-per-tile
 // streaming kernels (ba_stream.hip): relative pose of a camera pair, the per-edge reprojection /
 // Jacobian / robust-weight arithmetic (projective_ops.py:54-100, ba.py:228-266), and the wave-wide
 // reduce-scatter of the 27 per-pair products.

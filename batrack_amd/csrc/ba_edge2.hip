@@ -806,7 +806,7 @@ static int launch_t(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEve
 
 }  // namespace e2
 
-// pose+structure reduce of a plan the edge-major layout applies to (Route::kEdge: plan_route, ba_kernels.hip)
+// pose+structure reduce of a plan the edge-major layout applies to (Route::kEdge: plan_route, ba_step.cpp)
 int launch_edge2(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
     if ((unsigned long long)pd.e_all * (unsigned long long)a.tstride * 4ull >= (1ull << 32)) return BT_EUNSUPPORTED;   // 32-bit byte offsets into the targets
     if ((unsigned long long)pd.p_tot * (unsigned long long)a.mstride * 4ull >= (1ull << 32)) return BT_EUNSUPPORTED;

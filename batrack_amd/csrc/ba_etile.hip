@@ -14,7 +14,7 @@
 // float64 on the float32 inputs by default (StepArgs::prec), float32 with BT_FORCE prec=f32.
 // MODE kEtSO: structure-only steps, the whole step in this launch (the tracks' first lanes write the new disparities, the
 // workgroups behind the tile workgroups do the rest of the buffer and the poses).  MODE kEtUpd: a step's last kernel — the
-// depth back-substitution dZ = Q (w' - sum E^T dX) re-evaluated per edge (see k_update in ba_kernels.hip), the rest of the
+// depth back-substitution dZ = Q (w' - sum E^T dX) re-evaluated per edge (see k_update in ba_tile.hip), the rest of the
 // patch buffer, the pose retraction and the clearing of [S | y].
 // Reference: ba.py:228-337, projective_ops.py:54-100.
 #include <hip/hip_runtime.h>

@@ -1,8 +1,11 @@
-// ba_kernels.hpp — argument block and launchers shared by ba_kernels.hip / ba_api.cpp.
+// ba_kernels.hpp — argument block, kernel picks and launchers shared by the kernel files of the BA step (ba_tile.hip,
+// ba_pair.hip, ba_solve.hip, ba_xchg.hip and the later families), its sequence (ba_step.cpp) and ba_api.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <hip/hip_ext.h>
 
 #include "ba_plan.hpp"
+#include "dev_cache.hpp"
 
 namespace bt {
 
@@ -27,8 +30,39 @@ struct StepArgs {
     int dbg;                      // env BT_DEBUG_MODE, 0 in production: 16 / 32 launch the cycle-counting variants of the solver / k_tile
 };
 
+// A kernel instantiation of a route with its workgroup, its dynamic LDS and the LDS limit kept for it.  fn == nullptr: the
+// route launches none of that family (k_stream, k_edge2 and k_etile launch their own; so does the dense solver).
+struct Pick { const void *fn; LdsLimit *lim; int threads; size_t lds; };
+
+template <auto K> Pick pick_of(int threads, size_t lds) {
+    static LdsLimit lim;              // one per kernel instantiation
+    return Pick{reinterpret_cast<const void *>(K), &lim, threads, lds};
+}
+
+// ev: the kernel's (start, stop) event pair, or nullptr; args: exactly the kernel's parameter types
+template <typename... Args>
+void launch_pick(const Pick &p, unsigned grid, hipStream_t st, const hipEvent_t *ev, Args... args) {
+    void *argv[] = {&args...};
+    if (ev) (void)hipExtLaunchKernel(p.fn, dim3(grid), dim3(p.threads), argv, p.lds, st, ev[0], ev[1], 0);
+    else (void)hipLaunchKernel(p.fn, dim3(grid), dim3(p.threads), argv, p.lds, st);      // (errors: hipGetLastError, as for <<< >>>)
+}
+
+// The picks of a route, per family.  fused: the structure-only k_tile that also does the step's update; prof: BT_DEBUG_MODE 32 / 16
+Pick pick_tile(const PlanDev &pd, bool so, bool fused, bool prof);       // ba_tile.hip
+Pick pick_update(const PlanDev &pd, bool so);                            // ba_tile.hip
+Pick pick_solver(const PlanDev &pd, bool prof);                          // ba_solve.hip
+
+// LDS of k_tile with per-edge numbers of rsz bytes and of the LDS-resident solvers: what plan_route weighs against kLdsBudget
+size_t tile_lds_bytes_r(const PlanDev &pd, bool so, size_t rsz, size_t kTileWaves);
+size_t solve_lds_bytes(const PlanDev &pd, size_t elem);
+size_t solve_fused_lds_bytes(const PlanDev &pd, int nthreads);
+size_t solve_pipe_lds_bytes(const PlanDev &pd);
+// 12 waves: enough helper threads for one round of update rows on banded systems, and a 170-register budget per thread so
+// that a whole 6x6 operand block can be in flight from LDS
+constexpr int kSolveThreads = 768;
+
 // decides the plan's route (pd.route: which Jacobian kernel, per-edge precision and solver its steps launch) and raises the
-// dynamic-LDS limit of every k_tile / k_update / solver instantiation that route can launch
+// dynamic-LDS limit of every k_tile / k_update / solver instantiation that route can launch (ba_step.cpp)
 int configure_kernels(PlanDev &pd);
 // wave-per-tile streaming kernels (ba_stream.hip) for graphs of many tiles; mode 0 = pose+structure, 1 = structure-only,
 // 2 = depth back-substitution
@@ -45,9 +79,13 @@ int launch_etile(const PlanDev &pd, const StepArgs &a, int mode, int do_poses, i
 // launch (fuse_so_poses = 1: copy the poses too) and sets *fused; the caller then skips launch_solve_update
 int launch_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st, hipEvent_t *ev = nullptr, unsigned *ran = nullptr,
                   int fuse_so_poses = -1, bool *fused = nullptr);
-// dense [S | y] <-> its non-zero blocks in factor order (bt_ba_pack / bt_ba_unpack)
+// B and v from the per-pair sums, behind every Jacobian kernel of a pose+structure step (ba_pair.hip); ev0, ev1: event pair or nullptr
+int launch_pair_finalize(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// the route's block-sparse solver with the refinement passes of a float32 factor (ba_solve.hip); ev: event pair or nullptr
+int launch_solve(const PlanDev &pd, const StepArgs &a, hipStream_t st, const hipEvent_t *ev);
+// dense [S | y] <-> its non-zero blocks in factor order (bt_ba_pack / bt_ba_unpack; ba_xchg.hip)
 int launch_pack(const PlanDev &pd, const StepArgs &a, bool unpack, hipStream_t st);
-// one-shot peer-write exchange of the packed [S | y] (ba_kernels.hip: k_xchg_push / k_xchg_pull)
+// one-shot peer-write exchange of the packed [S | y] (ba_xchg.hip: k_xchg_push / k_xchg_pull)
 constexpr int kMaxRanks = 16;
 size_t xchg_bytes(const PlanDev &pd, int world);
 int launch_xchg_push(const PlanDev &pd, const StepArgs &a, void *const *bufs, int world, int rank, long long epoch, hipStream_t st);

@@ -1,5 +1,5 @@
 // ba_plan.hpp — structure of one BA edge list, shared by the host planner
-// (ba_plan.cpp), the kernels (ba_kernels.hip) and the C ABI (ba_api.cpp).
+// (ba_plan.cpp), the kernels (ba_tile.hip and the other ba_*.hip) and the C ABI (ba_api.cpp).
 #pragma once
 #include <array>
 #include <atomic>
@@ -72,7 +72,7 @@ BT_HD inline size_t etile_full_lds_bytes(int max_rows16, int max_tile_pairs, siz
     return (size_t)4 * 26 * smax * sizeof(double) + (rows * kLdsRowStride + 128 + mtp * kPairGeomFloats) * rsz + rows * sizeof(int) + 64;
 }
 
-// The kernels a plan's BA step launches: decided once per plan from its PlanDev scalars and BT_FORCE (ba_kernels.hip:
+// The kernels a plan's BA step launches: decided once per plan from its PlanDev scalars and BT_FORCE (ba_step.cpp:
 // plan_route, called by configure_kernels) and read by the launchers only.
 struct Route {
     enum : int { kTile = 0, kStream = 1, kEdge = 2, kEtile = 3 };          // kernel: the bt_plan_jacobian_kernel codes
@@ -139,7 +139,7 @@ struct PlanDev {
 };
 
 // Bytes of the status block at WsLayout::status: int 0 the solver status, 1 the exchange time-out, 4.. profiling counters, 200 / 201
-// the dense solver's flags, 210 the refinement's flag (ba_kernels.hip, ba_dense.hip).  Cleared by bt_ba_workspace_init.
+// the dense solver's flags, 210 the refinement's flag (ba_solve.hip, ba_dense.hip).  Cleared by bt_ba_workspace_init.
 constexpr size_t kStatusBytes = 1024;
 
 // Byte offsets of the regions inside the caller's workspace.

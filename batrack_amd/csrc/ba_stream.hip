@@ -1,6 +1,6 @@
 // ba_stream.hip — k_stream: tiles streamed through two-wave workgroups, for graphs of 2048 .. ~6000 tiles (gfx950, wave64).
 //
-// The tile kernel of ba_kernels.hip spreads one tile of 64 tracks over a workgroup of 8-16 waves: right for
+// The tile kernel of ba_tile.hip spreads one tile of 64 tracks over a workgroup of 8-16 waves: right for
 // graphs of a few hundred tiles, where a tile's latency is all there is.  On graphs of thousands of tiles the
 // chain  tile tables -> poses / patches -> edge list -> targets -> barriers -> Schur product -> atomics  of ONE
 // tile at a time keeps a CU's pipes idle.  Here a workgroup is TWO waves that own whole tiles and walk a contiguous
@@ -15,8 +15,8 @@
 //     accumulators kept in REGISTERS across consecutive tiles with the same cameras (tracks of one frame), atomics
 //     only when the cameras change; E Q w' by a wave reduce-scatter;
 //   * MODE kModeSO: structure-only steps (C, w, Q, w' only);  kModeUpd: the depth back-substitution of k_update
-//     (ba_kernels.hip) for the same tile walk.
-// Which graphs take this kernel: plan_route() in ba_kernels.hip (profiles/r02_kernel_choice.txt).
+//     (ba_tile.hip) for the same tile walk.
+// Which graphs take this kernel: plan_route() in ba_step.cpp (profiles/r02_kernel_choice.txt).
 // Reference: ba.py:228-337, projective_ops.py:54-100.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

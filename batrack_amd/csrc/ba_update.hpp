@@ -1,4 +1,4 @@
-// ba_update.hpp — the part of a step's last kernel that is not per tile, shared by k_update / k_tile (ba_kernels.hip) and
+// ba_update.hpp — the part of a step's last kernel that is not per tile, shared by k_update / k_tile (ba_tile.hip) and
 // k_etile (ba_etile.hip): the pose retraction Exp(dX) * G (groups.py:153-156) and the copy + clamp of the patch buffer
 // (ba.py:333).
 #pragma once

@@ -20,7 +20,7 @@
 #define BT_PROBE_ET_MARK(i)
 #define BT_PROBE_ET_END(full, lane, wave, extra)
 #endif
-// k_tile (ba_kernels.hip)
+// k_tile (ba_tile.hip)
 #ifndef BT_PROBE_TILE_DECL
 #define BT_PROBE_TILE_DECL()
 #define BT_PROBE_TILE_MARK(i)

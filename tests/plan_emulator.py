@@ -1,6 +1,6 @@
 """Test helper: executes a bt_plan on the CPU in float64 numpy, mirroring what the
-HIP kernels do with the plan arrays (ba_kernels.hip: k_prep, k_tile,
-k_pair_finalize, k_solve, k_update), with the per-edge Jacobians taken from the
+HIP kernels do with the plan arrays (ba_tile.hip: k_tile, k_update; ba_pair.hip:
+k_pair_finalize; ba_solve.hip: k_solve_*), with the per-edge Jacobians taken from the
 oracle.  It validates the plan layout, the Ji = -Jj Ad algebra and the
 block-sparse factorisation structure without a GPU.  Test infrastructure only.
 """

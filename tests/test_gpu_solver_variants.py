@@ -1,8 +1,7 @@
 """-m gpu: every reduced-system solver variant, and the persistent variant of the Jacobian kernel, give the
 reference's pose update.
 
-The library picks the variant from the system's size (ba_kernels.hip: solver_mode,
-use_pipe_solver, use_fused_solver): the barrier-free double LDS kernel (default where it applies), the
+The library picks the variant from the system's size (ba_step.cpp: plan_route; the kernels are in ba_solve.hip): the barrier-free double LDS kernel (default where it applies), the
 one-phase-per-level kernel with a barrier per level, the two-phase double LDS kernel (levels wider than two columns), the float LDS kernel and the global-memory kernel
 (systems too large for LDS).  The environment switches that force a variant are read once per
 process, so each case runs in its own interpreter."""
