@@ -179,9 +179,8 @@ __global__ __launch_bounds__(1024) void k_solve_global(PlanDev pd, StepArgs a) {
 //   phase 2   all threads: one block row each of L_ij = A_ij L_jj^-T by forward
 //             substitution; the extra row is y_j (forward substitution of the RHS)
 // The diagonal block keeps L_jj with 1/l_cc on its diagonal.  After the sweep all
-// threads bring the factor into back-substitution form (L_jj^-1 in the strict upper
-// triangle of the diagonal block, M_ij = (L_ij L_jj^-1)^T), and wave 0 runs the
-// sequential back substitution with DPP reductions.
+// threads bring the factor into back-substitution form (M_ij = (L_ij L_jj^-1)^T:
+// lds_backsub_prep), and wave 0 runs the sequential back substitution with DPP reductions.
 #define BT_LT(r, c) ((r) * ((r) + 1) / 2 + (c))
 
 // in place: lower triangle (packed) -> its Cholesky factor, diagonal entries hold 1 / l_cc.
@@ -205,6 +204,72 @@ __device__ __forceinline__ bool chol6_packed(T (&L)[21]) {
         }
     }
     return ok;
+}
+
+// The factor into back-substitution form, in one pass with one thread per factor block: M_ij = (L_ij L_jj^-1)^T in place
+// of L_ij, i.e. Mt[r][c] = sum_{k>=c} Linv_j[k][c] L_ij[r][k], and zt_j[c] = sum_{k>=c} Linv_j[k][c] z_j[k] from the thread
+// of the diagonal block.  Every thread reads its column's diagonal block (the lanes of a column the same addresses: a
+// broadcast), factors it where the sweep left the updated A_jj there (RAW_DIAG; otherwise it holds L_jj with 1/l_cc on the
+// diagonal) and inverts it in registers - redundantly, which costs the dependent chain once whether 63 threads or 476 walk
+// it - and transforms its own six rows.  L_jj^-1 is stored nowhere: the level loop reads off-diagonal M entries and zt only,
+// a retry loads the whole factor again.  Race-free by construction: an off-diagonal block is read and written by its own
+// thread alone, diagonal blocks and z are only read, zt_j is written by one thread; no barrier inside.
+// `row_idx`: row | col << 8 per block; the diagonal block of column j is block col_ptr[j].
+template <typename T, bool RAW_DIAG>
+__device__ __forceinline__ void lds_backsub_prep(T *Lw, const T *z, T *zt, const int *row_idx, const int *col_ptr, int nnzb, int tid, int nth) {
+    for (int b = tid; b < nnzb; b += nth) {
+        const int rc = row_idx[b], j = (rc >> 8) & 255;
+        const bool diag = (rc & 255) == j;
+        const T *dblk = Lw + (size_t)col_ptr[j] * 36;
+        T L[21], li[21];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            T row[6];
+            load_row6(dblk + 6 * r, row);
+#pragma unroll
+            for (int c = 0; c <= r; ++c) L[BT_LT(r, c)] = row[c];
+        }
+        if (RAW_DIAG) (void)chol6_packed<T>(L);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            li[BT_LT(c, c)] = L[BT_LT(c, c)];
+#pragma unroll
+            for (int r = c + 1; r < 6; ++r) {
+                T t = (T)0;
+#pragma unroll
+                for (int k = c; k < r; ++k) t += L[BT_LT(r, k)] * li[BT_LT(k, c)];
+                li[BT_LT(r, c)] = -t * L[BT_LT(r, r)];
+            }
+        }
+        auto to_m = [&](const T (&in)[6], T (&out)[6]) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                T t = li[BT_LT(c, c)] * in[c];
+#pragma unroll
+                for (int k = c + 1; k < 6; ++k) t += li[BT_LT(k, c)] * in[k];
+                out[c] = t;
+            }
+        };
+        if (diag) {
+            T in[6], out[6];
+            load_row6(z + 6 * j, in);
+            to_m(in, out);
+            store_row6(zt + 6 * j, out);
+        } else {
+            // rows two at a time: their loads in flight together, and no more than 12 values beside li (three at a time
+            // cost k_solve_lds<double> two registers)
+            T *p = Lw + (size_t)b * 36;
+            for (int h = 0; h < 3; ++h, p += 12) {
+                T in[2][6], out[2][6];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) load_row6(p + 6 * u, in[u]);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) to_m(in[u], out[u]);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) store_row6(p + 6 * u, out[u]);
+            }
+        }
+    }
 }
 
 size_t solve_lds_bytes(const PlanDev &pd, size_t elem) {
@@ -402,7 +467,7 @@ __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
                 }
                 const bool ok = chol6_packed<T>(L);
                 BT_PF(2);
-                if (lane == 0) {                 // entries above the diagonal are don't-care until Linv is put there
+                if (lane == 0) {                 // entries above the diagonal are don't-care: nothing reads them
                     if (!ok) flags[0] = 1;
 #pragma unroll
                     for (int r = 0; r < 6; ++r) {
@@ -517,57 +582,8 @@ __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
             long long *o = reinterpret_cast<long long *>(a.status + 4) + 40 + wave * 2;
             o[0] = ph1; o[1] = ph2;
         }
-        // ---- back-substitution form
-        // (a) L_jj^-1 into the strict upper triangle of the diagonal block (one thread per column)
-        for (int j = tid; j < n; j += nth) {
-            T *dblk = Lw + (size_t)col_ptr[j] * 36;
-            T L[21], li[21];
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c <= r; ++c) L[BT_LT(r, c)] = dblk[6 * r + c];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                li[BT_LT(c, c)] = L[BT_LT(c, c)];
-#pragma unroll
-                for (int r = c + 1; r < 6; ++r) {
-                    T t = (T)0;
-#pragma unroll
-                    for (int k = c; k < r; ++k) t += L[BT_LT(r, k)] * li[BT_LT(k, c)];
-                    li[BT_LT(r, c)] = -t * L[BT_LT(r, r)];
-                }
-            }
-#pragma unroll
-            for (int r = 1; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < r; ++c) dblk[6 * c + r] = li[BT_LT(r, c)];      // Linv[r][c] at [c][r]
-        }
-        __syncthreads();
-        // (b) block rows: Mt[r][c] = sum_{k>=c} Linv_j[k][c] L_ij[r][k];  zt_j[c] = sum_{k>=c} Linv_j[k][c] z_j[k]
-        for (int idx = tid; idx < nnzb * 6 + n; idx += nth) {
-            int j;
-            T *p, *q;
-            if (idx < nnzb * 6) {
-                const int b = idx / 6, r = idx - 6 * b;
-                j = (row_idx[b] >> 8) & 255;
-                if ((row_idx[b] & 255) == j) continue;
-                p = Lw + (size_t)b * 36 + 6 * r; q = p;
-            } else {
-                j = idx - nnzb * 6;
-                p = z + 6 * j; q = zt + 6 * j;
-            }
-            const T *dblk = Lw + (size_t)col_ptr[j] * 36;
-            T in[6], out[6];
-            load_row6(p, in);
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                T t = dblk[7 * c] * in[c];
-#pragma unroll
-                for (int k = c + 1; k < 6; ++k) t += dblk[6 * c + k] * in[k];
-                out[c] = t;
-            }
-            store_row6(q, out);
-        }
+        // ---- back-substitution form (M_ij in place of L_ij, zt from z), one thread per factor block
+        lds_backsub_prep<T, false>(Lw, z, zt, row_idx, col_ptr, nnzb, tid, nth);
         __syncthreads();
         BT_PF(6);
         // (c) x_j = zt_j - sum_{i>j} M_ij x_i, levels descending; one wave per column of the level,
@@ -658,8 +674,8 @@ __device__ __forceinline__ void sys_dma_issue(const PlanDev &pd, const StepArgs 
 // After the DMA: the blocks S holds transposed, one thread per (block of the list `trl`, row r < 5) — its up to five
 // (r, c > r) / (c, r) swaps with all reads in flight before the writes —, and the damping of the diagonal (ba.py:67), one
 // thread per diagonal element.  The upper triangles of the diagonal blocks stay as they came (S keeps its lower triangle
-// only): nothing reads them — the column wave's lanes carry them along as dead values, the back substitution overwrites
-// them with L^-1.
+// only): nothing reads them — the column wave's lanes carry them along as dead values, the back substitution's preparation
+// keeps L^-1 in registers.
 template <typename T>
 __device__ __forceinline__ void sys_dma_fixup(const PlanDev &pd, const StepArgs &a, T *Lw, const int *trl, int ntr, const int *col_ptr, double lm, bool zero_upper, int tid, int nth) {
     for (int it = tid; it < ntr * 5; it += nth) {
@@ -710,67 +726,14 @@ __device__ __forceinline__ void lds_load_system_dma(const PlanDev &pd, const Ste
 }
 
 // Back substitution of the LDS-resident factor (diagonal blocks hold L_jj with 1/l_cc on the
-// diagonal): brings it into M form, then x_j = zt_j - sum_{i>j} M_ij x_i by levels, descending.
+// diagonal, or the updated A_jj: RAW_DIAG): brings it into M form, then x_j = zt_j - sum_{i>j} M_ij x_i by levels, descending.
 template <typename T, bool RAW_DIAG = false>
 __device__ __forceinline__ void lds_back_substitute(const PlanDev &pd, T *Lw, T *z, T *zt, const int *row_idx,
                                                     const int *col_ptr, const int4 *lvl_meta, int mstride, int tid, int nth, long long *tprof = nullptr) {
     const int n = pd.n, nnzb = pd.nnzb, nlev = pd.nlev, wave = tid >> 6, lane = tid & 63;
-    for (int j = tid; j < n; j += nth) {
-        T *dblk = Lw + (size_t)col_ptr[j] * 36;
-        T L[21], li[21];
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c <= r; ++c) L[BT_LT(r, c)] = dblk[6 * r + c];
-        if (RAW_DIAG) {                   // the block still holds the (fully updated) A_jj: factor it here
-            (void)chol6_packed<T>(L);
-#pragma unroll
-            for (int c = 0; c < 6; ++c) dblk[7 * c] = L[BT_LT(c, c)];
-        }
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            li[BT_LT(c, c)] = L[BT_LT(c, c)];
-#pragma unroll
-            for (int r = c + 1; r < 6; ++r) {
-                T t = (T)0;
-#pragma unroll
-                for (int k = c; k < r; ++k) t += L[BT_LT(r, k)] * li[BT_LT(k, c)];
-                li[BT_LT(r, c)] = -t * L[BT_LT(r, r)];
-            }
-        }
-#pragma unroll
-        for (int r = 1; r < 6; ++r)
-#pragma unroll
-            for (int c = 0; c < r; ++c) dblk[6 * c + r] = li[BT_LT(r, c)];      // Linv[r][c] at [c][r]
-    }
+    lds_backsub_prep<T, RAW_DIAG>(Lw, z, zt, row_idx, col_ptr, nnzb, tid, nth);
     __syncthreads();
-    if (tprof) tprof[0] = clock64();
-    for (int idx = tid; idx < nnzb * 6 + n; idx += nth) {
-        int j;
-        T *p, *q;
-        if (idx < nnzb * 6) {
-            const int b = idx / 6, r = idx - 6 * b;
-            j = (row_idx[b] >> 8) & 255;
-            if ((row_idx[b] & 255) == j) continue;
-            p = Lw + (size_t)b * 36 + 6 * r; q = p;
-        } else {
-            j = idx - nnzb * 6;
-            p = z + 6 * j; q = zt + 6 * j;
-        }
-        const T *dblk = Lw + (size_t)col_ptr[j] * 36;
-        T in[6], out[6];
-        load_row6(p, in);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            T t = dblk[7 * c] * in[c];
-#pragma unroll
-            for (int k = c + 1; k < 6; ++k) t += dblk[6 * c + k] * in[k];
-            out[c] = t;
-        }
-        store_row6(q, out);
-    }
-    __syncthreads();
-    if (tprof) tprof[1] = clock64();
+    if (tprof) tprof[0] = tprof[1] = clock64();         // (one pass: L^-1 and the M form end together)
     // (c) x_j = zt_j - sum_{i>j} M_ij x_i, levels descending, ONE WAVE PER COLUMN SLOT and no barrier unless
     // the level reads an x_i another slot's wave wrote since the last barrier (lvl_meta[..].w, ba_plan.cpp
     // bs_sync): on a two-ended chain the two waves run down their chains independently.  The static
@@ -1107,7 +1070,7 @@ __global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) {
         if (wave == 0 || wave == 2) {
             long long *g = reinterpret_cast<long long *>(a.status + 4) + (wave ? 10 : 0);
             g[0] = tload; g[1] = tsweep; g[2] = clock64() - tall;
-            for (int i = 0; i < 6; ++i) g[3 + i] = sub[i];       // wave 0: ends of Linv / M form / back substitution; wave 2: row-wave stages
+            for (int i = 0; i < 6; ++i) g[3 + i] = sub[i];       // wave 0: end of the back-substitution preparation (twice: it was two phases) and of the back substitution; wave 2: row-wave stages
         }
     }
 #undef BT_SUB

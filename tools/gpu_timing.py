@@ -64,7 +64,7 @@ if int(os.environ.get("BT_DEBUG_MODE", "0")) & 16:
         print(f"  pipe solver: load={g[0]} sweep_end={g[1]} total={g[2]} | row wave 2: row_update={g[13]} wait_diag={g[14]} chol+trsm={g[15]} waits_at_level_start={g[16]} (for a column {g[17]}, for the helpers {g[18]}) | diagonal wave 0: waits for a column {g[7]}, for the helpers {g[8]}")
     elif forced_solver == "fused":
         g = pf.reshape(-1)
-        print(f"  fused solver: load={g[0]} sweep_end={g[1]} total={g[2]} | tail: Linv_end={g[3]} Mform_end={g[4]} backsub_end={g[5]} | row wave: row_update={g[16]} wait+load+chol={g[17]} trsm+store={g[18]}")
+        print(f"  fused solver: load={g[0]} sweep_end={g[1]} total={g[2]} | tail: prep_end={g[4]} backsub_end={g[5]} | row wave: row_update={g[16]} wait+load+chol={g[17]} trsm+store={g[18]}")
     for w in range(2):
         print(f"  solver wave{w} cycles: " + " ".join(f"{n}={v}" for n, v in zip(names, pf[w])) + f" total={pf[w].sum()}")
 print(f"mode={os.environ.get('BT_DEBUG_MODE','0')} {args.workload} E={plan.E} n={plan.n} tiles={plan.tiles} nnzb={plan.nnz_blocks}: " +
