@@ -8,12 +8,12 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip"]
-HEADERS = ["ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip"]
+HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
-           os.path.join("..", "..", "include", "batrack_observe.h")]
+           os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -67,6 +67,15 @@ class ObserveArgs(ctypes.Structure):                 # == bt_observe_args in inc
                 [(n, ctypes.c_void_p) for n in ("traj", "depth", "vis", "dyn", "queries", "dmaps", "ii", "jj", "kk", "patches_valid",
                                                 "patches_local", "local_monodisp", "local_vis", "local_static", "local_weights",
                                                 "targets_3d", "weights", "weights_pose", "query_disp")])
+
+
+class KeyframeStatus(ctypes.Structure):              # == bt_keyframe_status in include/batrack_keyframe.h
+    _fields_ = [("removed", ctypes.c_int64), ("E_out", ctypes.c_int64), ("mag_prev", ctypes.c_float), ("mag_next", ctypes.c_float),
+                ("cnt_prev", ctypes.c_int32), ("cnt_next", ctypes.c_int32)]
+
+
+class RowBuffer(ctypes.Structure):                   # == bt_row_buffer
+    _fields_ = [("ptr", ctypes.c_void_p), ("row_bytes", ctypes.c_int64)]
 
 
 def kernel_sources_sha16():
@@ -302,6 +311,18 @@ def lib():
     L.bt_observe_workspace_bytes.argtypes = []
     L.bt_observe_window.restype = i32
     L.bt_observe_window.argtypes = [ctypes.POINTER(ObserveArgs), vp, vp]
+    L.bt_keyframe_workspace_bytes.restype = ctypes.c_size_t
+    L.bt_keyframe_workspace_bytes.argtypes = [i64]
+    L.bt_edges_prune_tile.restype = i64
+    L.bt_edges_prune_tile.argtypes = []
+    L.bt_edges_prune_scan_span.restype = i64
+    L.bt_edges_prune_scan_span.argtypes = []
+    L.bt_keyframe_decide.restype = i32
+    L.bt_keyframe_decide.argtypes = [i64, vp, vp, vp, i64, vp, i64, vp, i64, i64, vp, ctypes.c_double, ctypes.c_double, vp, vp]
+    L.bt_edges_prune.restype = i32
+    L.bt_edges_prune.argtypes = [i64, i64, i64, i64] + [vp] * 6 + [i64] + [vp] * 8
+    L.bt_rows_shift.restype = i32
+    L.bt_rows_shift.argtypes = [ctypes.POINTER(RowBuffer), i32, i64, i64, vp, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

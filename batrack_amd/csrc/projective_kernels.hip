@@ -9,28 +9,9 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_projective.h"
+#include "projective_edge.hpp"
 
 namespace bt {
-
-struct Q4 { float x, y, z, w; };
-
-__device__ __forceinline__ Q4 q_unit(Q4 q) {                                   // so3.h:35-37
-    const float n = 1.0f / sqrtf(q.x*q.x + q.y*q.y + q.z*q.z + q.w*q.w);
-    return {q.x*n, q.y*n, q.z*n, q.w*n};
-}
-__device__ __forceinline__ Q4 q_mul(Q4 a, Q4 b) {
-    return { a.w*b.x + a.x*b.w + a.y*b.z - a.z*b.y,
-             a.w*b.y - a.x*b.z + a.y*b.w + a.z*b.x,
-             a.w*b.z + a.x*b.y - a.y*b.x + a.z*b.w,
-             a.w*b.w - a.x*b.x - a.y*b.y - a.z*b.z };
-}
-__device__ __forceinline__ void q_rot(Q4 q, const float *p, float *o) {       // so3.h:55-60
-    float ux = q.y*p[2] - q.z*p[1], uy = q.z*p[0] - q.x*p[2], uz = q.x*p[1] - q.y*p[0];
-    ux += ux; uy += uy; uz += uz;
-    o[0] = p[0] + q.w*ux + (q.y*uz - q.z*uy);
-    o[1] = p[1] + q.w*uy + (q.z*ux - q.x*uz);
-    o[2] = p[2] + q.w*uz + (q.x*uy - q.y*ux);
-}
 
 template <bool DEPTH, bool TONLY>
 __global__ __launch_bounds__(256) void k_reproject(const float *__restrict__ poses, int64_t n_poses,
@@ -50,29 +31,8 @@ __global__ __launch_bounds__(256) void k_reproject(const float *__restrict__ pos
             if (valid) valid[t] = 0.0f;
             continue;
         }
-        const float *pi = poses + 7 * i, *pj = poses + 7 * j, *Ki = intr + 4 * i, *Kj = intr + 4 * j;
         const float *pat = patches + (size_t)k * 3 * pe + pix;
-        // X0 = ((x - cx)/fx, (y - cy)/fy, 1, d)                                           projective_ops.py:19-29
-        const float d = pat[2 * pe];
-        const float X0[3] = { (pat[0] - Ki[2]) / Ki[0], (pat[pe] - Ki[3]) / Ki[1], 1.0f };
-        // Gij = G_j * G_i^-1                                                               se3.h:36-47
-        const Q4 qi = q_unit({pi[3], pi[4], pi[5], pi[6]}), qj = q_unit({pj[3], pj[4], pj[5], pj[6]});
-        const Q4 qiv = {-qi.x, -qi.y, -qi.z, qi.w};
-        const float ti[3] = {pi[0], pi[1], pi[2]};
-        float tiv[3], tr[3];
-        q_rot(qiv, ti, tiv);
-        tiv[0] = -tiv[0]; tiv[1] = -tiv[1]; tiv[2] = -tiv[2];
-        q_rot(qj, tiv, tr);
-        const float tij[3] = { pj[0] + tr[0], pj[1] + tr[1], pj[2] + tr[2] };
-        float R[3];
-        if (TONLY) { R[0] = X0[0]; R[1] = X0[1]; R[2] = X0[2]; }                           // projective_ops.py:61-64
-        else q_rot(q_unit(q_mul(qj, qiv)), X0, R);
-        // X1 = (R X0 + t d, d)                                                              se3.h:53-56
-        const float X = R[0] + tij[0] * d, Y = R[1] + tij[1] * d, Z = R[2] + tij[2] * d;
-        const float iz = 1.0f / fmaxf(Z, 1e-2f);                                            // projective_ops.py:43
-        out[0] = Kj[0] * (iz * X) + Kj[2];
-        out[1] = Kj[1] * (iz * Y) + Kj[3];
-        if (DEPTH) out[2] = iz * d;
+        const float Z = reproject_pixel<DEPTH, TONLY>(poses + 7 * i, poses + 7 * j, intr + 4 * i, intr + 4 * j, pat, pe, out);   // projective_edge.hpp
         if (valid) valid[t] = Z > 0.2f ? 1.0f : 0.0f;                                       // projective_ops.py:103
     }
 }

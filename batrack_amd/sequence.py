@@ -9,9 +9,14 @@ oracle (tests / tools only), and the two trajectories are compared by their ATE.
 doubles as the check that batrack_amd.backend.ba is a drop-in at the call site.  State tensors
 live on `device`; nothing here is specific to the GPU except the `ba` passed in.
 
-Out of scope (not restated): image preprocessing, patch selection, the tracker network, the
-motion-magnitude keyframe removal (`keyframe`, batrack.py:1026-1071 — `keyframe_simple` is used,
-as in the reference when `use_keyframe` is off), visualisers.
+The motion-magnitude keyframe removal (`keyframe`, batrack.py:1026-1073) runs with `SlamConfig.use_keyframe`; it is
+off by default, as in the reference's sintel configuration, and `keyframe_simple` is used then.  With a `keyframer`
+(`batrack_amd.frontend.keyframe.prune_keyframe`) both are one call of the device pipeline; without one they are torch
+statements on the object's own tensors, which is what the CPU replay uses.  After a removal a buffer slot no longer
+holds the frame of the same number: `tstamps` (the host mirror of `tstamps_`) maps a slot to its source frame, and the
+observation model is asked through it.
+
+Out of scope (not restated): image preprocessing, patch selection, the tracker network, visualisers.
 """
 import dataclasses
 import time
@@ -42,6 +47,9 @@ class SlamConfig:
     num_init: int = 12
     init_updates: int = 12            # batrack.py:990-991
     UPDATE_POINT_CLOUD: bool = False  # not a key of the reference's file: it always runs the step (see WindowedBA)
+    use_keyframe: bool = False        # batrack.py:1004: motion-magnitude keyframe removal (davis_demo.yaml sets it)
+    KEYFRAME_INDEX: int = 4
+    KEYFRAME_THRESH: float = 10.0
 
 
 class SyntheticObservations:
@@ -75,10 +83,18 @@ class SyntheticObservations:
         sl = slice(f * self.M, (f + 1) * self.M)
         return np.concatenate([self.xy[sl], self.disp_init[sl, None]], 1), self.disp_prior[sl]
 
-    def predict(self, kk, jj):
+    def _source(self, kk, jj, slot_frame):
+        """Buffer slots -> source frames: track kk -> slot_frame[kk // M]*M + kk % M, frame jj -> slot_frame[jj]."""
+        sf = np.asarray(slot_frame, dtype=np.int64)
+        return sf[kk // self.M] * self.M + kk % self.M, sf[jj]
+
+    def predict(self, kk, jj, slot_frame=None):
         """Targets and labels for edges (track kk -> frame jj): what `get_window_trajs` +
         `predict_target` (batrack.py:760-795) hand to the BA.  Returns targets3 [E,3],
-        visible [E], static [E]."""
+        visible [E], static [E].  slot_frame: the source frame of every buffer slot when kk, jj are slot numbers of a
+        buffer that frames were removed from (None: slot == frame)."""
+        if slot_frame is not None:
+            kk, jj = self._source(kk, jj, slot_frame)
         ii = kk // self.M
         gt = np.concatenate([self.xy, self.disp_gt[:, None]], 1)
         intr = np.tile(self.intrinsics, (self.n_frames, 1))
@@ -91,20 +107,22 @@ class SyntheticObservations:
         vis = (Z > 0.2) & (self._rng.random(E) >= self.drop_frac)
         return t3, vis, ~self.dynamic[kk]
 
-    def predict_window(self, kk, jj, S):
+    def predict_window(self, kk, jj, S, slot_frame=None):
         """The draws of `predict` for the window's edges (track-major: all frames of a track together), shaped as the
         tracker network returns them for a window padded to S frames — traj [1,S,Nq,2] in full-image pixels, depth
         [1,S,Nq,1] (the reciprocal of predict's disparity), vis [1,S,Nq] (1 / 0), dyn [1,S,Nq] (1 for a moving track) —
         plus queries [1,Nq,3] = (frame within the window, x, y) of the tracks, as `get_queries` (batrack.py:459-480).  The
-        padded frames repeat the last one (batrack.py:692-694).  numpy, float32."""
-        t3, vis, static = self.predict(kk, jj)
+        padded frames repeat the last one (batrack.py:692-694).  numpy, float32.  slot_frame as in `predict`; the window's
+        geometry (its first frame, its length, the query's frame within it) stays in slot numbers."""
+        t3, vis, static = self.predict(kk, jj, slot_frame)
         lo = int(jj.min())
         Sp = int(jj.max()) - lo + 1
         Nq = kk.shape[0] // Sp
         pad = lambda a: np.concatenate([a] + [a[-1:]] * (S - Sp)).astype(np.float32)[None]
         fr = lambda a: np.swapaxes(a.reshape(Nq, Sp, *a.shape[1:]), 0, 1)
         q = kk.reshape(Nq, Sp)[:, 0]
-        queries = np.concatenate([(q // self.M - lo)[:, None], self.xy[q]], 1).astype(np.float32)[None]
+        qs = q if slot_frame is None else self._source(q, q // self.M, slot_frame)[0]
+        queries = np.concatenate([(q // self.M - lo)[:, None], self.xy[qs]], 1).astype(np.float32)[None]
         return (pad(fr(t3[:, :2])), pad(fr(1.0 / t3[:, 2:])), pad(fr(vis.astype(np.float64))),
                 pad(fr(1.0 - static.astype(np.float64))), queries)
 
@@ -136,8 +154,11 @@ class WindowedBA:
     without it: with it off nothing is allocated or computed, and the depth prior of a track stays the tracker's
     disparity for the track's whole life, where the reference hands a live track its current estimate."""
 
-    def __init__(self, obs, ba, cfg=None, device="cpu", sync=None, prefetch=None, se3=SE3, observer=None):
-        """observer: optional function with the signature of `batrack_amd.frontend.observe.window_observations`.  With it,
+    def __init__(self, obs, ba, cfg=None, device="cpu", sync=None, prefetch=None, se3=SE3, observer=None, keyframer=None):
+        """keyframer: optional function with the signature of `batrack_amd.frontend.keyframe.prune_keyframe`.  With it
+        `keyframe()` and `keyframe_simple()` are one call each (the decision, the edge pruning and the buffer shift run where
+        the keyframer runs); without it they are torch statements on this object's tensors.
+        observer: optional function with the signature of `batrack_amd.frontend.observe.window_observations`.  With it,
         `predict_target` hands the observation model's window tensors (`obs.predict_window`) and the window's depth maps
         to it and appends what it returns: the step between the tracker and the BA then runs where the observer runs, and
         the object also owns `patches_monodisp_` [N, M, 1] and `patches_local_monodisp_` (batrack.py:80,85).  Without it
@@ -179,7 +200,11 @@ class WindowedBA:
             self.patches_monodisp_ = torch.zeros(self.N, self.M, 1, **f32)                     # batrack.py:85
             self.patches_local_monodisp_ = torch.zeros(self.N, self.M, self.S_local, 1, **f32)  # batrack.py:80
             self._dmaps = {}
+        self.keyframer = keyframer
+        self.delta = {}                       # removed time stamp -> (the time stamp before it, their relative pose)   batrack.py:1043
+        self.keyframe_log = []                # (time stamp of the candidate, m / 2, removed) of every keyframe() that decided
         self.tstamps_ = torch.zeros(self.N, **i64)
+        self.tstamps = [0] * self.N           # host mirror of tstamps_: the source frame of every slot
         self.tlist, self.counter = [], 0
         self.ii, self.jj, self.kk = (torch.zeros(0, **i64) for _ in range(3))
         self.targets_3d = torch.zeros(1, 0, 3, **f32)
@@ -243,7 +268,7 @@ class WindowedBA:
         if self.observer is not None:
             return self._observe_target()
         kk, jj = self._kk_new.cpu().numpy(), self._jj_new.cpu().numpy()
-        t3, vis, static = self.obs.predict(kk, jj)
+        t3, vis, static = self.obs.predict(kk, jj, self._slot_frame())
         S = min(self.n, self.cfg.S_slam)
         w = np.ones((kk.shape[0], 2))
         w[~vis] = 0.0
@@ -270,13 +295,15 @@ class WindowedBA:
         Sp = min(self.n, c.S_slam)
         lo = self.n - Sp
         up = lambda a: torch.as_tensor(a, dtype=torch.float32, device=self.device)
-        window = [up(a) for a in self.obs.predict_window(self._kk_new.cpu().numpy(), self._jj_new.cpu().numpy(), c.S_slam)]
-        for f in range(lo, self.n):
+        window = [up(a) for a in self.obs.predict_window(self._kk_new.cpu().numpy(), self._jj_new.cpu().numpy(), c.S_slam,
+                                                         self._slot_frame())]
+        src = self.tstamps[lo:self.n]                                                          # the window's source frames
+        for f in src:
             if f not in self._dmaps:
                 self._dmaps[f] = up(self.obs.depth_map(f)[..., 0])
-        for f in [f for f in self._dmaps if f < lo]:
+        for f in [f for f in self._dmaps if f not in src]:
             del self._dmaps[f]
-        dmaps = torch.stack([self._dmaps[f] for f in range(lo, self.n)])
+        dmaps = torch.stack([self._dmaps[f] for f in src])
         t3, w, wp, qd = self.observer(*window, dmaps, self._kk_new // self.M, self._jj_new, self._kk_new,
                                       patches_valid=self.patches_valid_, patches_local=self.patches_local_,
                                       local_monodisp=self.patches_local_monodisp_, local_vis=self.patches_local_vis_,
@@ -358,23 +385,88 @@ class WindowedBA:
         t0 = max(n_at_update - c.OPTIMIZATION_WINDOW, 1)        # update(): is_initialized is set by then
         self.prefetch(self.ii, self.jj, self.kk, self.N, self.N * self.M, t0, self.device)
 
+    def _slot_frame(self):
+        """Slot -> source frame for the observation model; None while no frame has been removed (slot == frame)."""
+        return self.tstamps[:self.n] if self.delta else None
+
+    def _frame_buffers(self):
+        """What the reference shifts when a frame leaves the buffer (batrack.py:1052-1063; it has `colors_` too)."""
+        b = [self.tstamps_, self.poses_, self.patches_, self.intrinsics_, self.patches_local_, self.patches_local_vis_,
+             self.patches_local_static_, self.patches_local_weights_, self.patches_valid_]
+        return b + ([self.trajs_3d_world_] if hasattr(self, "trajs_3d_world_") else [])
+
+    def _removed(self, k, dP):
+        """Host bookkeeping of the removal of slot k (batrack.py:1039-1043, 1065-1066); dP: SE3 of one pose."""
+        ts = self.tstamps
+        self.delta[ts[k]] = (ts[k - 1], dP)
+        ts[k:self.n - 1] = ts[k + 1:self.n]
+        self.n -= 1
+        self.m -= self.M
+
+    def _keyframer_call(self, candidate):
+        from .frontend.keyframe import KeyframeConfig
+        c = self.cfg
+        r = self.keyframer(self.poses_, self.patches, self.intrinsics_, self.ii, self.jj, self.kk, self.targets_3d, self.weights,
+                           self.weights_pose, n=self.n, M=self.M, kf_stride=c.kf_stride, frame_buffers=self._frame_buffers(),
+                           cfg=KeyframeConfig(KEYFRAME_INDEX=c.KEYFRAME_INDEX, KEYFRAME_THRESH=c.KEYFRAME_THRESH,
+                                              REMOVAL_WINDOW=c.REMOVAL_WINDOW), candidate=candidate)
+        self.ii, self.jj, self.kk = r.ii, r.jj, r.kk
+        self.targets_3d, self.weights, self.weights_pose = r.targets_3d, r.weights, r.weights_pose
+        return r
+
+    # ---- batrack.py:1011-1018
+    def motionmag(self, i, j):
+        k = (self.ii == i) & (self.jj == j)
+        flow = pops.flow_mag(self.SE3(self.poses), self.patches, self.intrinsics, self.ii[k], self.jj[k], self.kk[k], beta=0.5)
+        return flow.mean().item()
+
     # ---- batrack.py:1020-1024
     def keyframe_simple(self):
+        if self.keyframer is not None:
+            self._keyframer_call(candidate=False)
+            return
         self.remove_factors(self.kk // self.M < self.n - self.cfg.REMOVAL_WINDOW)
+
+    # ---- batrack.py:1026-1073
+    def keyframe(self):
+        c = self.cfg
+        k = self.n - c.KEYFRAME_INDEX
+        if k % c.kf_stride != 0:
+            return
+        if self.keyframer is not None:
+            r = self._keyframer_call(candidate=True)
+            self.keyframe_log.append((self.tstamps[k], (r.mag_prev + r.mag_next) / 2, r.removed))
+            if r.removed:
+                self._removed(k, self.SE3(r.dP[None]))
+            return
+        m = self.motionmag(k - 1, k) + self.motionmag(k + 1, k)
+        removed = m / 2 < c.KEYFRAME_THRESH
+        self.keyframe_log.append((self.tstamps[k], m / 2, removed))
+        if removed:
+            dP = self.SE3(self.poses_[k][None]) * self.SE3(self.poses_[k - 1][None]).inv()
+            self.remove_factors((self.ii == k) | (self.jj == k))
+            self.kk[self.ii > k] -= self.M
+            self.ii[self.ii > k] -= 1
+            self.jj[self.jj > k] -= 1
+            for buf in self._frame_buffers():
+                buf[k:self.n - 1] = buf[k + 1:self.n].clone()
+            self._removed(k, dP)
+        self.remove_factors(self.kk // self.M < self.n - c.REMOVAL_WINDOW)
 
     # ---- batrack.py:937-1008
     def __call__(self):
         if self.n + 1 >= self.N:
             raise RuntimeError("The buffer size is too small")
         c = self.cfg
-        pat, prior = self.obs.frame_patches(self.n)
+        pat, prior = self.obs.frame_patches(self.counter)       # the source frame: slot n holds it (counter == n until a frame is removed)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.patches_[self.n] = torch.as_tensor(pat, **f32).view(self.M, 3, 1, 1)
         if self.n % c.kf_stride == 0 and not self.is_initialized:
             self.patches_valid_[self.n] = 1                                       # batrack.py:968-969
         self.init_motion()
-        self.tlist.append(float(self.n))
+        self.tlist.append(float(self.counter))
         self.tstamps_[self.n] = self.counter
+        self.tstamps[self.n] = self.counter
         self.counter += 1
         self.n += 1
         self.m += self.M
@@ -388,7 +480,10 @@ class WindowedBA:
                 self.update()
         elif self.is_initialized:
             self.update()
-            self.keyframe_simple()
+            if c.use_keyframe and (self.n - 1) % c.kf_stride == 0:      # batrack.py:1004-1007
+                self.keyframe()
+            else:
+                self.keyframe_simple()
             if self.n % c.kf_stride != 0:                       # the next frame appends nothing: its edge list is final now
                 self._prefetch(self.n + 1)
 
@@ -399,10 +494,11 @@ class WindowedBA:
         `trajs_2d_disp` [T,M,S_local,3] float32 (a track's (u, v, disparity) targets in the S_local frames around its own),
         `trajs_valid` [T,M] bool (some weight > 0 in the window), `trajs_static`, `trajs_vis` [T,M,S_local] float32,
         `grid_query_frames` (the frames with a valid patch), `dmaps` / `rgbs` / `dmaps_gt` as float64 arrays of what the caller
-        hands in (None stays None).  T = frames seen; no frame is ever dropped from the buffer by `keyframe_simple`, so the
-        reference's per-time-stamp pose lookup (`get_pose`) is the buffer itself.  Pickled to `save_path` if given."""
+        hands in (None stays None).  T = frames seen.  The poses are the reference's per-time-stamp lookup (`get_pose`): the
+        buffer itself while no frame was removed, a removed frame's through `delta`; every other key is the first T rows of
+        its buffer, as the reference cuts it (batrack.py:1091-1103).  Pickled to `save_path` if given."""
         T = self.counter
-        G = self.SE3(self.poses_[:T])
+        G = self._poses_by_tstamp()
         pts_valid = self.patches_valid_[:T].detach().cpu().numpy()
         trajs_valid = self.patches_local_weights_[:T, ..., 0]
         results = {
@@ -423,6 +519,25 @@ class WindowedBA:
             with open(save_path, "wb+") as f:
                 pickle.dump(results, f)
         return results
+
+    # ---- batrack.py:223-228
+    def get_pose(self, t):
+        if t in self.traj:
+            return self.SE3(self.traj[t])
+        t0, dP = self.delta[t]
+        return dP * self.get_pose(t0)
+
+    def _poses_by_tstamp(self):
+        """SE3 [counter, 7]: the pose of every time stamp seen (batrack.py:900-905, 1081-1086)."""
+        self.traj = {self.tstamps[i]: self.poses_[i][None] for i in range(self.n)}
+        return self.SE3(torch.cat([self.get_pose(t).data for t in range(self.counter)], 0))
+
+    # ---- batrack.py:898-915
+    def terminate(self):
+        """(poses [counter, 7] camera -> world as tx ty tz qw qx qy qz, float32; tstamps [counter] float64): one pose per time
+        stamp seen, the removed frames' interpolated through `delta`."""
+        poses = self._poses_by_tstamp().inv().data.detach().cpu().numpy()
+        return poses[:, [0, 1, 2, 6, 3, 4, 5]], np.array(self.tlist, dtype=float)
 
     def run(self, n_frames=None):
         for _ in range(self.obs.n_frames if n_frames is None else n_frames):
