@@ -8,24 +8,28 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip"]
-HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip"]
+HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
-           os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h")]
+           os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h"),
+           os.path.join("..", "..", "include", "batrack_patches.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
 BT_OK, BT_EINVAL, BT_ENOMEM, BT_EHIP, BT_EUNSUPPORTED = 0, -1, -2, -3, -4
 BT_DEPTH_F32, BT_DEPTH_F64 = 0, 1                    # include/batrack_depth.h
+BT_IMAGE_U8, BT_IMAGE_F32 = 0, 1                     # include/batrack_patches.h
+BT_PATCH_ROWS = {"reference": 0, "image": 1}
 ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "HIP runtime error",
           BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
                            "than one source frame: ii must equal ix[kk]; global alignment: more than 4096 tracks per frame "
                            "with the inter-frame term, or a scale grid of more than 12 * 1024 cells in the backward, or more than 8192 cells wide in "
                            "bt_ga_scaled_dmaps; depth metrics: more than 2^31 - 1 elements; depth alignment: 2^30 or more pixels per map; mono-depth alignment: more than 2^31 - 1 pixels in a scene; world tracks: a window of more than 2^20 frames; "
                            "correlation lookup: more than 512 channels, a radius above 7, more than 8 levels, a map side above 32768, or more than 2^31 - 1 (frame, query, level) triples; "
-                           "window observations: a window of more than 64 frames, 2^24 or more scores, or window buffers of 2^31 or more slots)"}
+                           "window observations: a window of more than 64 frames, 2^24 or more scores, or window buffers of 2^31 or more slots; "
+                           "patch generation: more than 1024 candidates per cell (8 * patches per cell), or an image side above 32768)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -72,6 +76,14 @@ class ObserveArgs(ctypes.Structure):                 # == bt_observe_args in inc
 class KeyframeStatus(ctypes.Structure):              # == bt_keyframe_status in include/batrack_keyframe.h
     _fields_ = [("removed", ctypes.c_int64), ("E_out", ctypes.c_int64), ("mag_prev", ctypes.c_float), ("mag_next", ctypes.c_float),
                 ("cnt_prev", ctypes.c_int32), ("cnt_next", ctypes.c_int32)]
+
+
+class PatchArgs(ctypes.Structure):                   # == bt_patch_args in include/batrack_patches.h
+    _fields_ = [("g", ctypes.c_void_p), ("Hp", ctypes.c_int64), ("Wp", ctypes.c_int64), ("image", ctypes.c_void_p),
+                ("dtype", ctypes.c_int32), ("rows_mode", ctypes.c_int32)] + \
+               [(n, ctypes.c_int64) for n in ("H", "W", "stride_c", "stride_y", "stride_x")] + \
+               [(n, ctypes.c_void_p) for n in ("depth", "ux", "uy")] + [("G", ctypes.c_int64), ("gm", ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in ("patches", "clr", "colors", "coords", "sel")]
 
 
 class RowBuffer(ctypes.Structure):                   # == bt_row_buffer
@@ -323,6 +335,10 @@ def lib():
     L.bt_edges_prune.argtypes = [i64, i64, i64, i64] + [vp] * 6 + [i64] + [vp] * 8
     L.bt_rows_shift.restype = i32
     L.bt_rows_shift.argtypes = [ctypes.POINTER(RowBuffer), i32, i64, i64, vp, vp]
+    L.bt_image_gradient.restype = i32
+    L.bt_image_gradient.argtypes = [vp, i32, i64, i64, i64, i64, i64, vp, vp]
+    L.bt_patch_generate.restype = i32
+    L.bt_patch_generate.argtypes = [ctypes.POINTER(PatchArgs), vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

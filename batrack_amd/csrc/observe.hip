@@ -24,6 +24,7 @@
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_observe.h"
 #include "radix_select.hpp"
+#include "sample_taps.hpp"
 
 #pragma clang fp contract(off)
 
@@ -36,15 +37,6 @@ constexpr int OB_SEL_THREADS = 1024;            // the threshold's single workgr
 
 struct OF3 { float x, y, z; };                  // 12-byte record, 4-byte aligned
 struct OF2 { float a, b; };
-
-// torch's clamp(min=1e-2): a NaN stays NaN (fmaxf would return 1e-2)
-__device__ __forceinline__ float ob_clamp_min(float d) { return d < 1e-2f ? 1e-2f : d; }
-
-// floor(x).int() with the out-of-range cases spelt out (NaN -> 0): the indices are clamped to the map afterwards
-__device__ __forceinline__ int ob_floor_int(float x) {
-    const float f = floorf(x);
-    return f != f ? 0 : (f <= -2147483648.0f ? (-2147483647 - 1) : (f >= 2147483648.0f ? 2147483647 : (int)f));
-}
 
 struct ObQuery {                              // the scalars of the query pass
     const float *queries, *dmaps;
@@ -59,18 +51,9 @@ __global__ __launch_bounds__(256) void k_observe_query(ObQuery a) {
     float d = NAN;
     if (tf >= 0.0f && tf < (float)a.Sp) {
         const int t = (int)tf;
-        const float *im = a.dmaps + (size_t)t * a.H * a.W;
-        const int x0 = ob_floor_int(x), y0 = ob_floor_int(y);
-        const long long x1 = (long long)x0 + 1, y1 = (long long)y0 + 1;
-        const float x0f = (float)x0, x1f = (float)x1, y0f = (float)y0, y1f = (float)y1;
-        const long long mx = a.W - 1, my = a.H - 1;
-        const long long cx0 = x0 < 0 ? 0 : (x0 > mx ? mx : x0), cx1 = x1 < 0 ? 0 : (x1 > mx ? mx : x1);
-        const long long cy0 = y0 < 0 ? 0 : (y0 > my ? my : y0), cy1 = y1 < 0 ? 0 : (y1 > my ? my : y1);
-        const float i00 = im[cy0 * a.W + cx0], i01 = im[cy0 * a.W + cx1], i10 = im[cy1 * a.W + cx0], i11 = im[cy1 * a.W + cx1];
-        const float w00 = (x1f - x) * (y1f - y), w01 = (x - x0f) * (y1f - y), w10 = (x1f - x) * (y - y0f), w11 = (x - x0f) * (y - y0f);
-        d = ((w00 * i00 + w01 * i01) + w10 * i10) + w11 * i11;                 // model_utils.py:152-154, left to right
+        d = bilinear_clamped(a.dmaps + (size_t)t * a.H * a.W, a.H, a.W, x, y);
     }
-    a.query_disp[q] = 1.0f / ob_clamp_min(d);
+    a.query_disp[q] = 1.0f / clamp_min_1e2(d);
 }
 
 // static = 1 - dyn over n values; a = the k0-th, b = the k1-th smallest (k1 = k0 or k0 + 1); *th = min(lerp(a, b, w), st)
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_observe_window(ObWindow a) {
                     x *= a.rx;                                                   // :584-585
                     y *= a.ry;
                 }
-                const float z = 1.0f / ob_clamp_min(a.depth[idx]);               // :765
+                const float z = 1.0f / clamp_min_1e2(a.depth[idx]);               // :765
                 const float stat = 1.0f - a.dyn[idx];                            // :718
                 const bool vl = a.has_vt ? v > a.vt : true;                      // :707-710
                 const bool in = x >= a.lo_x && x < a.hi_x && y >= a.lo_y && y < a.hi_y;   // :713

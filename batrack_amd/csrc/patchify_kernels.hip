@@ -5,6 +5,7 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_patchify.h"
+#include "sample_taps.hpp"
 
 namespace bt {
 
@@ -36,10 +37,7 @@ __global__ void k_patchify(const float *net, const float *coords, float *out,
             const float dx = x - fx, dy = y - fy;
             const float p00 = tap(plane, i, j, H, W), p01 = tap(plane, i, j + 1, H, W);
             const float p10 = tap(plane, i + 1, j, H, W), p11 = tap(plane, i + 1, j + 1, H, W);
-            const float w00 = (1.0f - dy) * (1.0f - dx), w01 = (1.0f - dy) * dx;
-            const float w10 = dy * (1.0f - dx), w11 = dy * dx;
-            const float t00 = w00 * p00, t01 = w01 * p01, t10 = w10 * p10, t11 = w11 * p11;     // (contract(off): products rounded, then summed)
-            out[n] = ((t00 + t01) + t10) + t11;
+            out[n] = blend4(dx, dy, p00, p01, p10, p11);
         }
     }
 }

@@ -1,5 +1,9 @@
-"""What batrack_amd provides of the reference's tracker front end (main/frontend): the correlation lookup.
+"""What batrack_amd provides of the reference's tracker front end (main/frontend) and of the steps of a frame around it.
 
   batrack_amd.frontend.corr.CorrBlock     the tracker's CorrBlock, fused: no correlation volume
   batrack_amd.frontend.corr.install       make the reference's unmodified md_tracker use it
+  batrack_amd.frontend.observe.window_observations   tracker output -> the BA's targets and weights
+  batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning
+  batrack_amd.frontend.patches.generate_patches      patch selection, depth initialisation and colours of a new frame
+  batrack_amd.frontend.patches.image_gradient        the pooled gradient-magnitude map it ranks by
 """

@@ -16,7 +16,9 @@ statements on the object's own tensors, which is what the CPU replay uses.  Afte
 holds the frame of the same number: `tstamps` (the host mirror of `tstamps_`) maps a slot to its source frame, and the
 observation model is asked through it.
 
-Out of scope (not restated): image preprocessing, patch selection, the tracker network, visualisers.
+Out of scope (not restated): image preprocessing, the tracker network, visualisers.  Patch selection and the depth
+initialisation of a new frame have a device path of their own (batrack_amd.frontend.patches.generate_patches); the replay's
+synthetic tracks are not image-derived, so it does not call it.
 """
 import dataclasses
 import time
