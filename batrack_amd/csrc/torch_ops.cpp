@@ -38,6 +38,18 @@
 //       ii / jj / kk [Nq*Sp] int64, patches_valid [N, M], patches_local [N*M, S_local, 3], the other window buffers [N*M, S_local],
 //       workspace: bt_observe_workspace_bytes() bytes -> targets_3d [E, 3], weights [E, 2], weights_pose [E, 2], query_disp [Nq]
 //       (query_disp is empty without dmaps)
+//   batrack_hip::track_pos_embed(Tensor tabx, Tensor taby, Tensor coords) -> Tensor
+//       bt_track_pos_embed (include/batrack_track.h): tabx [W, E/2], taby [H, E/2], coords [N, >= 2] with unit last stride
+//       (a row view of the tracker's [S, N, 3] state is read in place) -> [N, E]
+//   batrack_hip::track_tokens(Tensor coords, Tensor? coords_sub, Tensor fcorrs, Tensor ffeats, Tensor track_mask, Tensor vis,
+//                             Tensor pos, Tensor time, Tensor w_flow, Tensor b_flow, bool fix_track_mask) -> Tensor
+//       bt_track_tokens: coords [S, N, 3], fcorrs [S, N, LRR], ffeats [S, N, C], track_mask / vis [S, N], pos [N, E], time [S, E],
+//       w_flow [F, 195], b_flow [F], all contiguous -> x [N, S, E], E = F + LRR + C + 2
+//   batrack_hip::track_apply(Tensor delta, Tensor gamma, Tensor beta, Tensor w_u, Tensor b_u, Tensor(a!) state, Tensor(b!) ffeats,
+//                            Tensor? total, Tensor? dyn_mask, float stride, float dz, float d_range, float d_near,
+//                            bool use_log_depth) -> Tensor
+//       bt_track_apply: delta [N, S, 3 + C]; state [S, N, 3] and ffeats [S, N, C] updated in place; total [S, N, 3] and
+//       dyn_mask [N] select the static pass -> out [S, N, 3]
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -50,6 +62,7 @@
 #include "../../include/batrack_corr.h"
 #include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
+#include "../../include/batrack_track.h"
 
 namespace {
 
@@ -305,6 +318,87 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> observe_window(
     return {targets, weights, weights_pose, query_disp};
 }
 
+at::Tensor track_pos_embed(const at::Tensor &tabx, const at::Tensor &taby, const at::Tensor &coords) {
+    const char *op = "batrack_hip::track_pos_embed: ";
+    const float *tx = f32(tabx, "tabx"), *ty = f32(taby, "taby"), *cd = f32(coords, "coords");
+    TORCH_CHECK(tabx.dim() == 2 && taby.dim() == 2 && tabx.is_contiguous() && taby.is_contiguous() && tabx.size(1) == taby.size(1),
+                op, "tabx [W, E/2] and taby [H, E/2] must be contiguous");
+    TORCH_CHECK(coords.dim() == 2 && coords.size(1) >= 2 && (coords.size(0) <= 1 || coords.stride(0) >= 2) && coords.stride(1) == 1,
+                op, "coords must be [N, >= 2] with unit last stride");
+    TORCH_CHECK(tabx.device() == coords.device() && taby.device() == coords.device(), op, "tensors must be on one device");
+    const int64_t N = coords.size(0), E = 2 * tabx.size(1);
+    at::Tensor out = at::empty({N, E}, tabx.options());
+    if (N == 0) return out;
+    const int rc = bt_track_pos_embed(tx, ty, taby.size(0), tabx.size(0), E, cd, N > 1 ? coords.stride(0) : 2, N, out.data_ptr<float>(),
+                                      c10::hip::getCurrentHIPStream(coords.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_track_pos_embed failed with status ", rc);
+    return out;
+}
+
+at::Tensor track_tokens(const at::Tensor &coords, const c10::optional<at::Tensor> &coords_sub, const at::Tensor &fcorrs,
+                        const at::Tensor &ffeats, const at::Tensor &track_mask, const at::Tensor &vis, const at::Tensor &pos,
+                        const at::Tensor &time, const at::Tensor &w_flow, const at::Tensor &b_flow, bool fix_track_mask) {
+    const char *op = "batrack_hip::track_tokens: ";
+    TORCH_CHECK(coords.dim() == 3 && coords.size(2) == 3 && fcorrs.dim() == 3 && ffeats.dim() == 3, op,
+                "coords [S, N, 3], fcorrs [S, N, LRR], ffeats [S, N, C]");
+    const int64_t S = coords.size(0), N = coords.size(1), LRR = fcorrs.size(2), C = ffeats.size(2);
+    TORCH_CHECK(w_flow.dim() == 2 && w_flow.size(1) == BT_TRACK_EMB && b_flow.numel() == w_flow.size(0), op, "w_flow [F, 195], b_flow [F]");
+    const int64_t F = w_flow.size(0), E = F + LRR + C + 2;
+    const at::Tensor *all[] = {&coords, &fcorrs, &ffeats, &track_mask, &vis, &pos, &time, &w_flow, &b_flow};
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->is_contiguous() && t->device() == coords.device(), op, "tensors must be contiguous and on one device");
+    }
+    TORCH_CHECK(fcorrs.size(0) == S && fcorrs.size(1) == N && ffeats.size(0) == S && ffeats.size(1) == N && track_mask.numel() == S * N
+                && vis.numel() == S * N && pos.numel() == N * E && time.numel() == S * E, op, "shapes disagree");
+    const float *sub = nullptr;
+    if (coords_sub.has_value()) {
+        sub = f32(*coords_sub, "coords_sub");
+        TORCH_CHECK(coords_sub->is_contiguous() && coords_sub->sizes() == coords.sizes() && coords_sub->device() == coords.device(), op,
+                    "coords_sub must be like coords");
+    }
+    at::Tensor x = at::empty({N, S, E}, coords.options());
+    if (N == 0) return x;
+    const int rc = bt_track_tokens(coords.data_ptr<float>(), sub, fcorrs.data_ptr<float>(), ffeats.data_ptr<float>(),
+                                   track_mask.data_ptr<float>(), vis.data_ptr<float>(), pos.data_ptr<float>(), time.data_ptr<float>(),
+                                   w_flow.data_ptr<float>(), b_flow.data_ptr<float>(), S, N, F, LRR, C, fix_track_mask ? 1 : 0,
+                                   x.data_ptr<float>(), c10::hip::getCurrentHIPStream(coords.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_track_tokens failed with status ", rc);
+    return x;
+}
+
+at::Tensor track_apply(const at::Tensor &delta, const at::Tensor &gamma, const at::Tensor &beta, const at::Tensor &w_u,
+                       const at::Tensor &b_u, at::Tensor state, at::Tensor ffeats, const c10::optional<at::Tensor> &total,
+                       const c10::optional<at::Tensor> &dyn_mask, double stride, double dz, double d_range, double d_near,
+                       bool use_log_depth) {
+    const char *op = "batrack_hip::track_apply: ";
+    TORCH_CHECK(delta.dim() == 3 && state.dim() == 3 && state.size(2) == 3 && ffeats.dim() == 3, op,
+                "delta [N, S, 3 + C], state [S, N, 3], ffeats [S, N, C]");
+    const int64_t N = delta.size(0), S = delta.size(1), C = ffeats.size(2);
+    const at::Tensor *all[] = {&delta, &gamma, &beta, &w_u, &b_u, &state, &ffeats};
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->is_contiguous() && t->device() == delta.device(), op, "tensors must be contiguous and on one device");
+    }
+    TORCH_CHECK(delta.size(2) == 3 + C && state.size(0) == S && state.size(1) == N && ffeats.size(0) == S && ffeats.size(1) == N
+                && gamma.numel() == C && beta.numel() == C && w_u.numel() == C * C && b_u.numel() == C, op, "shapes disagree");
+    TORCH_CHECK(total.has_value() == dyn_mask.has_value(), op, "total and dyn_mask come together (the static pass)");
+    const float *tot = nullptr, *dm = nullptr;
+    if (total.has_value()) {
+        tot = f32(*total, "total"); dm = f32(*dyn_mask, "dyn_mask");
+        TORCH_CHECK(total->is_contiguous() && total->sizes() == state.sizes() && dyn_mask->is_contiguous() && dyn_mask->numel() == N
+                    && total->device() == delta.device() && dyn_mask->device() == delta.device(), op, "total [S, N, 3], dyn_mask [N]");
+    }
+    at::Tensor out = at::empty_like(state);
+    if (N == 0) return out;
+    const int rc = bt_track_apply(delta.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), w_u.data_ptr<float>(),
+                                  b_u.data_ptr<float>(), state.data_ptr<float>(), ffeats.data_ptr<float>(), tot, dm, S, N, C, (float)stride,
+                                  (float)dz, (float)d_range, (float)d_near, use_log_depth ? 1 : 0, out.data_ptr<float>(),
+                                  c10::hip::getCurrentHIPStream(delta.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_track_apply failed with status ", rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -326,4 +420,9 @@ TORCH_LIBRARY(batrack_hip, m) {
           "int interp_h) -> (Tensor, Tensor, Tensor, Tensor)", &observe_window);
     m.def("corr_pyramid(Tensor fmaps, int levels) -> Tensor", &corr_pyramid);
     m.def("corr_lookup(Tensor pyramid, int[] shape, int levels, int radius, Tensor targets, Tensor coords) -> Tensor", &corr_lookup);
+    m.def("track_pos_embed(Tensor tabx, Tensor taby, Tensor coords) -> Tensor", &track_pos_embed);
+    m.def("track_tokens(Tensor coords, Tensor? coords_sub, Tensor fcorrs, Tensor ffeats, Tensor track_mask, Tensor vis, Tensor pos, "
+          "Tensor time, Tensor w_flow, Tensor b_flow, bool fix_track_mask) -> Tensor", &track_tokens);
+    m.def("track_apply(Tensor delta, Tensor gamma, Tensor beta, Tensor w_u, Tensor b_u, Tensor(a!) state, Tensor(b!) ffeats, "
+          "Tensor? total, Tensor? dyn_mask, float stride, float dz, float d_range, float d_near, bool use_log_depth) -> Tensor", &track_apply);
 }

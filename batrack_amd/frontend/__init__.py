@@ -2,6 +2,9 @@
 
   batrack_amd.frontend.corr.CorrBlock     the tracker's CorrBlock, fused: no correlation volume
   batrack_amd.frontend.corr.install       make the reference's unmodified md_tracker use it
+  batrack_amd.frontend.track_iter.forward_iteration   the tracker's refinement loop around its transformers: tokens and state update
+  batrack_amd.frontend.track_iter.sample_pos_embed    the position embedding of the tracks from two 1-D tables
+  batrack_amd.frontend.track_iter.install             make the reference's md_tracker use both
   batrack_amd.frontend.observe.window_observations   tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning
   batrack_amd.frontend.patches.generate_patches      patch selection, depth initialisation and colours of a new frame
