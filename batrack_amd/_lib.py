@@ -8,13 +8,14 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip"]
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_api.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip"]
 HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
            os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h"),
-           os.path.join("..", "..", "include", "batrack_patches.h"), os.path.join("..", "..", "include", "batrack_track.h")]
+           os.path.join("..", "..", "include", "batrack_patches.h"), os.path.join("..", "..", "include", "batrack_track.h"),
+           os.path.join("..", "..", "include", "batrack_attn.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -30,7 +31,8 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
                            "correlation lookup: more than 512 channels, a radius above 7, more than 8 levels, a map side above 32768, or more than 2^31 - 1 (frame, query, level) triples; "
                            "window observations: a window of more than 64 frames, 2^24 or more scores, or window buffers of 2^31 or more slots; "
                            "patch generation: more than 1024 candidates per cell (8 * patches per cell), or an image side above 32768; "
-                           "tracker iteration: more than 144 flow columns, more than 128 feature channels in the state update, or 2^31 - 16 or more tokens)"}
+                           "tracker iteration: more than 144 flow columns, more than 128 feature channels in the state update, or 2^31 - 16 or more tokens; "
+                           "attention: a head size other than 48, a size, stride or row index above 2^31 - 1, or more than 2^24 - 1 workgroups)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -347,6 +349,8 @@ def lib():
     L.bt_track_tokens.argtypes = [vp] * 10 + [i64] * 5 + [i32, vp, vp]
     L.bt_track_apply.restype = i32
     L.bt_track_apply.argtypes = [vp] * 9 + [i64] * 3 + [f32] * 4 + [i32, vp, vp]
+    L.bt_attention.restype = i32
+    L.bt_attention.argtypes = [vp, i64, vp, i64] + [i64] * 6 + [f32, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

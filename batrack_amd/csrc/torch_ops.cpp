@@ -50,6 +50,10 @@
 //                            bool use_log_depth) -> Tensor
 //       bt_track_apply: delta [N, S, 3 + C]; state [S, N, 3] and ffeats [S, N, C] updated in place; total [S, N, 3] and
 //       dyn_mask [N] select the static pass -> out [S, N, 3]
+//   batrack_hip::attention(Tensor qkv, int heads, int n_seq, int L, int seq_stride, int tok_stride, float scale) -> Tensor
+//       bt_attention (include/batrack_attn.h): qkv [rows, >= 3 * heads * 48] with unit last stride (the row stride is read from
+//       the tensor); token i of sequence b is row b * seq_stride + i * tok_stride -> [rows, heads * 48] (rows that no token
+//       addresses are left unwritten)
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -58,6 +62,7 @@
 #include <tuple>
 #include <vector>
 
+#include "../../include/batrack_attn.h"
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_corr.h"
 #include "../../include/batrack_observe.h"
@@ -399,6 +404,24 @@ at::Tensor track_apply(const at::Tensor &delta, const at::Tensor &gamma, const a
     return out;
 }
 
+at::Tensor attention(const at::Tensor &qkv, int64_t heads, int64_t n_seq, int64_t L, int64_t seq_stride, int64_t tok_stride, double scale) {
+    const char *op = "batrack_hip::attention: ";
+    const float *p = f32(qkv, "qkv");
+    TORCH_CHECK(heads >= 1 && heads <= (1 << 20) && n_seq >= 0 && L >= 1 && seq_stride >= 1 && tok_stride >= 1, op,
+                "heads, L and the strides must be positive, n_seq not negative");
+    const int64_t C = heads * BT_ATTN_HEAD_DIM, rows = qkv.dim() == 2 ? qkv.size(0) : 0;
+    TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) >= 3 * C && (qkv.size(1) == 1 || qkv.stride(1) == 1) && (rows <= 1 || qkv.stride(0) >= 3 * C),
+                op, "qkv must be [rows, >= 3 * heads * ", BT_ATTN_HEAD_DIM, "] with unit last stride");
+    TORCH_CHECK(n_seq <= BT_ATTN_MAX_INDEX && L <= BT_ATTN_MAX_INDEX && seq_stride <= BT_ATTN_MAX_INDEX && tok_stride <= BT_ATTN_MAX_INDEX
+                && (n_seq == 0 || (n_seq - 1) * seq_stride + (L - 1) * tok_stride < rows), op, "a token addresses a row past the end of qkv");
+    at::Tensor out = at::empty({rows, C}, qkv.options());
+    if (n_seq == 0 || rows == 0) return out;
+    const int rc = bt_attention(p, rows > 1 ? qkv.stride(0) : qkv.size(1), out.data_ptr<float>(), C, n_seq, L, seq_stride, tok_stride, heads,
+                                BT_ATTN_HEAD_DIM, (float)scale, c10::hip::getCurrentHIPStream(qkv.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_attention failed with status ", rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -425,4 +448,5 @@ TORCH_LIBRARY(batrack_hip, m) {
           "Tensor time, Tensor w_flow, Tensor b_flow, bool fix_track_mask) -> Tensor", &track_tokens);
     m.def("track_apply(Tensor delta, Tensor gamma, Tensor beta, Tensor w_u, Tensor b_u, Tensor(a!) state, Tensor(b!) ffeats, "
           "Tensor? total, Tensor? dyn_mask, float stride, float dz, float d_range, float d_near, bool use_log_depth) -> Tensor", &track_apply);
+    m.def("attention(Tensor qkv, int heads, int n_seq, int L, int seq_stride, int tok_stride, float scale) -> Tensor", &attention);
 }

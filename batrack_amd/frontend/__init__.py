@@ -5,6 +5,9 @@
   batrack_amd.frontend.track_iter.forward_iteration   the tracker's refinement loop around its transformers: tokens and state update
   batrack_amd.frontend.track_iter.sample_pos_embed    the position embedding of the tracks from two 1-D tables
   batrack_amd.frontend.track_iter.install             make the reference's md_tracker use both
+  batrack_amd.frontend.update_former.forward          the update transformers: attention without the score matrix
+  batrack_amd.frontend.update_former.attention        fused float32 attention over strided sequences
+  batrack_amd.frontend.update_former.install          make the reference's UpdateFormer use it
   batrack_amd.frontend.observe.window_observations   tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning
   batrack_amd.frontend.patches.generate_patches      patch selection, depth initialisation and colours of a new frame

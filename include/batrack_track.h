@@ -1,7 +1,7 @@
 /* batrack_track.h — C ABI of the tracker's refinement iteration around its two update transformers
  * (the reference's main/frontend/md_tracker.py:181-413, `MDTracker.forward_iteration`, and :49-61, `sample_pos_embed`):
  * the position embedding of the tracks, the transformer's input tokens in one launch, and the state update from the
- * transformer's output in one launch.  The transformers themselves are not here.
+ * transformer's output in one launch.  The transformers themselves are not here: their attention core is batrack_attn.h.
  *
  * Layouts.  B = 1.  State tensors are frame-major, as the correlation lookup (batrack_corr.h) wants them:
  * coords [S, N, 3] (x, y, z), ffeats [S, N, C], track_mask [S, N], vis [S, N], fcorrs [S, N, LRR], float32 contiguous.
