@@ -3,12 +3,10 @@
 //   cur  = D[i][m],                                    m = (A[i-1] > 0) & (D[i] > 0),  c = |m|
 //   prev = A[0][m] (i == 1)  or  A[i-2][(A[i-2] > 0) & (A[i-1] > 0)] ⊎ A[i-1][m]  (i >= 2)
 // unless c < 100 (A[i] = D[i]).  Per frame, one fixed sequence of launches on the caller's stream, no host round trip:
-//   k_ad_hist   one pass of a radix select (8-bit digits, most significant first: 4 passes for float32, 8 for float64) over
-//               the raw bits of the selected values (all > 0, so the bits order them), for four selections at once: the
-//               lower and upper middle element of cur and of prev.  Per-workgroup LDS histograms with wave-aggregated
-//               increments (radix_select.hpp's hist_add), flushed to global memory with integer atomics.  An upper selection
-//               shares its lower one's histogram while their prefixes agree.
-//   k_ad_pick   one workgroup, one wave per selection: narrows (prefix, rank) and clears the histogram for the next pass.
+//   k_ad_hist   one histogram pass of the radix select of radix_select.hpp (4 passes for float32, 8 for float64) over the
+//               raw bits of the selected values (all > 0, so the bits order them), for four selections at once: the lower
+//               and upper middle element of cur and of prev.
+//   k_ad_pick   its pick, one workgroup, one wave per selection; clears the histogram for the next pass.
 //               Pass 0 records c and the union count and decides the c < 100 branch; later passes of a skipped frame do
 //               nothing.  The last pass forms the medians and s in the input's dtype and hands (s, skip) to the write pass.
 //   k_ad_write  A[i] = s * D[i] (or D[i] for a skipped frame, or frame 0), 16-byte loads and stores, one multiply per pixel.
@@ -24,7 +22,7 @@ namespace bt {
 namespace ad {
 
 constexpr int kSel = 4;                          // cur lower, cur upper, prev lower, prev upper middle element
-constexpr int kBins = 256;
+constexpr int kBins = rs::kBins;
 constexpr int kHistThreads = 512, kHistBlocks = 256;
 constexpr int kWriteThreads = 256, kWriteBlocks = 1024;
 constexpr uint32_t kMinOverlap = 100;            // min_overlap_threshold, utils.py:273
@@ -44,7 +42,6 @@ constexpr size_t kStateOff = kHistBytes;
 constexpr size_t kWsBytes = kStateOff + 256;
 static_assert(sizeof(State) <= 256, "State");
 
-using rs::hist_add;
 using rs::mean2;
 
 __device__ __forceinline__ State *state(unsigned char *ws) { return reinterpret_cast<State *>(ws + kStateOff); }
@@ -90,32 +87,21 @@ __global__ __launch_bounds__(kHistThreads) void k_ad_hist(const T *cur, const T 
     const State *st = state(ws);
     if (pass > 0 && st->skip) return;                                     // c < 100: nothing to select
     __shared__ uint32_t h[kSel * kBins];
-    for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) h[i] = 0u;
+    rs::hist_clear(h, kSel * kBins);
     __syncthreads();
     constexpr int kBits = 8 * sizeof(T);
     const int shift = kBits - 8 - 8 * pass;
-    const uint64_t hi = pass == 0 ? 0ull : (~0ull << (shift + 8));       // the bits the prefix has fixed
+    const uint64_t hi = rs::fixed_mask<uint64_t>(pass, shift);
     const uint64_t p0 = st->prefix[0], p1 = st->prefix[1], p2 = st->prefix[2], p3 = st->prefix[3];
-    const bool dup_c = p0 == p1, dup_p = p2 == p3;
     for_pixels<T, VEC>(cur, prev, past, n, [&](T d, T a1, T a2) {
         const bool m = a1 > T(0) && d > T(0);                             // (NaN fails both tests)
         const bool mp = past != nullptr && a2 > T(0) && a1 > T(0);
-        const uint64_t kd = key(d), k1 = key(a1), k2 = key(a2);
-        hist_add(h, kd, shift, m && ((kd ^ p0) & hi) == 0ull);
-        if (!dup_c) hist_add(h + kBins, kd, shift, m && ((kd ^ p1) & hi) == 0ull);
-        hist_add(h + 2 * kBins, k1, shift, m && ((k1 ^ p2) & hi) == 0ull);
-        hist_add(h + 2 * kBins, k2, shift, mp && ((k2 ^ p2) & hi) == 0ull);
-        if (!dup_p) {
-            hist_add(h + 3 * kBins, k1, shift, m && ((k1 ^ p3) & hi) == 0ull);
-            hist_add(h + 3 * kBins, k2, shift, mp && ((k2 ^ p3) & hi) == 0ull);
-        }
+        rs::add_pair(h, key(d), shift, hi, p0, p1, m);
+        rs::add_pair(h + 2 * kBins, key(a1), shift, hi, p2, p3, m);
+        rs::add_pair(h + 2 * kBins, key(a2), shift, hi, p2, p3, mp);
     });
     __syncthreads();
-    uint32_t *gh = reinterpret_cast<uint32_t *>(ws);
-    for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) {
-        const uint32_t c = h[i];
-        if (c) atomicAdd(&gh[i], c);
-    }
+    rs::hist_flush(h, reinterpret_cast<uint32_t *>(ws), kSel * kBins);
 }
 
 template <class T>
@@ -126,44 +112,21 @@ __global__ __launch_bounds__(256) void k_ad_pick(unsigned char *ws, int pass, in
     constexpr int kPasses = sizeof(T);
     State *st = state(ws);
     uint32_t *gh = reinterpret_cast<uint32_t *>(ws);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x < kSel) old[threadIdx.x] = sel[threadIdx.x] = st->prefix[threadIdx.x];
+    const int w = threadIdx.x >> 6;
+    if (threadIdx.x < kSel) old[threadIdx.x] = sel[threadIdx.x] = st->prefix[threadIdx.x];   // old: as the histogram pass saw them
     if (threadIdx.x == 0) s_skip = pass == 0 ? 0u : st->skip;
     __syncthreads();
     if (!s_skip) {
-        // (the histogram pass decided on the prefixes before this pick: an upper selection whose prefix was its lower one's used that histogram)
-        const int src = (w == 1 && old[1] == old[0]) ? 0 : ((w == 3 && old[3] == old[2]) ? 2 : w);
-        const uint32_t *hh = gh + src * kBins;
-        uint32_t c[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[j] = hh[4 * lane + j];
-        const uint32_t loc = c[0] + c[1] + c[2] + c[3];
-        uint32_t inc = loc;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(inc, o);
-            if (lane >= o) inc += u;
-        }
-        const uint32_t excl = inc - loc, total = __shfl(inc, 63);
         // pass 0: every element of a set is counted in its selections' histogram; the middle ranks of the set's size
-        const uint32_t k = pass == 0 ? ((w & 1) ? total / 2 : (total ? (total - 1) / 2 : 0u)) : st->rank[w];
-        if (total > 0 && excl <= k && k < inc) {
-            uint32_t cum = excl;
-            int d = 4 * lane + 3;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (k < cum + c[j]) { d = 4 * lane + j; break; }
-                cum += c[j];
-            }
-            const uint64_t p = old[w] | ((uint64_t)d << (8 * (kPasses - 1 - pass)));
-            st->prefix[w] = p;
-            st->rank[w] = k - cum;
-            sel[w] = p;
-        }
-        if (lane == 0) tot[w] = total;
+        const uint32_t total = rs::narrow(gh + rs::shared_source(w, old) * kBins,
+                                          [&](uint32_t t) { return pass == 0 ? rs::middle_rank(t, w & 1) : st->rank[w]; },
+                                          8 * (kPasses - 1 - pass), sel[w], st->rank[w]);
+        if ((threadIdx.x & 63) == 0) tot[w] = total;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) gh[i] = 0u;  // clear for the next pass (read above by this block only)
+    rs::hist_clear(gh, kSel * kBins);                                     // for the next pass (read above by this block only)
     if (threadIdx.x != 0) return;
+    for (int q = 0; q < kSel; ++q) st->prefix[q] = sel[q];               // (the picks narrowed the copies in LDS)
     if (pass == 0) {
         st->count[0] = tot[0];
         st->count[1] = tot[2];

@@ -1,11 +1,8 @@
 // depth_eval.hip — the video-depth metrics of the reference's compute_errors / eval_depth_metric (include/batrack_depth.h), gfx950.
-//   k_de_hist     one pass of a radix select (8-bit digits, 4 passes, most significant first) over the order-preserving uint32 keys
-//                 of the valid gt and pred values, for four selections at once: the lower and upper middle element of each.
-//                 Per-workgroup LDS histograms with wave-aggregated increments, flushed to global memory with integer atomics.
-//                 The upper-middle selection shares the lower one's histogram while their prefixes agree (always on pass 0).
-//   k_de_pick     one workgroup, one wave per selection: the digit that holds the remaining rank, narrowing (prefix, rank); after
-//                 the last pass the medians and their ratio (numpy's median: an even count takes the float64 mean of the two
-//                 middle elements).
+//   k_de_hist     one histogram pass of the radix select of radix_select.hpp (4 passes) over the order-preserving uint32 keys of
+//                 the valid gt and pred values, for four selections at once: the lower and upper middle element of each.
+//   k_de_pick     its pick, one workgroup, one wave per selection; after the last pass the medians and their ratio (numpy's
+//                 median: an even count takes the float64 mean of the two middle elements).
 //   k_de_sums     least-squares scaling: per-workgroup count, means and centred second moments of (p, g) in float64, each thread's
 //                 sums taken about its first valid element and merged pairwise (Chan et al.) in a fixed order;  k_de_solve: the
 //                 same merge over the workgroups, s = Cpg / Cpp, t = mean g - s mean p, the rank decision from det = n Cpp
@@ -24,7 +21,7 @@ namespace bt {
 namespace de {
 
 constexpr int kSel = 4;                          // gt lower, gt upper, pred lower, pred upper middle element
-constexpr int kBins = 256;
+constexpr int kBins = rs::kBins;
 constexpr int kPasses = 4;                       // 8-bit digits
 constexpr int kHistThreads = 512, kHistBlocks = 512;
 constexpr int kSumThreads = 256, kSumBlocks = 2048;
@@ -45,7 +42,6 @@ static_assert(sizeof(State) <= 256, "State");
 
 using rs::fdecode;
 using rs::fkey;
-using rs::hist_add;
 
 __device__ __forceinline__ State *state(unsigned char *ws) { return reinterpret_cast<State *>(ws + kStateOff); }
 __device__ __forceinline__ double *partials(unsigned char *ws) { return reinterpret_cast<double *>(ws + kPartOff); }
@@ -75,67 +71,37 @@ __global__ __launch_bounds__(kHistThreads) void k_de_hist(const float *gt, const
                                                           float dmax, unsigned char *ws, int pass) {
     __shared__ uint32_t h[kSel * kBins];
     __shared__ uint32_t s_nan;
-    for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) h[i] = 0u;
+    rs::hist_clear(h, kSel * kBins);
     if (threadIdx.x == 0) s_nan = 0u;
     __syncthreads();
     const State *st = state(ws);
     const int shift = 24 - 8 * pass;
-    const uint32_t hi = pass == 0 ? 0u : (0xffffffffu << (shift + 8));      // the bits the prefix has fixed
+    const uint32_t hi = rs::fixed_mask<uint32_t>(pass, shift);
     const uint32_t p0 = st->prefix[0], p1 = st->prefix[1], p2 = st->prefix[2], p3 = st->prefix[3];
-    const bool dup_g = p0 == p1, dup_p = p2 == p3;
     for_elems<VEC>(gt, pred, mask, n, [&](float g, float p, bool m) {
         const bool v = m && g > dmin && g < dmax;
-        const uint32_t kg = fkey(g), kp = fkey(p);
-        hist_add(h, kg, shift, v && ((kg ^ p0) & hi) == 0u);
-        if (!dup_g) hist_add(h + kBins, kg, shift, v && ((kg ^ p1) & hi) == 0u);
-        hist_add(h + 2 * kBins, kp, shift, v && ((kp ^ p2) & hi) == 0u);
-        if (!dup_p) hist_add(h + 3 * kBins, kp, shift, v && ((kp ^ p3) & hi) == 0u);
+        rs::add_pair(h, fkey(g), shift, hi, p0, p1, v);
+        rs::add_pair(h + 2 * kBins, fkey(p), shift, hi, p2, p3, v);
         if (pass == 0) {
             const uint64_t b = __ballot(v && p != p);
             if (b && (int)__lane_id() == __ffsll((unsigned long long)b) - 1) atomicAdd(&s_nan, (uint32_t)__popcll(b));
         }
     });
     __syncthreads();
-    uint32_t *gh = reinterpret_cast<uint32_t *>(ws) + (size_t)pass * kSel * kBins;
-    for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) {
-        const uint32_t c = h[i];
-        if (c) atomicAdd(&gh[i], c);
-    }
+    rs::hist_flush(h, reinterpret_cast<uint32_t *>(ws) + (size_t)pass * kSel * kBins, kSel * kBins);
     if (pass == 0 && threadIdx.x == 0 && s_nan) atomicAdd(&state(ws)->nan_pred, s_nan);
 }
 
 __global__ __launch_bounds__(256) void k_de_pick(unsigned char *ws, int pass) {
     __shared__ uint32_t old[kSel];
     State *st = state(ws);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x < kSel) old[threadIdx.x] = st->prefix[threadIdx.x];
+    const int w = threadIdx.x >> 6;
+    if (threadIdx.x < kSel) old[threadIdx.x] = st->prefix[threadIdx.x];  // as the histogram pass saw them
     __syncthreads();
-    // (the histogram pass decided on the prefixes before this pick: an upper selection whose prefix was its lower one's used that histogram)
-    const int src = (w == 1 && old[1] == old[0]) ? 0 : ((w == 3 && old[3] == old[2]) ? 2 : w);
-    const uint32_t *hh = reinterpret_cast<const uint32_t *>(ws) + ((size_t)pass * kSel + src) * kBins;
-    uint32_t c[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = hh[4 * lane + j];
-    const uint32_t loc = c[0] + c[1] + c[2] + c[3];
-    uint32_t inc = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    const uint32_t excl = inc - loc, total = __shfl(inc, 63);
+    const uint32_t *hh = reinterpret_cast<const uint32_t *>(ws) + ((size_t)pass * kSel + rs::shared_source(w, old)) * kBins;
     // pass 0: every valid element is counted in every selection's histogram; the middle ranks of the valid count
-    const uint32_t k = pass == 0 ? ((w & 1) ? total / 2 : (total ? (total - 1) / 2 : 0u)) : st->rank[w];
-    if (total > 0 && excl <= k && k < inc) {
-        uint32_t cum = excl;
-        int d = 4 * lane + 3;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k < cum + c[j]) { d = 4 * lane + j; break; }
-            cum += c[j];
-        }
-        st->prefix[w] = old[w] | ((uint32_t)d << (24 - 8 * pass));
-        st->rank[w] = k - cum;
-    }
+    const uint32_t total = rs::narrow(hh, [&](uint32_t t) { return pass == 0 ? rs::middle_rank(t, w & 1) : st->rank[w]; },
+                                      24 - 8 * pass, st->prefix[w], st->rank[w]);
     if (pass == 0 && threadIdx.x == 0) st->count = total;
     if (pass == kPasses - 1) {
         __syncthreads();

@@ -8,17 +8,16 @@
 //   depth = clip(1 / ((1 / n) y), 1e-4, 1e4),  depth = 0 where depth < 1e-2.
 // One fixed sequence of launches on the caller's stream, no host round trip, nothing allocated:
 //   k_ma_init    clears the histograms and the selection state (the workspace's contents on entry are arbitrary).
-//   k_ma_hist    one pass of a SEGMENTED radix select (8-bit digits, most significant first: 4 passes for float32, 8 for float64)
-//                over order-preserving keys (radix_select.hpp: -0 and +0 are one key; NaN is left out, so a segment's NaN count
-//                is its size minus its histogram total).  A workgroup takes a slice of one frame, builds that frame's histograms
-//                in LDS (wave-aggregated increments) and flushes them with integer atomics.  g, the ratio and g - s d are
-//                recomputed from m and d in every pass: storing g would cost the same bytes as reading m.
+//   k_ma_hist    one histogram pass of the radix select of radix_select.hpp (4 passes for float32, 8 for float64), SEGMENTED:
+//                a workgroup takes a slice of one frame and adds to that frame's histograms.  NaN is left out, so a segment's
+//                NaN count is its size minus its histogram total.  g, the ratio and g - s d are recomputed from m and d in
+//                every pass: storing g would cost the same bytes as reading m.
 //                  round A   the two middle elements of g and of d, for every frame at once
 //                  round B   the two middle elements of the ratio            round C   of g - s_t d
 //                  round P   two order statistics of y over all T*H*W elements (numpy's previous / next index of the 98th
 //                            percentile), one segment
-//   k_ma_pick    one wave per selection (a workgroup per frame): narrows (prefix, rank) and clears the histogram for the next
-//                pass; the last pass forms the medians (NaN when the segment holds a NaN) or the percentile's interpolation.
+//   k_ma_pick    its pick, one wave per selection (a workgroup per frame); clears the histogram for the next pass; the last
+//                pass forms the medians (NaN when the segment holds a NaN) or the percentile's interpolation.
 //   k_ma_scene   one workgroup: median(p) by radix select in LDS, the argmin (first index on ties, the first NaN if any), the
 //                aligns and numpy's percentile indices and gamma for T*H*W elements.
 //   k_ma_write   depth from d, 16-byte loads and stores.
@@ -38,11 +37,10 @@ namespace ma {
 
 using rs::fdecode;
 using rs::fkey;
-using rs::hist_add;
 using rs::mean2;
 
 enum Round { kA = 0, kB = 1, kC = 2, kP = 3 };
-constexpr int kBins = 256;
+constexpr int kBins = rs::kBins;
 constexpr int kMaxSel = 4;                        // round A: g lower, g upper, d lower, d upper middle element
 constexpr int kHistThreads = 512;
 constexpr int kHistTarget = 2048;                 // workgroups of a hist pass: about 8 per CU, the rest grid-strided
@@ -168,80 +166,41 @@ __global__ __launch_bounds__(kHistThreads) void k_ma_hist(const float *mono, con
     constexpr int kSel = R == kA ? 4 : 2;
     __shared__ uint32_t h[kSel * kBins];
     const int shift = 8 * (int)sizeof(T) - 8 - 8 * pass;
-    const uint64_t hi = pass == 0 ? 0ull : (~0ull << (shift + 8));      // the bits the prefix has fixed
+    const uint64_t hi = rs::fixed_mask<uint64_t>(pass, shift);
     Scene *sc = scene(ws, nt);
     const Seg *sg_all = segs(ws, nt);
     const int64_t units = nseg * parts;
     for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
         const int64_t s = u / parts;
         const int part = (int)(u - s * parts);
-        for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) h[i] = 0u;
+        rs::hist_clear(h, kSel * kBins);
         __syncthreads();
         const Seg *sg = R == kP ? &sc->sel : &sg_all[s];
         const uint64_t p0 = sg->prefix[0], p1 = sg->prefix[1], p2 = sg->prefix[2], p3 = sg->prefix[3];
-        const bool dup0 = p0 == p1, dup1 = p2 == p3;
         const float *d = mono + s * len;
         const T *m = R == kP ? nullptr : metric + s * len;
         // (a NaN value fails x == x and is never added: the histogram total of a set is its non-NaN count)
-        auto add2 = [&](uint32_t *hh, T x, uint64_t q0, uint64_t q1, bool dup) {
-            const uint64_t kx = (uint64_t)fkey(x);
-            const bool ok = x == x;
-            hist_add(hh, kx, shift, ok && ((kx ^ q0) & hi) == 0ull);
-            if (!dup) hist_add(hh + kBins, kx, shift, ok && ((kx ^ q1) & hi) == 0ull);
-        };
+        auto add2 = [&](uint32_t *hh, T x, uint64_t q0, uint64_t q1) { rs::add_pair(hh, (uint64_t)fkey(x), shift, hi, q0, q1, x == x); };
         if (R == kA) {
             for_segment<T, VEC>(d, m, len, part, parts, [&](float dv, T mv) {
-                add2(h, gdisp<T>(mv, dv), p0, p1, dup0);
-                add2(h + 2 * kBins, (T)dv, p2, p3, dup1);                // d's keys in D's width: the same order
+                add2(h, gdisp<T>(mv, dv), p0, p1);
+                add2(h + 2 * kBins, (T)dv, p2, p3);                      // d's keys in D's width: the same order
             });
         } else if (R == kB) {
             const T mg = (T)sg->v[0];
             const float md = (float)sg->v[1];
-            for_segment<T, VEC>(d, m, len, part, parts, [&](float dv, T mv) { add2(h, ratio<T>(gdisp<T>(mv, dv), dv, mg, md), p0, p1, dup0); });
+            for_segment<T, VEC>(d, m, len, part, parts, [&](float dv, T mv) { add2(h, ratio<T>(gdisp<T>(mv, dv), dv, mg, md), p0, p1); });
         } else if (R == kC) {
             const T st = (T)sg->v[2];
-            for_segment<T, VEC>(d, m, len, part, parts, [&](float dv, T mv) { add2(h, resid<T>(gdisp<T>(mv, dv), dv, st), p0, p1, dup0); });
+            for_segment<T, VEC>(d, m, len, part, parts, [&](float dv, T mv) { add2(h, resid<T>(gdisp<T>(mv, dv), dv, st), p0, p1); });
         } else {
             const T a_s = (T)sc->a_s, a_c = (T)sc->a_c;
-            for_segment<T, VEC>(d, (const T *)nullptr, len, part, parts, [&](float dv, T) { add2(h, affine<T>(dv, a_s, a_c), p0, p1, dup0); });
+            for_segment<T, VEC>(d, (const T *)nullptr, len, part, parts, [&](float dv, T) { add2(h, affine<T>(dv, a_s, a_c), p0, p1); });
         }
         __syncthreads();
-        uint32_t *gh = hist(ws, s);
-        for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) {
-            const uint32_t c = h[i];
-            if (c) atomicAdd(&gh[i], c);
-        }
+        rs::hist_flush(h, hist(ws, s), kSel * kBins);
         __syncthreads();                                                  // h is cleared for the next unit
     }
-}
-
-// one wave: the inclusive / exclusive prefix of this lane's four bins and the histogram's total
-__device__ __forceinline__ void wave_scan(const uint32_t *hh, uint32_t c[4], uint32_t &excl, uint32_t &inc, uint32_t &total) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) c[j] = hh[4 * lane + j];
-    const uint32_t loc = c[0] + c[1] + c[2] + c[3];
-    inc = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    excl = inc - loc;
-    total = __shfl(inc, 63);
-}
-
-// the lane whose bins hold rank k (excl <= k < inc): the digit, and the rank left among the keys of that digit
-__device__ __forceinline__ int find_digit(const uint32_t c[4], uint32_t excl, uint32_t k, uint32_t &rem) {
-    const int lane = threadIdx.x & 63;
-    uint32_t cum = excl;
-    int d = 4 * lane + 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (k < cum + c[j]) { d = 4 * lane + j; break; }
-        cum += c[j];
-    }
-    rem = k - cum;
-    return d;
 }
 
 // numpy's median from the two middle elements of a set of `len` elements of which `count` are not NaN
@@ -271,35 +230,25 @@ __global__ __launch_bounds__(kPickThreads) void k_ma_pick(unsigned char *ws, int
     __shared__ uint64_t old[kMaxSel], sel[kMaxSel];
     __shared__ uint32_t tot[kMaxSel];
     Scene *sc = scene(ws, nt);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
     for (int64_t s = blockIdx.x; s < nseg; s += gridDim.x) {
         Seg *sg = R == kP ? &sc->sel : &segs(ws, nt)[s];
         uint32_t *gh = hist(ws, s);
-        if (threadIdx.x < kSel) old[threadIdx.x] = sel[threadIdx.x] = sg->prefix[threadIdx.x];
+        if (threadIdx.x < kSel) old[threadIdx.x] = sel[threadIdx.x] = sg->prefix[threadIdx.x];   // old: as the hist pass saw them
         __syncthreads();
         if (w < kSel) {
-            // (the hist pass decided on the prefixes before this pick: an upper selection whose prefix was its lower one's used
-            // that histogram)
-            const int src = (w == 1 && old[1] == old[0]) ? 0 : ((w == 3 && old[3] == old[2]) ? 2 : w);
-            uint32_t c[4], excl, inc, total;
-            wave_scan(gh + src * kBins, c, excl, inc, total);
-            uint32_t k;
-            if (pass > 0) k = sg->rank[w];
-            else if (R == kP) k = total ? (uint32_t)((uint64_t)sc->target[w] < total ? sc->target[w] : total - 1) : 0u;
-            else k = (w & 1) ? total / 2 : (total ? (total - 1) / 2 : 0u);    // the middle ranks of the non-NaN count
-            if (total > 0 && excl <= k && k < inc) {
-                uint32_t rem;
-                const int dg = find_digit(c, excl, k, rem);
-                const uint64_t p = old[w] | ((uint64_t)dg << (8 * (kPasses - 1 - pass)));
-                sg->prefix[w] = p;
-                sg->rank[w] = rem;
-                sel[w] = p;
-            }
-            if (lane == 0) tot[w] = total;
+            auto rank_of = [&](uint32_t total) -> uint32_t {
+                if (pass > 0) return sg->rank[w];
+                if (R == kP) return total ? (uint32_t)((uint64_t)sc->target[w] < total ? sc->target[w] : total - 1) : 0u;
+                return rs::middle_rank(total, w & 1);                     // of the non-NaN count
+            };
+            const uint32_t total = rs::narrow(gh + rs::shared_source(w, old) * kBins, rank_of, 8 * (kPasses - 1 - pass), sel[w], sg->rank[w]);
+            if ((threadIdx.x & 63) == 0) tot[w] = total;
         }
         __syncthreads();
-        for (int i = threadIdx.x; i < kSel * kBins; i += blockDim.x) gh[i] = 0u;   // for the next pass (read above by this block only)
+        rs::hist_clear(gh, kSel * kBins);                                 // for the next pass (read above by this block only)
         if (threadIdx.x == 0) {
+            for (int q = 0; q < kSel; ++q) sg->prefix[q] = sel[q];       // (the picks narrowed the copies in LDS)
             if (pass == 0) {
                 sg->count[0] = tot[0];
                 sg->count[1] = kSel == 4 ? tot[2] : 0u;
@@ -369,31 +318,21 @@ __global__ __launch_bounds__(kSceneThreads) void k_ma_scene(unsigned char *ws, i
     // median(p): the two middle elements by radix select over the T values, in LDS
     for (int pass = 0; pass < kPasses; ++pass) {
         const int shift = 8 * kPasses - 8 - 8 * pass;
-        const uint64_t hi = pass == 0 ? 0ull : (~0ull << (shift + 8));
-        for (int i = threadIdx.x; i < 2 * kBins; i += blockDim.x) h[i] = 0u;
+        const uint64_t hi = rs::fixed_mask<uint64_t>(pass, shift);
+        rs::hist_clear(h, 2 * kBins);
         __syncthreads();
-        const uint64_t q0 = prefix[0], q1 = prefix[1];
+        const uint64_t q[2] = {prefix[0], prefix[1]};                     // as this pass's histograms see them
         for (int64_t t0 = 0; t0 < nt; t0 += blockDim.x) {                 // (whole waves run every trip: hist_add is wave-wide)
             const int64_t t = t0 + threadIdx.x;
             const bool in = t < nt;
             const T x = in ? pval(t) : T(0);
-            const uint64_t kx = (uint64_t)fkey(x);
-            const bool ok = in && x == x;
-            hist_add(h, kx, shift, ok && ((kx ^ q0) & hi) == 0ull);
-            hist_add(h + kBins, kx, shift, ok && ((kx ^ q1) & hi) == 0ull);
+            rs::add_pair(h, (uint64_t)fkey(x), shift, hi, q[0], q[1], in && x == x);
         }
         __syncthreads();
         if (w < 2) {
-            uint32_t c[4], excl, inc, tt;
-            wave_scan(h + w * kBins, c, excl, inc, tt);
-            const uint32_t k = pass > 0 ? rank[w] : (w ? tt / 2 : (tt ? (tt - 1) / 2 : 0u));
+            const uint32_t tt = rs::narrow(h + rs::shared_source(w, q) * kBins,
+                                           [&](uint32_t t) { return pass > 0 ? rank[w] : rs::middle_rank(t, w & 1); }, shift, prefix[w], rank[w]);
             if (pass == 0 && threadIdx.x == 0) total = tt;
-            if (tt > 0 && excl <= k && k < inc) {
-                uint32_t rem;
-                const int dg = find_digit(c, excl, k, rem);
-                prefix[w] |= (uint64_t)dg << shift;
-                rank[w] = rem;
-            }
         }
         __syncthreads();
     }

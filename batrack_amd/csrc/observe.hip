@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_observe_query(ObQuery a) {
 // static = 1 - dyn over n values; a = the k0-th, b = the k1-th smallest (k1 = k0 or k0 + 1); *th = min(lerp(a, b, w), st)
 __global__ __launch_bounds__(OB_SEL_THREADS) void k_observe_threshold(const float *__restrict__ dyn, int n, int k0, int k1,
                                                                        float w, float st, float *__restrict__ th) {
-    __shared__ uint32_t h[256];
+    __shared__ uint32_t h[rs::kBins];
     __shared__ uint32_t s_prefix, s_rank, s_cnt, s_nan;
     __shared__ uint32_t s_min[OB_SEL_THREADS / 64];
     const int tid = threadIdx.x;
@@ -67,8 +67,8 @@ __global__ __launch_bounds__(OB_SEL_THREADS) void k_observe_threshold(const floa
     if (tid == 0) s_nan = 0;
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
-        const uint32_t mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-        if (tid < 256) h[tid] = 0;
+        const uint32_t mask = rs::fixed_mask<uint32_t>(pass, shift);
+        if (tid < rs::kBins) h[tid] = 0;
         __syncthreads();
         for (int base = 0; base < n; base += OB_SEL_THREADS) {                 // every lane of a wave walks the loop
             const int i = base + tid;
@@ -78,28 +78,20 @@ __global__ __launch_bounds__(OB_SEL_THREADS) void k_observe_threshold(const floa
                 const float v = dyn[i];
                 if (pass == 0 && v != v) s_nan = 1;
                 key = rs::fkey(1.0f - v);
-                act = (key & mask) == prefix;
+                act = rs::carries(key, prefix, mask);
             }
             rs::hist_add(h, key, shift, act);
         }
         __syncthreads();
-        if (tid < 64) {                                                        // the bin that holds `rank`: 4 bins a lane
-            const uint32_t c0 = h[4 * tid], c1 = h[4 * tid + 1], c2 = h[4 * tid + 2], c3 = h[4 * tid + 3];
-            const uint32_t s = c0 + c1 + c2 + c3;
-            uint32_t inc = s;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t up = __shfl_up(inc, d);
-                if (tid >= d) inc += up;
-            }
-            const uint32_t exc = inc - s;
-            if (rank >= exc && rank < inc) {
-                uint32_t r = rank - exc, bin = 4 * tid, c = c0;
-                if (r >= c0) { r -= c0; ++bin; c = c1;
-                    if (r >= c1) { r -= c1; ++bin; c = c2;
-                        if (r >= c2) { r -= c2; ++bin; c = c3; } } }
-                s_prefix = prefix | (bin << shift);
-                s_rank = r;
-                s_cnt = c;
+        if (tid < 64) {                                                        // one wave: the bin that holds `rank`
+            uint32_t c[4], excl, inc, total;
+            rs::wave_scan(h, c, excl, inc, total);
+            if (excl <= rank && rank < inc) {
+                uint32_t rem, cnt;
+                const int d = rs::find_digit(c, excl, rank, rem, cnt);
+                s_prefix = prefix | ((uint32_t)d << shift);
+                s_rank = rem;
+                s_cnt = cnt;
             }
         }
         __syncthreads();

@@ -1,8 +1,9 @@
 """bt_observe_window at its limits (include/batrack_observe.h, batrack_amd/csrc/observe.hip), the op against the torch
 restatement tests/observe_util.window_observations_ref on the same GPU tensors, every output and every buffer bit for
 bit: query counts around the workgroup's block of 32 tracks and the wave, windows of 1, 2 and 12 frames filled to 1,
-S - 1 and S, no edges at all, every optional pointer NULL, quantile ranks that are integers and fractional, all scores
-equal, 28,800 scores (29 passes of the select's workgroup), and every invalid argument of the header."""
+S - 1 and S, no edges at all, every optional pointer NULL, quantile ranks that are integers and fractional, the
+interpolated pair inside and across groups of tied scores, all scores equal, 28,800 scores (29 passes of the select's
+workgroup), and every invalid argument of the header."""
 import ctypes
 
 import numpy as np
@@ -59,6 +60,20 @@ def test_quantile_ranks(q):
     got = compare(args, kw, f"q {q}")
     if q == 0.5:
         assert got["weights_pose"].any() and not np.array_equal(got["weights_pose"], got["weights"])
+
+
+@pytest.mark.parametrize("q", [0.07, 0.36, 0.5, 1.0])
+def test_quantile_pair_against_tie_groups(q):
+    """Eight scores in three tie groups of 3, 2 and 3: counted from the largest static score the interpolated pair is ranks
+    (0, 1) inside the first group, (2, 3) across two groups, (3, 4) inside the middle group, and the last element alone."""
+    S, Nq = 2, 4
+    M, kf = split(Nq, S)
+    dyn = np.array([[0.99, 0.95, 0.97, 0.99], [0.95, 0.99, 0.95, 0.97]])
+    cfg = ObserveConfig(STATIC_QUANTILE=q)
+    args, kw = ou.random_inputs(21, Nq, M, S, S, kf, DEV, cfg=cfg, dyn=dyn)
+    th = ou.static_threshold(args[3].cpu(), cfg.STATIC_QUANTILE, cfg.STATIC_THRESHOLD)
+    assert np.isfinite(th) and th < cfg.STATIC_THRESHOLD
+    compare(args, kw, f"tie groups, q {q}")
 
 
 @pytest.mark.parametrize("value,any_static", [(0.95, True), (0.5, True), (float("nan"), False)])
