@@ -22,10 +22,12 @@ __device__ __forceinline__ float blend4(float dx, float dy, float p00, float p01
 // torch's clamp(min=1e-2): a NaN stays NaN (fmaxf would return 1e-2)
 __device__ __forceinline__ float clamp_min_1e2(float d) { return d < 1e-2f ? 1e-2f : d; }
 
-// floor(x).int() with the out-of-range cases spelt out (NaN -> 0): the indices are clamped to the map afterwards
+// floor(x).int() with the out-of-range cases spelt out.  The reference converts on an x86 host, where every value that does
+// not fit an int32 — beyond 2^31 on EITHER side, and NaN — becomes INT_MIN; so does this (a saturating conversion would put
+// +3e9 at INT_MAX: other weights, another clamped index).  The largest float below 2^31 is 2^31 - 128: x0 + 1 never overflows.
 __device__ __forceinline__ int floor_int(float x) {
     const float f = floorf(x);
-    return f != f ? 0 : (f <= -2147483648.0f ? (-2147483647 - 1) : (f >= 2147483648.0f ? 2147483647 : (int)f));
+    return f >= -2147483648.0f && f < 2147483648.0f ? (int)f : (-2147483647 - 1);
 }
 
 // model_utils.py:94-154 on one [H, W] map

@@ -14,7 +14,15 @@
  *   x0 = floor(x), x1 = x0 + 1 (the same for y); the four corner indices clamped to the map; the weights from the UNCLAMPED
  *   corners, (x1 - x)(y1 - y), (x - x0)(y1 - y), (x1 - x)(y - y0), (x - x0)(y - y0); every product rounded, the four
  *   products summed left to right.  out [N, E].  Bit-equal to the reference's float32 run given tables that are the
- *   float32 rounding of its float64 table.  A NaN or infinite coordinate gives non-finite values in its own row only.
+ *   float32 rounding of its float64 table — for EVERY finite coordinate, the reference run on an x86 host: it takes x0 as
+ *   floor(x).int(), and a floor that does not fit an int32 (|x| >= 2^31 on either side) becomes INT_MIN there, as it does
+ *   here.  What then holds for finite coordinates (tests/golden/pos_embed_far.npz records it):
+ *     both coordinates below 2^31 in size   the sample; from 2^24 up x0 = x, x1 = x0 + 1 rounds to even, the weights are 0, 1 or 2;
+ *     one coordinate beyond                 its two weights are +-(x + 2^31), the clamped indices coincide at 0 and the four
+ *                                           terms cancel up to their rounding: zero, or a finite residue of the size of an
+ *                                           ulp of the weight when the other coordinate has a fractional part;
+ *     both beyond (or one beyond, the other from 2^24 + 2 up) with |x - x0| |y - y0| above FLT_MAX   NaN (inf - inf).
+ *   A NaN or infinite coordinate gives non-finite values; whatever a coordinate is, it touches its own row only.
  *
  * bt_track_tokens.  x [N, S, E], E = F + LRR + C + 2.  With c = coords - coords_sub (coords_sub may be null: c = coords)
  * and flow[n, t, :] = c[t, n, :] - c[0, n, :]:

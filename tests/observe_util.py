@@ -42,12 +42,19 @@ def static_threshold(dyn, static_quantile, static_thr):
     return f32(min(th, static_thr))
 
 
+def floor_int32(v):
+    """floor(v).int() as the reference's x86 host converts, held in float: a floor that does not fit an int32 (beyond 2^31 on
+    either side, or NaN) is INT_MIN (the same as track_iter_util.floor_int32)."""
+    f = torch.floor(v)
+    return torch.where((f >= -2.0 ** 31) & (f < 2.0 ** 31), f, torch.full_like(f, -2.0 ** 31))
+
+
 def sample_maps(dmaps, queries):
-    """The depth maps [S', H, W] at the queries (t, x, y) [Nq, 3]: floor, clamped indices, weights from the unclamped
-    corners, the four products summed left to right."""
+    """The depth maps [S', H, W] at the queries (t, x, y) [Nq, 3]: floor (converted to int32 as the reference's host does),
+    clamped indices, weights from the unclamped corners, the four products summed left to right."""
     _, H, W = dmaps.shape
     t, x, y = queries[:, 0].long(), queries[:, 1], queries[:, 2]
-    x0, y0 = torch.floor(x), torch.floor(y)
+    x0, y0 = floor_int32(x), floor_int32(y)
     x1, y1 = x0 + 1, y0 + 1
     cx0, cx1 = (c.clamp(0, W - 1).long() for c in (x0, x1))
     cy0, cy1 = (c.clamp(0, H - 1).long() for c in (y0, y1))

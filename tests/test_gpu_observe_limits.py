@@ -109,6 +109,19 @@ def test_null_optional_buffers_and_no_tail():
     compare(args, kw, "no tail, short window buffer")
 
 
+def test_far_query_coordinates():
+    """The query depth at finite coordinates beyond int32 (bilinear_clamped of csrc/sample_taps.hpp): the reference's floor
+    becomes INT_MIN on either side, the clamped indices coincide, the weights are of the coordinate's size and cancel: d is 0
+    or a rounding residue (query_disp = 100 where it is 0), and NaN where the product of two far weights overflows."""
+    S, Nq, M, kf = 6, 66, 22, 2
+    args, kw = ou.random_inputs(14, Nq, M, S, S, kf, DEV, interp_shape=None)
+    far = [(3e9, 5.0), (-3e9, 5.5), (7.25, 3e9), (7.25, 2.0 ** 31), (2.0 ** 31, 9.0), (1e30, 4.5), (5.5, -1e30), (5e37, 7.0),
+           (3e9, -1e30), (1e30, 3e9), (2.0 ** 24 + 2, 6.5), (-(2.0 ** 24 + 2), 2.0 ** 24 + 2)]
+    args[4][0, 10:10 + len(far), 1:] = torch.tensor(far, device=DEV)
+    got = compare(args, kw, "far queries")["query_disp"][10:10 + len(far)]
+    assert got[0] == 100.0 and got[4] == 100.0 and np.isnan(got[8]) and np.isnan(got[9]) and np.isfinite(got[[0, 1, 2, 3, 4, 5, 6, 7, 10, 11]]).all()
+
+
 # ---- the C ABI itself
 def c_args(args, kw, outs):
     traj, depth, vis, dyn, queries, dmaps, ii, jj, kk = args

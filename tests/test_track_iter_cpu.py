@@ -116,6 +116,27 @@ def test_separable_tables_are_the_full_table():
     assert np.array_equal(track_iter._sincos_1d(U.E, np.arange(12, dtype=np.float32)), U.sincos_1d(U.E, 12))
 
 
+def test_restatement_reproduces_the_reference_at_far_coordinates():
+    """tests/golden/pos_embed_far.npz: the reference's sample_pos_embed at every pair of 19 finite coordinates up to FLT_MAX.
+    The restatement equals it wherever the reference's result is finite (-0 and +0 alike) and is non-finite exactly where
+    the reference is.  Beyond 2^31 the reference's finite results are not zeros: a coordinate there meets a fractional one
+    in range in 26 pairs whose four terms cancel only up to rounding (values up to 1e31)."""
+    F = np.load(U.FAR_GOLD)
+    H, W, E = int(F["H"]), int(F["W"]), int(F["E"])
+    values, xy, want = torch.from_numpy(F["values"]), torch.from_numpy(F["xy"]), torch.from_numpy(F["out"])
+    assert (H, W, E) == (U.FAR_H, U.FAR_W, U.FAR_E) and torch.equal(values, U.far_values(W)) and torch.equal(xy, U.far_pairs(values))
+    assert bool(torch.isfinite(xy).all()) and want.shape == (values.numel() ** 2, E)
+    got = U.pos_embed(*U.pos_tables(H, W, E), xy)
+    finite = torch.isfinite(want)
+    assert torch.equal(torch.isfinite(got), finite)
+    assert bool((got[finite] == want[finite]).all())
+    near = (xy.abs() < 2.0 ** 31).all(1)
+    assert bool(finite[near].all()) and int(near.sum()) == 11 * 11               # where the int32 floor is defined: all finite
+    far_finite = finite.all(1) & ~near
+    assert int((~finite.all(1)).sum()) == 48 and int((want[far_finite] != 0).any(1).sum()) == 26
+    assert os.path.getsize(U.FAR_GOLD) < 8 * 1024
+
+
 def test_fixture_stays_small():
     assert os.path.getsize(U.GOLD) < 523 * 1024
 

@@ -83,9 +83,17 @@ def full_table(H, W, E=E):
                             .astype(np.float32))
 
 
+def floor_int32(v):
+    """floor(v).int() as the reference's x86 host converts, held in float: a floor that does not fit an int32 (beyond 2^31 on
+    either side, or NaN) is INT_MIN.  (torch's own .int() is undefined there: it saturates on a GPU.)  The + 1 that follows
+    may be done in float: from 2^24 up it rounds to even exactly as the conversion of the int32 sum does."""
+    f = torch.floor(v)
+    return torch.where((f >= -2.0 ** 31) & (f < 2.0 ** 31), f, torch.full_like(f, -2.0 ** 31))
+
+
 def _corners(xy, H, W):
     x, y = xy[:, 0].float(), xy[:, 1].float()
-    x0, y0 = torch.floor(x), torch.floor(y)
+    x0, y0 = floor_int32(x), floor_int32(y)
     x1, y1 = x0 + 1, y0 + 1
     idx = lambda v, hi: v.clamp(0, hi).long()
     w = [((x1 - x) * (y1 - y))[:, None], ((x - x0) * (y1 - y))[:, None], ((x1 - x) * (y - y0))[:, None], ((x - x0) * (y - y0))[:, None]]
@@ -106,6 +114,27 @@ def pos_embed_full_table(H, W, E, xy):
     tab = full_table(H, W, E).to(xy.device)
     ix0, ix1, iy0, iy1, (w00, w01, w10, w11) = _corners(xy, H, W)
     return w00 * tab[iy0, ix0] + w01 * tab[iy0, ix1] + w10 * tab[iy1, ix0] + w11 * tab[iy1, ix1]
+
+
+# ---------------------------------------------------------------------------------------------------- far coordinates
+FAR_GOLD = os.path.join(os.path.dirname(GOLD), "pos_embed_far.npz")
+FAR_H, FAR_W, FAR_E = 16, 24, 8          # the fixture's map; E = 8 keeps the file to a few KB
+
+
+def far_values(W=FAR_W):
+    """The finite float32 coordinates of tests/golden/pos_embed_far.npz: inside the map, just outside it, around 2^24 (where
+    x + 1 starts to round), at 2^31 (where an int32 floor ends) and far beyond, up to FLT_MAX."""
+    fmax = float(np.finfo(np.float32).max)
+    v = [0.0, 3.25, 7.5, 15.0, 22.75, -3.5, W + 2.25]
+    for a in (2.0 ** 24 + 1, 2.0 ** 24 + 2, 2.0 ** 31, 3e9, 1e30, fmax):
+        v += [a, -a]
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def far_pairs(values):
+    """[V * V, 2]: every (x, y) pair, x outer."""
+    V = values.numel()
+    return torch.stack([values[:, None].expand(V, V), values[None, :].expand(V, V)], -1).reshape(V * V, 2).contiguous()
 
 
 # ------------------------------------------------------------------------------------------------------------- tokens
