@@ -3,6 +3,7 @@
 //                     fractional offsets, every product rounded, the sum left to right.       k_patchify<true>, k_patch_generate
 //   bilinear_clamped  bilinear_sample2d (frontend/core/model_utils.py:75-158) of one map: floor, indices clamped to the
 //                     map, weights from the unclamped corners, the sum left to right.        k_observe_query, k_patch_generate
+//                     bilinear_taps + bilinear_blend are its two halves, for a point with many channels.        k_feat_sample
 // Every operation is rounded (contraction off inside each function, whatever the including file sets); the division is the
 // correctly rounded one: files that include this must not be built with a fast-math flag.
 #pragma once
@@ -30,8 +31,14 @@ __device__ __forceinline__ int floor_int(float x) {
     return f >= -2147483648.0f && f < 2147483648.0f ? (int)f : (-2147483647 - 1);
 }
 
-// model_utils.py:94-154 on one [H, W] map
-__device__ __forceinline__ float bilinear_clamped(const float *im, int H, int W, float x, float y) {
+// model_utils.py:94-147: the four corner offsets into one [H, W] map (indices clamped to the map) and the four weights
+// (from the unclamped corners).  Computed once per point; bilinear_blend applies them to as many maps as the point has channels.
+struct BilinearTaps {
+    long long i00, i01, i10, i11;
+    float w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ BilinearTaps bilinear_taps(int H, int W, float x, float y) {
 #pragma clang fp contract(off)
     const int x0 = floor_int(x), y0 = floor_int(y);
     const long long x1 = (long long)x0 + 1, y1 = (long long)y0 + 1;
@@ -39,9 +46,21 @@ __device__ __forceinline__ float bilinear_clamped(const float *im, int H, int W,
     const long long mx = W - 1, my = H - 1;
     const long long cx0 = x0 < 0 ? 0 : (x0 > mx ? mx : x0), cx1 = x1 < 0 ? 0 : (x1 > mx ? mx : x1);
     const long long cy0 = y0 < 0 ? 0 : (y0 > my ? my : y0), cy1 = y1 < 0 ? 0 : (y1 > my ? my : y1);
-    const float i00 = im[cy0 * W + cx0], i01 = im[cy0 * W + cx1], i10 = im[cy1 * W + cx0], i11 = im[cy1 * W + cx1];
-    const float w00 = (x1f - x) * (y1f - y), w01 = (x - x0f) * (y1f - y), w10 = (x1f - x) * (y - y0f), w11 = (x - x0f) * (y - y0f);
-    return ((w00 * i00 + w01 * i01) + w10 * i10) + w11 * i11;                  // model_utils.py:152-154, left to right
+    BilinearTaps t;
+    t.i00 = cy0 * W + cx0; t.i01 = cy0 * W + cx1; t.i10 = cy1 * W + cx0; t.i11 = cy1 * W + cx1;
+    t.w00 = (x1f - x) * (y1f - y); t.w01 = (x - x0f) * (y1f - y); t.w10 = (x1f - x) * (y - y0f); t.w11 = (x - x0f) * (y - y0f);
+    return t;
+}
+
+// model_utils.py:152-154 on one map: every product rounded, the sum left to right
+__device__ __forceinline__ float bilinear_blend(const float *im, const BilinearTaps &t) {
+#pragma clang fp contract(off)
+    return ((t.w00 * im[t.i00] + t.w01 * im[t.i01]) + t.w10 * im[t.i10]) + t.w11 * im[t.i11];
+}
+
+// model_utils.py:94-154 on one [H, W] map
+__device__ __forceinline__ float bilinear_clamped(const float *im, int H, int W, float x, float y) {
+    return bilinear_blend(im, bilinear_taps(H, W, x, y));
 }
 
 }  // namespace bt

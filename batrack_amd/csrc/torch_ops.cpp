@@ -54,6 +54,15 @@
 //       bt_attention (include/batrack_attn.h): qkv [rows, >= 3 * heads * 48] with unit last stride (the row stride is read from
 //       the tensor); token i of sequence b is row b * seq_stride + i * tok_stride -> [rows, heads * 48] (rows that no token
 //       addresses are left unwritten)
+//   batrack_hip::depth_range(Tensor depth, bool use_log_depth) -> Tensor
+//       bt_depth_range (include/batrack_window.h): depth [T, H, W], any strides (read in place) -> [2] (min, max) on the device
+//   batrack_hip::window_depth(Tensor depth, int S, int stride, float d_near, float d_range, float dz, bool use_log_depth) -> (Tensor, Tensor)
+//       bt_window_depth: depth [frames <= S, H, W], any strides -> dmaps [S, H / stride, W / stride] and zrange [2]
+//   batrack_hip::embed_conv(Tensor fnet_maps, Tensor dmaps, Tensor zrange, Tensor wpacked, Tensor bias, Tensor freqs, int frame0,
+//                           Tensor(a!) out) -> ()
+//       bt_embed_conv: fnet_maps [F, 128, h, w], any strides; dmaps [S, h, w]; wpacked [24, 9, 8, 128]; out [F, 128, h, w] contiguous
+//   batrack_hip::feat_sample(Tensor fmaps, Tensor frames, Tensor xy) -> Tensor
+//       bt_feat_sample: fmaps [S, 128, h, w] contiguous, frames [n] int32, xy [n, >= 2] with unit last stride -> [n, 128]
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -68,6 +77,7 @@
 #include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
 #include "../../include/batrack_track.h"
+#include "../../include/batrack_window.h"
 
 namespace {
 
@@ -422,6 +432,85 @@ at::Tensor attention(const at::Tensor &qkv, int64_t heads, int64_t n_seq, int64_
     return out;
 }
 
+at::Tensor window_workspace(const at::Tensor &like) {          // zeroed: the ticket in its last word must be
+    return at::zeros({(int64_t)((bt_window_workspace_bytes() + 3) / 4)}, like.options().dtype(at::kInt));
+}
+
+at::Tensor depth_range(const at::Tensor &depth, bool use_log_depth) {
+    const char *op = "batrack_hip::depth_range: ";
+    const float *d = f32(depth, "depth");
+    TORCH_CHECK(depth.dim() == 3 && depth.numel() > 0, op, "depth must be [T, H, W] and not empty");
+    at::Tensor out = at::empty({2}, depth.options()), ws = window_workspace(depth);
+    const int rc = bt_depth_range(d, depth.size(0), depth.size(1), depth.size(2), depth.stride(0), depth.stride(1), depth.stride(2),
+                                  use_log_depth ? 1 : 0, ws.data_ptr(), out.data_ptr<float>(),
+                                  c10::hip::getCurrentHIPStream(depth.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_depth_range failed with status ", rc);
+    return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> window_depth(const at::Tensor &depth, int64_t S, int64_t stride, double d_near, double d_range,
+                                                double dz, bool use_log_depth) {
+    const char *op = "batrack_hip::window_depth: ";
+    const float *d = f32(depth, "depth");
+    TORCH_CHECK(depth.dim() == 3 && depth.numel() > 0 && stride >= 1 && S >= depth.size(0), op,
+                "depth must be [frames <= S, H, W] and not empty, stride positive");
+    at::Tensor dmaps = at::empty({S, depth.size(1) / stride, depth.size(2) / stride}, depth.options());
+    at::Tensor zrange = at::empty({2}, depth.options()), ws = window_workspace(depth);
+    const int rc = bt_window_depth(d, depth.size(0), S, depth.size(1), depth.size(2), depth.stride(0), depth.stride(1), depth.stride(2),
+                                   stride, (float)d_near, (float)d_range, (float)dz, use_log_depth ? 1 : 0, ws.data_ptr(),
+                                   dmaps.data_ptr<float>(), zrange.data_ptr<float>(),
+                                   c10::hip::getCurrentHIPStream(depth.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_window_depth failed with status ", rc);
+    return std::make_tuple(dmaps, zrange);
+}
+
+void embed_conv(const at::Tensor &fnet_maps, const at::Tensor &dmaps, const at::Tensor &zrange, const at::Tensor &wpacked,
+                const at::Tensor &bias, const at::Tensor &freqs, int64_t frame0, at::Tensor out) {
+    const char *op = "batrack_hip::embed_conv: ";
+    const at::Tensor *all[] = {&fnet_maps, &dmaps, &zrange, &wpacked, &bias, &freqs, &out};
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->device() == fnet_maps.device(), op, "tensors must be on one device");
+    }
+    TORCH_CHECK(fnet_maps.dim() == 4 && dmaps.dim() == 3 && dmaps.is_contiguous(), op, "fnet_maps [F, C, h, w], dmaps [S, h, w] contiguous");
+    const int64_t F = fnet_maps.size(0), C = fnet_maps.size(1), h = fnet_maps.size(2), w = fnet_maps.size(3), S = dmaps.size(0);
+    TORCH_CHECK(C == BT_WINDOW_C, op, "the encoder's maps must have ", BT_WINDOW_C, " channels");
+    TORCH_CHECK(h >= 2 && w >= 2, op, "maps of fewer than 2 rows or columns have no x or y range to normalise by");
+    TORCH_CHECK(dmaps.size(1) == h && dmaps.size(2) == w && frame0 >= 0 && frame0 + F <= S, op, "dmaps must be [S, h, w] with frame0 + F <= S");
+    TORCH_CHECK(zrange.numel() == 2 && zrange.is_contiguous() && bias.numel() == BT_WINDOW_C && bias.is_contiguous()
+                && freqs.numel() == BT_WINDOW_FREQS && freqs.is_contiguous() && wpacked.is_contiguous()
+                && wpacked.numel() == 9 * (BT_WINDOW_C + BT_WINDOW_EMB + 1) * BT_WINDOW_C, op,
+                "zrange [2], bias [128], freqs [10], wpacked [24, 9, 8, 128], all contiguous");
+    TORCH_CHECK(out.is_contiguous() && out.dim() == 4 && out.size(0) == F && out.size(1) == C && out.size(2) == h && out.size(3) == w, op,
+                "out must be a contiguous [F, 128, h, w]");
+    if (F == 0) return;
+    const int rc = bt_embed_conv(fnet_maps.data_ptr<float>(), fnet_maps.stride(0), fnet_maps.stride(1), fnet_maps.stride(2), fnet_maps.stride(3),
+                                 dmaps.data_ptr<float>(), zrange.data_ptr<float>(), wpacked.data_ptr<float>(), bias.data_ptr<float>(),
+                                 freqs.data_ptr<float>(), S, frame0, F, h, w, C, out.data_ptr<float>(),
+                                 c10::hip::getCurrentHIPStream(fnet_maps.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_embed_conv failed with status ", rc);
+}
+
+at::Tensor feat_sample(const at::Tensor &fmaps, const at::Tensor &frames, const at::Tensor &xy) {
+    const char *op = "batrack_hip::feat_sample: ";
+    const float *fm = f32(fmaps, "fmaps"), *pxy = f32(xy, "xy");
+    TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kInt && frames.dim() == 1 && frames.is_contiguous(), op,
+                "frames must be a contiguous int32 [n] on the GPU");
+    TORCH_CHECK(fmaps.dim() == 4 && fmaps.is_contiguous() && fmaps.size(1) == BT_WINDOW_C && fmaps.numel() > 0, op,
+                "fmaps must be a contiguous [S, 128, h, w]");
+    const int64_t n = frames.size(0);
+    TORCH_CHECK(xy.dim() == 2 && xy.size(0) == n && xy.size(1) >= 2 && (n <= 1 || xy.stride(0) >= 2) && xy.stride(1) == 1, op,
+                "xy must be [n, >= 2] with unit last stride");
+    TORCH_CHECK(frames.device() == fmaps.device() && xy.device() == fmaps.device(), op, "tensors must be on one device");
+    at::Tensor out = at::empty({n, (int64_t)BT_WINDOW_C}, fmaps.options());
+    if (n == 0) return out;
+    const int rc = bt_feat_sample(fm, fmaps.size(0), fmaps.size(1), fmaps.size(2), fmaps.size(3), frames.data_ptr<int32_t>(), pxy,
+                                  n > 1 ? xy.stride(0) : 2, n, out.data_ptr<float>(),
+                                  c10::hip::getCurrentHIPStream(fmaps.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_feat_sample failed with status ", rc);
+    return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -449,4 +538,10 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("track_apply(Tensor delta, Tensor gamma, Tensor beta, Tensor w_u, Tensor b_u, Tensor(a!) state, Tensor(b!) ffeats, "
           "Tensor? total, Tensor? dyn_mask, float stride, float dz, float d_range, float d_near, bool use_log_depth) -> Tensor", &track_apply);
     m.def("attention(Tensor qkv, int heads, int n_seq, int L, int seq_stride, int tok_stride, float scale) -> Tensor", &attention);
+    m.def("depth_range(Tensor depth, bool use_log_depth) -> Tensor", &depth_range);
+    m.def("window_depth(Tensor depth, int S, int stride, float d_near, float d_range, float dz, bool use_log_depth) -> (Tensor, Tensor)",
+          &window_depth);
+    m.def("embed_conv(Tensor fnet_maps, Tensor dmaps, Tensor zrange, Tensor wpacked, Tensor bias, Tensor freqs, int frame0, "
+          "Tensor(a!) out) -> ()", &embed_conv);
+    m.def("feat_sample(Tensor fmaps, Tensor frames, Tensor xy) -> Tensor", &feat_sample);
 }

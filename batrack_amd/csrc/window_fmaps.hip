@@ -1,0 +1,316 @@
+// window_fmaps.hip — the tracker's window preparation (include/batrack_window.h holds the specification): k_depth_range,
+// k_window_depth, k_embed_conv, k_feat_sample.
+//
+// k_depth_range and k_window_depth end in a minimum and a maximum over everything they read.  Each block reduces its own
+// share and leaves the pair in the workspace; a ticket tells the last block to finish that it is the last, and it reduces the
+// pairs and puts the ticket back to zero.  One launch, no atomics on the values, and min / max do not depend on the order.
+// A NaN among the values they select makes both results NaN, as torch's min() and max() do.
+//
+// k_embed_conv is the 3 x 3 convolution 191 -> 128 as an implicit GEMM on v_mfma_f32_16x16x4_f32: rows are output pixels,
+// columns the 128 output channels, K = 9 taps x 192 input channels (191 and a zero weight).
+//   tile     a workgroup (4 waves) owns a 16 x 8 tile of output pixels of one frame and all 128 channels; wave v owns tile
+//            rows 2v and 2v + 1, each a 16-pixel MFMA row block: 2 x 8 accumulators of 4 registers.
+//   K-chunk  8 input channels at a time: their 18 x 10 halo tile (zero outside the map) and their 9 x 8 x 128 weights are
+//            staged in LDS, 50288 bytes with the pixels' coordinates — two workgroups share a CU (184 VGPRs allow two waves a SIMD), and while one
+//            stages the other multiplies.  Chunks 0 .. 15 are the encoder's channels, read from memory; chunks 16 .. 23 are the embedding,
+//            COMPUTED into the same halo tile from the pixel's normalised (x, y, z), which is kept in LDS per halo pixel.
+//   operands A: lane l holds pixel l % 16 of the row block and channel l / 16 of the group of four — one ds_read_b32 from the
+//            halo tile at the tap's offset.  B: lane l holds channel l / 16 and output column 16 ct + l % 16.  The halo
+//            plane stride (208) and the weight row stride (144) are 16 mod 32, so that the two channel rows a 32-lane half
+//            reads fall on different banks.  A B fragment feeds both row blocks: 10 LDS reads per 16 MFMAs.
+//   order    chunk, tap, group of four channels: fixed, the same for every pixel of every frame, whatever frame0 and F are.
+// What it leaves on the table is in DESIGN.md.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/batrack_ba.h"
+#include "../../include/batrack_window.h"
+#include "sample_taps.hpp"
+
+namespace bt {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int WD_THREADS = 256, WD_MAX_BLOCKS = 1024, WD_PER_THREAD = 8;
+constexpr size_t WD_WORKSPACE = (size_t)2 * WD_MAX_BLOCKS * sizeof(float) + sizeof(unsigned);
+
+constexpr int EC_THREADS = 256, EC_TW = 16, EC_TH = 8, EC_HW = EC_TW + 2, EC_HH = EC_TH + 2, EC_HALO = EC_HW * EC_HH;
+constexpr int EC_KC = BT_WINDOW_KCHUNK, EC_PL = 208, EC_WLD = 144, EC_CHUNKS = (BT_WINDOW_C + BT_WINDOW_EMB + 1) / EC_KC;
+constexpr int EC_NT = BT_WINDOW_C / 16;
+static_assert(EC_PL >= EC_HALO && EC_PL % 32 == 16 && EC_WLD >= BT_WINDOW_C && EC_WLD % 32 == 16, "LDS strides");
+static_assert(EC_CHUNKS * EC_KC == 192 && EC_TH == 2 * (EC_THREADS / 64), "tiling");
+
+constexpr int FS_THREADS = BT_WINDOW_C;
+
+__device__ __forceinline__ float depth_process(float d, int use_log) {
+    if (!use_log) return d;
+    return logf(d < 1e-3f ? 1e-3f : d);                        // clamp(min=1e-3): a NaN stays NaN
+}
+
+// torch's min / max: a NaN on either side is the result
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
+__device__ __forceinline__ void nan_minmax(float v, float &mn, float &mx) { mn = nan_min(mn, v); mx = nan_max(mx, v); }
+
+// the block's (mn, mx) -> part[block]; the last block to arrive reduces part[0 .. gridDim.x) into out[0 .. 1]
+__device__ void minmax_finish(float mn, float mx, float *part, unsigned *ticket, float *out) {
+    __shared__ float s_mn[WD_THREADS / 64], s_mx[WD_THREADS / 64];
+    __shared__ unsigned s_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto block_reduce = [&](float &a, float &b) {
+        for (int o = 32; o; o >>= 1) { a = nan_min(a, __shfl_xor(a, o)); b = nan_max(b, __shfl_xor(b, o)); }
+        __syncthreads();
+        if (lane == 0) { s_mn[wave] = a; s_mx[wave] = b; }
+        __syncthreads();
+        a = s_mn[0]; b = s_mx[0];
+        for (int i = 1; i < WD_THREADS / 64; ++i) { a = nan_min(a, s_mn[i]); b = nan_max(b, s_mx[i]); }
+    };
+    block_reduce(mn, mx);
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(part + 2 * blockIdx.x, mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(part + 2 * blockIdx.x + 1, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        s_last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    mn = INFINITY; mx = -INFINITY;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += WD_THREADS) {
+        mn = nan_min(mn, __hip_atomic_load(part + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        mx = nan_max(mx, __hip_atomic_load(part + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    block_reduce(mn, mx);
+    if (threadIdx.x == 0) {
+        out[0] = mn; out[1] = mx;
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- k_depth_range
+__global__ __launch_bounds__(WD_THREADS) void k_depth_range(const float *__restrict__ depth, int H, int W, long long st, long long sy,
+                                                           long long sx, long long total, int use_log, float *part,
+                                                           unsigned *ticket, float *out) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (long long i = (long long)blockIdx.x * WD_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * WD_THREADS) {
+        const long long row = i / W, t = row / H;
+        const int x = (int)(i - row * W), y = (int)(row - t * H);
+        const float d = depth[t * st + y * sy + x * sx];
+        if (use_log || d > 0.01f) {
+            nan_minmax(depth_process(d, use_log), mn, mx);       // (d > 0.01 is false for a NaN: only the log form can meet one)
+        }
+    }
+    minmax_finish(mn, mx, part, ticket, out);
+}
+
+// -------------------------------------------------------------------------------------------------------- k_window_depth
+__global__ __launch_bounds__(WD_THREADS) void k_window_depth(const float *__restrict__ depth, int frames, int h, int w, long long st,
+                                                            long long sy, long long sx, int stride, float d_near, float d_range,
+                                                            float Dz, int use_log, long long total, float *__restrict__ dmaps,
+                                                            float *part, unsigned *ticket, float *zrange) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (long long i = (long long)blockIdx.x * WD_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * WD_THREADS) {
+        const long long row = i / w, t = row / h;
+        const int x = (int)(i - row * w), y = (int)(row - t * h);
+        const long long ts = t < frames ? t : frames - 1;        // a short last window repeats its last frame
+        const float d = depth_process(depth[ts * st + (long long)y * stride * sy + (long long)x * stride * sx], use_log);
+        const float v = __fmul_rn(__fdiv_rn(__fsub_rn(d, d_near), d_range), Dz);
+        dmaps[i] = v;
+        nan_minmax(v, mn, mx);
+    }
+    minmax_finish(mn, mx, part, ticket, zrange);
+}
+
+// ---------------------------------------------------------------------------------------------------------- k_embed_conv
+// 2 ((v - lo) / (hi - lo) - 0.5), md_tracker.py:525-528, every operation rounded
+__device__ __forceinline__ float normalise(float v, float lo, float hi) {
+    return __fmul_rn(2.0f, __fsub_rn(__fdiv_rn(__fsub_rn(v, lo), __fsub_rn(hi, lo)), 0.5f));
+}
+
+__global__ __launch_bounds__(EC_THREADS) void k_embed_conv(const float *__restrict__ fnet, long long sf, long long sc, long long sy,
+                                                          long long sx, const float *__restrict__ dmaps,
+                                                          const float *__restrict__ zrange, const float *__restrict__ wp,
+                                                          const float *__restrict__ bias, const float *__restrict__ freqs,
+                                                          int frame0, int h, int w, int tiles_x, float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float w_l[9 * EC_KC * EC_WLD];       // [tap][channel of the chunk][EC_WLD]
+    __shared__ float in_l[EC_KC * EC_PL];                                         // [channel of the chunk][halo pixel]
+    __shared__ float p_l[3 * EC_HALO];                                            // normalised x, y, z of the halo pixels
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
+    const int f = blockIdx.y, ty0 = (blockIdx.x / tiles_x) * EC_TH, tx0 = (blockIdx.x % tiles_x) * EC_TW;
+    const long long hw = (long long)h * w;
+
+    {
+        const float zlo = zrange[0], zhi = zrange[1];
+        const float *dm = dmaps + (long long)(frame0 + f) * hw;
+        for (int p = tid; p < EC_HALO; p += EC_THREADS) {
+            const int gy = ty0 + p / EC_HW - 1, gx = tx0 + p % EC_HW - 1;
+            const bool inside = gy >= 0 && gy < h && gx >= 0 && gx < w;
+            p_l[p] = normalise((float)gx, 0.0f, (float)(w - 1));
+            p_l[EC_HALO + p] = normalise((float)gy, 0.0f, (float)(h - 1));
+            p_l[2 * EC_HALO + p] = inside ? normalise(dm[(long long)gy * w + gx], zlo, zhi) : 0.0f;
+        }
+    }
+
+    f32x4 acc[2][EC_NT];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int ct = 0; ct < EC_NT; ++ct) acc[r][ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    const float *fbase = fnet + (long long)f * sf;
+    for (int chunk = 0; chunk < EC_CHUNKS; ++chunk) {
+        __syncthreads();                                         // the previous chunk's reads are done (and p_l is written)
+        const float4 *wsrc = reinterpret_cast<const float4 *>(wp + (size_t)chunk * 9 * EC_KC * BT_WINDOW_C);
+        for (int i = tid; i < 9 * EC_KC * (BT_WINDOW_C / 4); i += EC_THREADS) {
+            const int row = i >> 5, c4 = i & 31;
+            *reinterpret_cast<float4 *>(w_l + row * EC_WLD + c4 * 4) = wsrc[i];
+        }
+        for (int idx = tid; idx < EC_KC * EC_HALO; idx += EC_THREADS) {
+            const int chl = idx / EC_HALO, p = idx - chl * EC_HALO;
+            const int gy = ty0 + p / EC_HW - 1, gx = tx0 + p % EC_HW - 1;
+            float v = 0.0f;                                      // zero padding, for the embedding as for the maps
+            if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
+                const int c = chunk * EC_KC + chl;
+                if (c < BT_WINDOW_C) v = fbase[c * sc + gy * sy + gx * sx];
+                else {
+                    const int e = c - BT_WINDOW_C;               // Embedder_Fourier's order: the input, then per frequency sin(xyz), cos(xyz)
+                    if (e < 3) v = p_l[e * EC_HALO + p];
+                    else if (e < BT_WINDOW_EMB) {
+                        const int i = (e - 3) / 6, r = (e - 3) - 6 * i;
+                        const float arg = __fmul_rn(p_l[(r < 3 ? r : r - 3) * EC_HALO + p], freqs[i]);
+                        v = r < 3 ? sinf(arg) : cosf(arg);
+                    }
+                }
+            }
+            in_l[chl * EC_PL + p] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+            for (int s = 0; s < EC_KC / 4; ++s) {
+                const float *ap = in_l + (4 * s + q) * EC_PL + (2 * wave + ky) * EC_HW + l16 + kx;
+                const float a0 = ap[0], a1 = ap[EC_HW];
+                const float *wr = w_l + (tap * EC_KC + 4 * s + q) * EC_WLD + l16;
+#pragma unroll
+                for (int ct = 0; ct < EC_NT; ++ct) {
+                    const float b = wr[ct * 16];
+                    acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][ct], 0, 0, 0);
+                    acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][ct], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // register j of lane l is pixel 4 (l / 16) + j of the row block, column 16 ct + l % 16
+    float *ob = out + (long long)f * BT_WINDOW_C * hw;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = ty0 + 2 * wave + r;
+        if (y >= h) continue;
+#pragma unroll
+        for (int ct = 0; ct < EC_NT; ++ct) {
+            const int col = ct * 16 + l16;
+            const float b = bias[col];
+            float *orow = ob + (long long)col * hw + (long long)y * w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = tx0 + 4 * q + j;
+                if (x < w) orow[x] = __fadd_rn(acc[r][ct][j], b);
+            }
+        }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------- k_feat_sample
+// one block per query, one thread per channel; the taps are the query's, the same in every thread
+__global__ __launch_bounds__(FS_THREADS) void k_feat_sample(const float *__restrict__ fmaps, int S, int h, int w,
+                                                           const int *__restrict__ frames, const float *__restrict__ xy,
+                                                           long long xy_stride, long long n, float *__restrict__ out) {
+    const long long hw = (long long)h * w;
+    for (long long k = blockIdx.x; k < n; k += gridDim.x) {
+        int fr = frames[k];
+        fr = fr < 0 ? 0 : (fr > S - 1 ? S - 1 : fr);
+        const BilinearTaps t = bilinear_taps(h, w, xy[k * xy_stride], xy[k * xy_stride + 1]);
+        out[k * BT_WINDOW_C + threadIdx.x] = bilinear_blend(fmaps + ((long long)fr * BT_WINDOW_C + threadIdx.x) * hw, t);
+    }
+}
+
+constexpr long long kI31 = 2147483647LL;
+
+static unsigned wd_blocks(long long total) {
+    const long long nb = (total + (long long)WD_THREADS * WD_PER_THREAD - 1) / ((long long)WD_THREADS * WD_PER_THREAD);
+    return (unsigned)(nb < 1 ? 1 : (nb < WD_MAX_BLOCKS ? nb : WD_MAX_BLOCKS));
+}
+
+// the largest element offset a [T, H, W] view with these strides reaches, or -1 when it passes 2^31 - 1
+static long long view_extent(long long T, long long H, long long W, long long st, long long sy, long long sx) {
+    if (st > kI31 || sy > kI31 || sx > kI31) return -1;
+    const __int128 e = (__int128)(T - 1) * st + (__int128)(H - 1) * sy + (__int128)(W - 1) * sx;
+    return e > kI31 ? -1 : (long long)e;
+}
+
+}  // namespace bt
+
+extern "C" size_t bt_window_workspace_bytes(void) { return bt::WD_WORKSPACE; }
+
+extern "C" int bt_depth_range(const float *depth, int64_t T, int64_t H, int64_t W, int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                              int32_t use_log_depth, void *workspace, float *out, void *stream) {
+    if (!depth || !workspace || !out || T < 1 || H < 1 || W < 1 || stride_t < 0 || stride_y < 0 || stride_x < 0) return BT_EINVAL;
+    if (T > bt::kI31 || H > bt::kI31 || W > bt::kI31 || (__int128)T * H * W > bt::kI31
+        || bt::view_extent(T, H, W, stride_t, stride_y, stride_x) < 0) return BT_EUNSUPPORTED;
+    const long long total = (long long)T * H * W;
+    float *part = (float *)workspace;
+    hipLaunchKernelGGL(bt::k_depth_range, dim3(bt::wd_blocks(total)), dim3(bt::WD_THREADS), 0, (hipStream_t)stream, depth, (int)H, (int)W,
+                       (long long)stride_t, (long long)stride_y, (long long)stride_x, total, (int)use_log_depth, part,
+                       (unsigned *)(part + 2 * bt::WD_MAX_BLOCKS), out);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}
+
+extern "C" int bt_window_depth(const float *depth, int64_t frames, int64_t S, int64_t H, int64_t W, int64_t stride_t, int64_t stride_y,
+                               int64_t stride_x, int64_t stride, float d_near, float d_range, float Dz, int32_t use_log_depth,
+                               void *workspace, float *dmaps, float *zrange, void *stream) {
+    if (!depth || !workspace || !dmaps || !zrange || S < 1 || frames < 1 || frames > S || H < 1 || W < 1 || stride < 1
+        || stride_t < 0 || stride_y < 0 || stride_x < 0) return BT_EINVAL;
+    if (S > bt::kI31 || H > bt::kI31 || W > bt::kI31 || stride > bt::kI31) return BT_EUNSUPPORTED;
+    const long long h = H / stride, w = W / stride;
+    if (h < 1 || w < 1) return BT_EINVAL;
+    if ((__int128)S * h * w > bt::kI31 || bt::view_extent(frames, H, W, stride_t, stride_y, stride_x) < 0) return BT_EUNSUPPORTED;
+    const long long total = (long long)S * h * w;
+    float *part = (float *)workspace;
+    hipLaunchKernelGGL(bt::k_window_depth, dim3(bt::wd_blocks(total)), dim3(bt::WD_THREADS), 0, (hipStream_t)stream, depth, (int)frames,
+                       (int)h, (int)w, (long long)stride_t, (long long)stride_y, (long long)stride_x, (int)stride, d_near, d_range, Dz,
+                       (int)use_log_depth, total, dmaps, part, (unsigned *)(part + 2 * bt::WD_MAX_BLOCKS), zrange);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}
+
+extern "C" int bt_embed_conv(const float *fnet, int64_t sf, int64_t sc, int64_t sy, int64_t sx, const float *dmaps, const float *zrange,
+                             const float *wpacked, const float *bias, const float *freqs, int64_t S, int64_t frame0, int64_t F,
+                             int64_t h, int64_t w, int64_t C, float *out, void *stream) {
+    if (!fnet || !dmaps || !zrange || !wpacked || !bias || !freqs || !out || ((uintptr_t)wpacked & 15)) return BT_EINVAL;
+    if (S < 1 || F < 0 || frame0 < 0 || frame0 > S || F > S - frame0 || h < 2 || w < 2 || C < 1 || sf < 0 || sc < 0 || sy < 0 || sx < 0)
+        return BT_EINVAL;
+    if (C != BT_WINDOW_C || S > bt::kI31 || h > bt::kI31 || w > bt::kI31 || (__int128)S * C * h * w > bt::kI31) return BT_EUNSUPPORTED;
+    if (F == 0) return BT_OK;
+    if (sf > bt::kI31 || sc > bt::kI31 || sy > bt::kI31 || sx > bt::kI31
+        || (__int128)(F - 1) * sf + (__int128)(C - 1) * sc + (__int128)(h - 1) * sy + (__int128)(w - 1) * sx > bt::kI31) return BT_EUNSUPPORTED;
+    const long long tiles_x = (w + bt::EC_TW - 1) / bt::EC_TW, tiles_y = (h + bt::EC_TH - 1) / bt::EC_TH;
+    if (F > 65535) return BT_EUNSUPPORTED;                       // the grid's second dimension
+    hipLaunchKernelGGL(bt::k_embed_conv, dim3((unsigned)(tiles_x * tiles_y), (unsigned)F), dim3(bt::EC_THREADS), 0, (hipStream_t)stream,
+                       fnet, (long long)sf, (long long)sc, (long long)sy, (long long)sx, dmaps, zrange, wpacked, bias, freqs, (int)frame0,
+                       (int)h, (int)w, (int)tiles_x, out);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}
+
+extern "C" int bt_feat_sample(const float *fmaps, int64_t S, int64_t C, int64_t h, int64_t w, const int32_t *frames, const float *xy,
+                              int64_t xy_stride, int64_t n, float *out, void *stream) {
+    if (!fmaps || !frames || !xy || !out || S < 1 || C < 1 || h < 1 || w < 1 || xy_stride < 2 || n < 0) return BT_EINVAL;
+    if (C != BT_WINDOW_C || S > bt::kI31 || h > bt::kI31 || w > bt::kI31 || (__int128)S * C * h * w > bt::kI31 || xy_stride > bt::kI31
+        || (__int128)n * C > bt::kI31 || (__int128)n * xy_stride > bt::kI31) return BT_EUNSUPPORTED;
+    if (n == 0) return BT_OK;
+    hipLaunchKernelGGL(bt::k_feat_sample, dim3((unsigned)(n < (1 << 20) ? n : (1 << 20))), dim3(bt::FS_THREADS), 0, (hipStream_t)stream,
+                       fmaps, (int)S, (int)h, (int)w, frames, xy, (long long)xy_stride, (long long)n, out);
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}

@@ -8,7 +8,11 @@
   batrack_amd.frontend.update_former.forward          the update transformers: attention without the score matrix
   batrack_amd.frontend.update_former.attention        fused float32 attention over strided sequences
   batrack_amd.frontend.update_former.install          make the reference's UpdateFormer use it
-  batrack_amd.frontend.observe.window_observations   tracker output -> the BA's targets and weights
+  batrack_amd.frontend.tracker.forward                the tracker's window loop: depth range, window depth, 3-D feature maps, track features
+  batrack_amd.frontend.tracker.embed_conv             `embedConv` with the Fourier embedding of (x, y, z) computed in the kernel
+  batrack_amd.frontend.tracker.sample_features        each new track's features from its own frame
+  batrack_amd.frontend.tracker.install                make the reference's MDTracker use `forward`
+  batrack_amd.frontend.observe.window_observations  tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning
   batrack_amd.frontend.patches.generate_patches      patch selection, depth initialisation and colours of a new frame
   batrack_amd.frontend.patches.image_gradient        the pooled gradient-magnitude map it ranks by
