@@ -298,7 +298,8 @@ static StepArgs make_args(const bt_plan *pl, const bt_ba_args *a, void *ws) {
     s.packed = reinterpret_cast<double *>(w + L.packed); s.qw = reinterpret_cast<float2 *>(w + L.qw);
     s.lfac = reinterpret_cast<float *>(w + L.lfac);
     s.linv = reinterpret_cast<float *>(w + L.linv); s.zvec = reinterpret_cast<float *>(w + L.zvec);
-    s.dx = reinterpret_cast<float *>(w + L.dx); s.dx0 = reinterpret_cast<float *>(w + L.dx0); s.status = reinterpret_cast<int *>(w + L.status);
+    s.dx = reinterpret_cast<float *>(w + L.dx); s.dx0 = reinterpret_cast<float *>(w + L.dx0);
+    s.dxg = reinterpret_cast<unsigned long long *>(w + L.dxg); s.status = reinterpret_cast<int *>(w + L.status);
     s.spart = reinterpret_cast<double *>(w + L.spart);
     s.esave = reinterpret_cast<double *>(w + L.esave);
     static const int dbg = std::getenv("BT_DEBUG_MODE") ? std::atoi(std::getenv("BT_DEBUG_MODE")) : 0;
@@ -813,7 +814,7 @@ int bt_ba_step(const bt_plan *pl, const bt_ba_args *a, void *ws, void *stream) {
     const bool copy_poses = so && a->poses_out && a->poses_out != a->poses;
     bool fused = false;              // (structure-only steps on the k_tile path are one launch)
     int r = launch_reduce(pl->dev, s, so, st, nullptr, nullptr, so ? (copy_poses ? 1 : 0) : -1, &fused);
-    if (r == BT_OK && !fused) r = launch_solve_update(pl->dev, s, so, copy_poses, st);
+    if (r == BT_OK && !fused) r = launch_solve_update(pl->dev, s, so, copy_poses, st, nullptr, nullptr, true);
     return r;
 }
 
@@ -830,7 +831,7 @@ int bt_ba_step_timed(const bt_plan *pl, const bt_ba_args *a, void *ws, void *str
     const bool copy_poses = so && a->poses_out && a->poses_out != a->poses;
     unsigned ran = 0;
     int r = launch_reduce(pl->dev, s, so, st, ev, &ran);
-    if (r == BT_OK) r = launch_solve_update(pl->dev, s, so, copy_poses, st, ev, &ran);
+    if (r == BT_OK) r = launch_solve_update(pl->dev, s, so, copy_poses, st, ev, &ran, true);
     if (r == BT_OK && hipStreamSynchronize(st) != hipSuccess) r = BT_EHIP;
     for (int k = 0; k < 6; ++k) {
         ms[k] = 0.0f;                                  // a kernel that was not launched (structure-only steps skip two) reads 0
@@ -947,9 +948,12 @@ float *bt_ba_dx(const bt_plan *pl, void *ws) {
 int bt_ba_status(const bt_plan *pl, void *ws, void *stream, int32_t *status) {
     if (!pl || !ws || !status) return BT_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMemcpyAsync(status, static_cast<char *>(ws) + pl->ws.status, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
+    int32_t w[3] = {0, 0, 0};             // (the solver's word, the exchange's, the fused update's hand-off time-out)
+    if (hipMemcpyAsync(w, static_cast<char *>(ws) + pl->ws.status, sizeof(w), hipMemcpyDeviceToHost, st) != hipSuccess)
         return BT_EHIP;
-    return hipStreamSynchronize(st) == hipSuccess ? BT_OK : BT_EHIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return BT_EHIP;
+    *status = w[kStatusHandoff] != 0 ? w[kStatusHandoff] : w[0];
+    return BT_OK;
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@ struct StepArgs {
     double *packed;               // the non-zero blocks of [S | y] in factor order (multi-GPU exchange buffer)
     float2 *qw;
     float *lfac, *linv, *zvec, *dx, *dx0;
+    unsigned long long *dxg;      // [D] granules {float dx, uint32 tag}: dX as the solver of a fused solve + update launch publishes it (ba_solve_update.hpp)
     float *pairgeo;               // [pairs][kPairGeomFloats]: relative pose of every camera pair, left by k_tile for k_pair_finalize
     int *status;
     double *spart;                // [tiles][ntl * 256 + max_rows16]: per-tile Schur products of k_etile when the plan's sp_ok (else unused)
@@ -51,12 +52,18 @@ void launch_pick(const Pick &p, unsigned grid, hipStream_t st, const hipEvent_t 
 Pick pick_tile(const PlanDev &pd, bool so, bool fused, bool prof);       // ba_tile.hip
 Pick pick_update(const PlanDev &pd, bool so);                            // ba_tile.hip
 Pick pick_solver(const PlanDev &pd, bool prof);                          // ba_solve.hip
+Pick pick_solve_update(const PlanDev &pd);                               // ba_solve_update.hpp (fn == nullptr: the route launches solver and update apart)
 
 // LDS of k_tile with per-edge numbers of rsz bytes and of the LDS-resident solvers: what plan_route weighs against kLdsBudget
 size_t tile_lds_bytes_r(const PlanDev &pd, bool so, size_t rsz, size_t kTileWaves);
 size_t solve_lds_bytes(const PlanDev &pd, size_t elem);
 size_t solve_fused_lds_bytes(const PlanDev &pd, int nthreads);
 size_t solve_pipe_lds_bytes(const PlanDev &pd);
+// LDS of an update workgroup of the fused solve + update launch with `wgs` update workgroups, per-edge numbers of rsz bytes
+size_t solve_update_lds_bytes(const PlanDev &pd, int wgs, size_t rsz);
+// update workgroups of that launch (CU count - 1, capped by the work and by BT_FORCE updwg=N) and the tiles each of them holds
+int solve_update_workgroups(const PlanDev &pd);
+inline int solve_update_tiles_per_wg(const PlanDev &pd, int wgs) { return wgs > 0 ? (pd.T + wgs - 1) / wgs : 0; }
 // 12 waves: enough helper threads for one round of update rows on banded systems, and a 170-register budget per thread so
 // that a whole 6x6 operand block can be in flight from LDS
 constexpr int kSolveThreads = 768;
@@ -83,6 +90,8 @@ int launch_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st,
 int launch_pair_finalize(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 // the route's block-sparse solver with the refinement passes of a float32 factor (ba_solve.hip); ev: event pair or nullptr
 int launch_solve(const PlanDev &pd, const StepArgs &a, hipStream_t st, const hipEvent_t *ev);
+// solver and the step's last kernel in ONE launch (routes with Route::fuse_update; ba_solve_update.hpp); ev: the solver's event pair or nullptr
+int launch_solve_update_fused(const PlanDev &pd, const StepArgs &a, hipStream_t st, const hipEvent_t *ev);
 // dense [S | y] <-> its non-zero blocks in factor order (bt_ba_pack / bt_ba_unpack; ba_xchg.hip)
 int launch_pack(const PlanDev &pd, const StepArgs &a, bool unpack, hipStream_t st);
 // one-shot peer-write exchange of the packed [S | y] (ba_xchg.hip: k_xchg_push / k_xchg_pull)
@@ -90,7 +99,11 @@ constexpr int kMaxRanks = 16;
 size_t xchg_bytes(const PlanDev &pd, int world);
 int launch_xchg_push(const PlanDev &pd, const StepArgs &a, void *const *bufs, int world, int rank, long long epoch, hipStream_t st);
 int launch_xchg_pull(const PlanDev &pd, const StepArgs &a, void *own, int world, long long epoch, hipStream_t st);
-int launch_solve_update(const PlanDev &pd, const StepArgs &a, bool so, bool copy_poses, hipStream_t st, hipEvent_t *ev = nullptr, unsigned *ran = nullptr);
+// after_reduce: the caller has launched launch_reduce in the same call, so k_pair_finalize has cleared the tags of the dX granules
+// and the route may fuse solver and update; this half on its own (bt_ba_solve_update: the multi-GPU phases, tests that solve
+// one reduced system several times) launches the two kernels apart, as it always has
+int launch_solve_update(const PlanDev &pd, const StepArgs &a, bool so, bool copy_poses, hipStream_t st, hipEvent_t *ev = nullptr, unsigned *ran = nullptr,
+                        bool after_reduce = false);
 // tracks seen by more than 64 free cameras sit in no tile (ba_loose.hip): their part of the reduce phase / of the last kernel
 int launch_loose_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st);
 int launch_loose_update(const PlanDev &pd, const StepArgs &a, hipStream_t st);

@@ -74,6 +74,10 @@ __global__ __launch_bounds__(256) void k_pair_finalize(PlanDev pd, StepArgs a, i
         int *arr = reinterpret_cast<int *>(a.priv + priv_copy_doubles((size_t)pd.D, (size_t)pd.P));
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kPrivArrive; i += pair_blocks * blockDim.x) if (arr[i] != 0) arr[i] = 0;
     }
+    // the tags of the dX granules, and the hand-off's time-out word: cleared for the fused solve + update launch behind this
+    // kernel (ba_solve_update.hpp), whose consumers take a granule only with this step's tag on it
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < pd.D; i += pair_blocks * blockDim.x) a.dxg[i] = 0ull;
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.status[kStatusHandoff] = 0;
     const bool live = p < pd.P;
     int ia = -1, ib = -1;
     if (live) {

@@ -52,6 +52,8 @@ const Force &force() {
             else if (tok == "order=natural") r.natural_order = 1; else if (tok == "prec=f32") r.f32_edges = 1;
             else if (tok == "wide=0") r.tile_wide = 0; else if (tok == "wide=1") r.tile_wide = 1;
             else if (tok == "plan=host") r.host_plan = 1; else if (tok == "wpt=0") r.wpt_off = 1;
+            else if (tok == "upd=split") r.upd_split = 1;
+            else if (tok.rfind("updwg=", 0) == 0 && std::atoi(tok.c_str() + 6) > 0) r.upd_wgs = std::atoi(tok.c_str() + 6);
             else if (!tok.empty()) std::fprintf(stderr, "batrack: unknown BT_FORCE token '%s'\n", tok.c_str());
         }
         return r;
@@ -109,6 +111,7 @@ static void layout_workspace(bt_plan *pl) {
     w.dx = off;       off = align_up(off + D * sizeof(float) + 64, 256);
     w.dx0 = off;      off = align_up(off + D * sizeof(float) + 64, 256);     // first solution of a refined solve (float32-factor systems)
     w.status = off;   off = align_up(off + kStatusBytes, 256);
+    w.dxg = off;      off = align_up(off + D * sizeof(unsigned long long), 256);   // dX as tagged granules (fused solve + update launch)
     w.spart = off;
     if (pl->dev.sp_ok) off = align_up(off + (size_t)I.tiles * sp_tile_doubles(pl->dev.max_rows16, pl->dev.max_tile_pairs) * sizeof(double), 256);
     w.esave = off;                                                 // k_etile -> k_etile_upd: the tiles' E, [tile][max_rows16][1 << et_lgts]

@@ -83,6 +83,8 @@ struct Route {
     int prec;                     // bytes of the per-edge maths (bt_plan_edge_precision): 8 float64, 6 mixed (k_stream, k_edge2), 4 float32
     int wide;                     // kTile with float32 maths only: k_tile / k_update run 16 waves per tile instead of 8
     int solver;
+    int fuse_update;              // pose+structure steps run the solver and the step's last kernel in one launch (ba_solve_update.hpp)
+    int upd_wgs;                  // ... with this many update workgroups behind the solver's
 };
 
 // Device-side view: raw pointers into one device allocation + sizes.
@@ -138,15 +140,17 @@ struct PlanDev {
     Route route;               // set by configure_kernels (host side only: no kernel reads it)
 };
 
-// Bytes of the status block at WsLayout::status: int 0 the solver status, 1 the exchange time-out, 4.. profiling counters, 200 / 201
+// Bytes of the status block at WsLayout::status: int 0 the solver status, 1 the exchange time-out, 2 the fused update's hand-off
+// time-out (BT_SOLVE_HANDOFF_TIMEOUT, cleared by k_pair_finalize every step), 4.. profiling counters, 200 / 201
 // the dense solver's flags, 210 the refinement's flag (ba_solve.hip, ba_dense.hip).  Cleared by bt_ba_workspace_init.
 constexpr size_t kStatusBytes = 1024;
+constexpr int kStatusHandoff = 2;
 
 // Byte offsets of the regions inside the caller's workspace.
 struct WsLayout {
     size_t sys, pairacc, zero_bytes;   // [sys, sys+zero_bytes): the accumulators; zero after bt_ba_workspace_init and after every completed
                                        // step (the kernels that consume them clear them; the reduce does not)
-    size_t packed, pairgeo, qw, lfac, linv, zvec, dx, dx0, status, spart, esave, total;
+    size_t packed, pairgeo, qw, lfac, linv, zvec, dx, dx0, dxg, status, spart, esave, total;
     size_t priv;                       // inside the cleared region: [kPrivY][D] then [kPrivP][pairs][kPairAccStride] doubles; 0 = none
 };
 
@@ -251,10 +255,14 @@ namespace bt {
 //   wide=0 | wide=1                                k_tile's 8 / 16 waves per tile
 //   plan=host                                      no device-side planner
 //   wpt=0                                          no wave-per-tile kernels (= bt_config_wave_per_tile_kernels(0))
+//   upd=split                                      solver and k_update as two launches where the route would fuse them (A/B, tests)
+//   updwg=N                                        at most N update workgroups in the fused launch, so that a small graph puts
+//                                                  several tiles on one workgroup (test hook only)
 struct Force {
     int kernel = -1;        // -1 the plan's own choice, 0 k_tile, 1 k_stream, 2 k_edge2, 3 k_etile
     int solver = -1;        // -1 default, 0 k_solve_fused (barrier per level), 1 k_solve_lds<double>, 2 k_solve_lds<float>, 3 k_solve_global
     int natural_order = 0, f32_edges = 0, tile_wide = -1, host_plan = 0, wpt_off = 0;
+    int upd_split = 0, upd_wgs = 0;     // upd=split; updwg=N (0: no cap)
 };
 const Force &force();
 // BT_PLAN_PROF: time per planner phase on stderr (measurement)

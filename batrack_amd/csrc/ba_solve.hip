@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_kernels.hpp"
+#include "ba_update.hpp"
 #include "ba_wave.hpp"
 
 namespace bt {
@@ -343,8 +344,10 @@ __device__ __forceinline__ void apply_update_row(T *Lw, const unsigned short *tr
     if (PROF) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const long long tn = clock64(); pf[9] += tn - *tcp; *tcp = tn; }
 }
 
-template <typename T, bool PROF>
-__global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
+// (the three LDS solvers are device functions so that the fused solve + update launch can run them in its first workgroup —
+//  ba_solve_update.hpp; PUB: dX also goes out as tagged granules, at the one point where it is final.  The kernels follow each.)
+template <typename T, bool PROF, bool PUB>
+__device__ __forceinline__ void solve_lds_body(const PlanDev &pd, const StepArgs &a) {
     if (sizeof(T) == 4 && a.status[kRefineDone] != 0) return;       // (the double factor solves once: no refinement, no flag)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int flags[2];
@@ -623,7 +626,11 @@ __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
         status = BT_SOLVE_RETRIED;
     }
     __syncthreads();
-    for (int i = tid; i < D; i += nth) a.dx[6 * pd.perm[i / 6] + i % 6] = (float)zt[i];
+    for (int i = tid; i < D; i += nth) {
+        const int k = 6 * pd.perm[i / 6] + i % 6;
+        a.dx[k] = (float)zt[i];
+        if (PUB) dx_publish(a, k, (float)zt[i]);
+    }
     if (tid == 0) a.status[0] = status;
     BT_PF(8);
     if (PROF && lane == 0 && (wave == 0 || wave == 2)) {        // measurement only: phase cycle counts of a critical and a helper wave
@@ -632,6 +639,9 @@ __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) {
     }
 #undef BT_PF
 }
+
+template <typename T, bool PROF>
+__global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) { solve_lds_body<T, PROF, false>(pd, a); }
 
 // ------------------------------------------------------------------ k_solve_fused
 // The LDS-resident factorisation with ONE phase and one barrier per level (levels of at most
@@ -858,8 +868,8 @@ size_t solve_fused_lds_bytes(const PlanDev &pd, int) {
 
 constexpr int kFusedCols = 2;     // columns per level k_solve_fused handles (two-ended chains); wider levels use k_solve_lds
 
-template <bool PROF>
-__global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) {
+template <bool PROF, bool PUB>
+__device__ __forceinline__ void solve_fused_body(const PlanDev &pd, const StepArgs &a) {
     typedef double T;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int flags[2];
@@ -1062,7 +1072,11 @@ __global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) {
         status = BT_SOLVE_RETRIED;
     }
     __syncthreads();
-    for (int i = tid; i < D; i += nth) a.dx[6 * pd.perm[i / 6] + i % 6] = (float)zt[i];
+    for (int i = tid; i < D; i += nth) {
+        const int k = 6 * pd.perm[i / 6] + i % 6;
+        a.dx[k] = (float)zt[i];
+        if (PUB) dx_publish(a, k, (float)zt[i]);
+    }
     if (tid == 0) a.status[0] = status;
     if (PROF && lane == 0) {        // measurement only: per-wave busy cycles (columns, lazy work) and the stage boundaries
         long long *o = reinterpret_cast<long long *>(a.status + 4) + 40 + wave * 2;
@@ -1075,6 +1089,9 @@ __global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) {
     }
 #undef BT_SUB
 }
+
+template <bool PROF>
+__global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) { solve_fused_body<PROF, false>(pd, a); }
 
 // ------------------------------------------------------------------ k_solve_pipe
 // k_solve_fused without the per-level workgroup barrier.  Waves have fixed roles and walk the levels at
@@ -1104,8 +1121,8 @@ __device__ __forceinline__ void wait_ge(int *flag, int target) {
     while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
 }
 
-template <bool PROF>
-__global__ __launch_bounds__(768) void k_solve_pipe(PlanDev pd, StepArgs a) {
+template <bool PROF, bool PUB>
+__device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArgs &a) {
     typedef double T;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int flags[2];
@@ -1128,7 +1145,12 @@ __global__ __launch_bounds__(768) void k_solve_pipe(PlanDev pd, StepArgs a) {
         const double lm = attempt == 0 ? 1e-4 : 1e-3;
         if (tid < 2) { flags[tid] = 0; lready[tid] = 0; colready[tid] = 0; }
         if (tid == 2) hcnt = 0;
-        for (int i = tid; i < pd.fz_nlazy; i += nth)          // one 8-byte word per triple: src1, src2, dst | shared << 15
+        int nlazy = pd.fz_nlazy;
+        // (inside k_solve_update the copy loop's trip count, hoisted out of the attempt loop, was the one value the register
+        //  allocator spilled: 8 bytes of scratch per lane that k_solve_pipe alone does not have, 0 with the value opaque here and
+        //  formed per attempt — compiler figures in profiles/r22_solve_update.txt.  k_solve_pipe itself compiles as before.)
+        if (PUB) asm volatile("" : "+s"(nlazy));
+        for (int i = tid; i < nlazy; i += nth)                // one 8-byte word per triple: src1, src2, dst | shared << 15
             reinterpret_cast<ushort4 *>(lazy)[i] = make_ushort4((unsigned short)pd.fz_lazy[3 * i], (unsigned short)pd.fz_lazy[3 * i + 1],
                                                                (unsigned short)pd.fz_lazy[3 * i + 2], 0);
         lds_load_system_dma<T>(pd, a, Lw, z, bsrc, trl, &ntr, col_ptr, lm, attempt == 0, true, tid, nth);
@@ -1323,7 +1345,11 @@ __global__ __launch_bounds__(768) void k_solve_pipe(PlanDev pd, StepArgs a) {
         status = BT_SOLVE_RETRIED;
     }
     __syncthreads();
-    for (int i = tid; i < D; i += nth) a.dx[6 * pd.perm[i / 6] + i % 6] = (float)zt[i];
+    for (int i = tid; i < D; i += nth) {
+        const int k = 6 * pd.perm[i / 6] + i % 6;
+        a.dx[k] = (float)zt[i];
+        if (PUB) dx_publish(a, k, (float)zt[i]);
+    }
     if (tid == 0) a.status[0] = status;
     if (PROF && lane == 0) {        // measurement only: per-wave (waiting, working) cycles of the sweep
         long long *o = reinterpret_cast<long long *>(a.status + 4) + 40 + wave * 2;
@@ -1336,6 +1362,9 @@ __global__ __launch_bounds__(768) void k_solve_pipe(PlanDev pd, StepArgs a) {
     }
 #undef BT_TW
 }
+
+template <bool PROF>
+__global__ __launch_bounds__(768) void k_solve_pipe(PlanDev pd, StepArgs a) { solve_pipe_body<PROF, false>(pd, a); }
 
 // ------------------------------------------------------------------ refinement of float32-factor solves
 // Systems whose factor does not fit LDS as double are factored in float32 (k_solve_lds<float>, k_solve_global): dX is then
@@ -1421,3 +1450,7 @@ int launch_solve(const PlanDev &pd, const StepArgs &a, hipStream_t st, const hip
 }
 
 }  // namespace bt
+
+// The fused solve + update launch runs the solver bodies above in its first workgroup: device functions do not link across
+// objects, so its header is part of this translation unit (and of no other).
+#include "ba_solve_update.hpp"

@@ -57,12 +57,26 @@ static Route plan_route(const PlanDev &pd) {
     return r;
 }
 
+// Solver and the step's last kernel in one launch (k_solve_update, ba_solve_update.hpp): the 8-wave k_tile routes whose solver
+// is one of the double LDS ones, on plans with camera pairs (k_pair_finalize, which every such step launches, clears the
+// granules' tags), where the tiles an update workgroup holds fit its LDS.  BT_FORCE upd=split: two launches, as every other route.
+static void plan_fuse_update(PlanDev &pd) {
+    Route &r = pd.route;
+    r.fuse_update = 0; r.upd_wgs = 0;
+    const bool solver_ok = r.solver == Route::kSolvePipe || r.solver == Route::kSolveFused || r.solver == Route::kSolveLds;
+    if (force().upd_split || r.kernel != Route::kTile || r.wide || !solver_ok || pd.P <= 0 || pd.T <= 0 || pd.n <= 0) return;
+    const int w = solve_update_workgroups(pd);
+    if (w <= 0 || solve_update_lds_bytes(pd, w, r.prec == 8 ? sizeof(double) : sizeof(float)) > kLdsBudget) return;
+    r.fuse_update = 1; r.upd_wgs = w;
+}
+
 int configure_kernels(PlanDev &pd) {
     pd.route = plan_route(pd);
+    plan_fuse_update(pd);
     // the LDS limits of everything the route can launch, raised here at upload (never first inside a captured step); the
     // launchers of the other kernel families raise their own
     for (int v = 0; v < 8; ++v)
-        for (const Pick &p : {pick_tile(pd, v & 1, v & 2, v & 4), pick_solver(pd, v & 4), pick_update(pd, v & 1)}) {
+        for (const Pick &p : {pick_tile(pd, v & 1, v & 2, v & 4), pick_solver(pd, v & 4), pick_update(pd, v & 1), pick_solve_update(pd)}) {
             if (!p.fn) continue;
             if (p.lds > kLdsBudget) return BT_EUNSUPPORTED;
             if (!p.lim->ensure(p.fn, p.lds, pd.dev_id)) return BT_EHIP;
@@ -104,8 +118,17 @@ int launch_reduce(const PlanDev &pd, const StepArgs &a, bool so, hipStream_t st,
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }
 
-int launch_solve_update(const PlanDev &pd, const StepArgs &a, bool so, bool copy_poses, hipStream_t st, hipEvent_t *ev, unsigned *ran) {
+int launch_solve_update(const PlanDev &pd, const StepArgs &a, bool so, bool copy_poses, hipStream_t st, hipEvent_t *ev, unsigned *ran, bool after_reduce) {
     const Route &r = pd.route;
+    if (!so && r.fuse_update && after_reduce && a.dbg == 0) {
+        // one launch: the solver's workgroup and the update workgroups behind it (timed: under the solver's event pair; the
+        // update's `ran` bit stays clear)
+        if (ran) *ran |= 1u << 3;
+        int rc = launch_solve_update_fused(pd, a, st, ev ? ev + 6 : nullptr);
+        if (rc == BT_OK) rc = launch_loose_update(pd, a, st);
+        if (rc != BT_OK) return rc;
+        return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+    }
     if (!so) {
         if (ran) *ran |= 1u << 3;
         const int rc = r.solver == Route::kSolveDense ? launch_solve_dense(pd, a, st, ev ? ev[6] : nullptr, ev ? ev[7] : nullptr)

@@ -418,8 +418,7 @@ __global__ __launch_bounds__(WIDE ? 1024 : 512, WIDE ? 2 : (sizeof(R) == 8 ? BT_
 //                            a track (the tile blocks write those).  Followed by one thread per buffer pose:
 //                            Exp(dX) * G in double (groups.py:153-156).
 //   [first_zero_block, ..)   [S | y] has been consumed by the solver: cleared for the next step's accumulation.
-constexpr int kUpdThreads = 512;
-constexpr int kUpdGeo = 28;          // floats per pair in LDS: the 20 of kPairGeomFloats, delta (6), padding to 16 bytes
+constexpr int kUpdThreads = 512;     // (kUpdGeo, the floats per pair in LDS: ba_update.hpp)
 
 // THREADS: 512, or 1024 for the few-tiles / many-slots graphs that k_tile runs 16 waves wide (tile_wide): the tile blocks'
 // slot loop, which is all the time there is on 40 tiles, halves.

@@ -8,6 +8,21 @@
 
 namespace bt {
 
+constexpr int kUpdGeo = 28;          // floats per pair in the LDS of an update's tile block: the 20 of kPairGeomFloats, delta (6), padding to 16 bytes
+
+// dX as tagged granules (StepArgs::dxg; the fused solve + update launch, ba_solve_update.hpp): one 8-byte word per component,
+// {float dx, uint32 tag}, written and read whole by relaxed agent-scope atomics.  The tag travels with the value, so the
+// hand-off needs no fence and no separate flag; k_pair_finalize clears the tags every step, the solver publishes tag 1.
+__device__ __forceinline__ void dx_publish(const StepArgs &a, int k, float v) {
+    __hip_atomic_store(a.dxg + k, (unsigned long long)__float_as_uint(v) | (1ull << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// one look at granule k: true, and its value, once it carries this step's tag
+__device__ __forceinline__ bool dx_peek(const StepArgs &a, int k, float &v) {
+    const unsigned long long g = __hip_atomic_load(a.dxg + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v = __uint_as_float((unsigned)g);
+    return (unsigned)(g >> 32) == 1u;
+}
+
 __device__ inline void retract_pose(const float *pin, const float *xi, float *pout) {
     // poses' = Exp(xi) * G  (groups.py:153-156; so3.h:153-190; se3.h:134-142), in double
     const double tau[3] = {xi[0], xi[1], xi[2]}, phi[3] = {xi[3], xi[4], xi[5]};

@@ -53,7 +53,9 @@ enum { BT_LOSS_TRIVIAL = 0, BT_LOSS_HUBER = 1, BT_LOSS_CAUCHY = 2 };   /* ba.py:
 
 /* status word written by the solver (bt_ba_status): */
 enum { BT_SOLVE_OK = 0, BT_SOLVE_CHOL_FAILED = 1,   /* dX = 0, ba.py:9-13            */
-       BT_SOLVE_RETRIED = 2 };                      /* NaN -> lm = 1e-3, ba.py:324-325 */
+       BT_SOLVE_RETRIED = 2,                        /* NaN -> lm = 1e-3, ba.py:324-325 */
+       BT_SOLVE_HANDOFF_TIMEOUT = 3 };              /* the step's update waited ~100 ms for dX inside the fused solve +
+                                                       update launch and gave up: its outputs are those of dX = 0 */
 
 typedef struct {
     int64_t E;            /* edges assembled by this plan (owned tracks)          */
