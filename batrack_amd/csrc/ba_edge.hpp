@@ -1,7 +1,8 @@
 // ba_edge.hpp — device helpers shared by the tile kernels (ba_tile.hip) and the wave-per-tile
 // streaming kernels (ba_stream.hip): relative pose of a camera pair, the per-edge reprojection /
-// Jacobian / robust-weight arithmetic (projective_ops.py:54-100, ba.py:228-266), and the wave-wide
-// reduce-scatter of the 27 per-pair products.
+// Jacobian / robust-weight arithmetic (projective_ops.py:54-100, ba.py:228-266), the wave-wide
+// reduce-scatter of the 27 per-pair products, and what every route's depth back-substitution (ba.py:328) is made of:
+// the pair's delta = dX_j - Ad(G_ij) dX_i (pair_delta), an edge's term Jz^T W Jj delta (edge_term), the 16-byte loads of a pair.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,46 @@ __device__ inline void pair_geometry(const float *poses, const float *intr, int 
     else { g[12] = (T)1 / (T)intr[4*i]; g[13] = (T)1 / (T)intr[4*i + 1]; }
     g[14] = intr[4*i + 2]; g[15] = intr[4*i + 3];
     for (int c = 0; c < 4; ++c) g[16 + c] = intr[4*j + c];
+}
+
+// N numbers (a multiple of 16 bytes' worth; the first N of g) from 16-byte aligned global memory or LDS, 16 bytes per access
+template <int N, typename T, int M>
+__device__ __forceinline__ void load16(const T *src, T (&g)[M]) {
+    constexpr int W = 16 / sizeof(T);
+    static_assert(N % W == 0 && N <= M, "whole 16-byte words");
+    typedef T V __attribute__((ext_vector_type(W)));
+    const V *s = reinterpret_cast<const V *>(src);
+#pragma unroll
+    for (int c = 0; c < N / W; ++c) {
+        const V t = s[c];
+#pragma unroll
+        for (int k = 0; k < W; ++k) g[W * c + k] = t[k];
+    }
+}
+// the 20 numbers of pair gp as the step's Jacobian kernel left them in the workspace (StepArgs::pairgeo holds T's)
+template <typename T, int M>
+__device__ __forceinline__ void load_pairgeo(const float *pairgeo, int gp, T (&g)[M]) {
+    load16<kPairGeomFloats>(reinterpret_cast<const T *>(pairgeo) + (size_t)gp * kPairGeomFloats, g);
+}
+
+// What dX moves a camera pair by, as seen from its target camera: delta = dX_j - Ad(G_ij) dX_i with
+// Ad(Gij) (tau, phi) = (R tau + t x (R phi), R phi) (se3.h:58-67; Ji = -Jj Ad, projective_ops.py:96).  g: the pair's R (g[0..8])
+// and t (g[9..11]); dx: dX by free camera, in global memory or LDS; ia / ib < 0: a fixed pose, which does not move.
+template <typename T>
+__device__ __forceinline__ void pair_delta(const T *g, const float *dx, int ia, int ib, T (&dl)[6]) {
+    T xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
+    if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = dx[6 * ia + c];
+    if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = dx[6 * ib + c];
+    T Rt[3], Rp[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        Rt[r] = g[3*r] * xi[0] + g[3*r + 1] * xi[1] + g[3*r + 2] * xi[2];
+        Rp[r] = g[3*r] * xi[3] + g[3*r + 1] * xi[4] + g[3*r + 2] * xi[5];
+    }
+    dl[0] = xj[0] - (Rt[0] + g[10] * Rp[2] - g[11] * Rp[1]);
+    dl[1] = xj[1] - (Rt[1] + g[11] * Rp[0] - g[9]  * Rp[2]);
+    dl[2] = xj[2] - (Rt[2] + g[9]  * Rp[1] - g[10] * Rp[0]);
+    dl[3] = xj[3] - Rp[0]; dl[4] = xj[4] - Rp[1]; dl[5] = xj[5] - Rp[2];
 }
 
 // ------------------------------------------------------------------ per-edge math
@@ -131,6 +172,15 @@ __device__ __forceinline__ void edge_eval(const T *g, T x, T y, T d, T tu, T tv,
     o.W0 = vld * (w0 * robust_weight(r0, a.loss));
     o.W1 = vld * (w1 * robust_weight(r1, a.loss));
     o.r0 = vld * r0; o.r1 = vld * r1;
+}
+
+// An edge's term of the depth back-substitution (ba.py:328), Jz^T W Jj delta: the two rows of Jj (the ten entries of q)
+// against the pair's delta (pair_delta), weighted by wj0 = W0 jz0 and wj1 = W1 jz1.
+template <typename T>
+__device__ __forceinline__ T edge_term(const EdgeQT<T> &q, T wj0, T wj1, const T *dl) {
+    const T d0 = q.a0 * dl[0] + q.a2 * dl[2] + q.a3 * dl[3] + q.a4 * dl[4] + q.a5 * dl[5];
+    const T d1 = q.b1 * dl[1] + q.b2 * dl[2] + q.b3 * dl[3] + q.b4 * dl[4] + q.b5 * dl[5];
+    return wj0 * d0 + wj1 * d1;
 }
 
 // MIXED precision (the wave-per-tile kernels of large graphs, round 4): the reprojection and the residual in float64 on the

@@ -754,7 +754,6 @@ __global__ __launch_bounds__(512, 1) void k_edge2(PlanDev pd, StepArgs a, int ti
     }
     BT_PROBE_E2_END(gw, (int)(gridDim.x * nwv));
 }
-#undef BT_DPPF
 
 static size_t lds_bytes(const PlanDev &pd, int lgs, bool with_lmbda_trk) {
     const size_t mtp = (size_t)(pd.max_tile_pairs > 0 ? pd.max_tile_pairs : 1);

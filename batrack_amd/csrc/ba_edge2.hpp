@@ -1,11 +1,12 @@
 // ba_edge2.hpp — what the two-edges-per-lane kernels of the edge-major layout share (ba_edge2.hip: k_edge2, the pose+structure
 // reduce; ba_edge2u.hip: k_edge2u, the structure-only step and the depth back-substitution): the tile record, packed-float32
-// helpers, lane-group sums by DPP, the float64 reprojection of one edge.
+// helpers, the 2-vector form of the lane-group sums (ba_wave.hpp), the float64 reprojection of one edge.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "ba_edge.hpp"
 #include "ba_kernels.hpp"
+#include "ba_wave.hpp"
 
 namespace bt {
 namespace e2 {
@@ -54,42 +55,20 @@ template <int P> struct IC { static constexpr int value = P; };
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f2 splat(float x) { return f2{x, x}; }
 
-#define BT_DPPF(x, ctrl) __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), (ctrl), 0xf, 0xf, true))
-template <int M>
-__device__ __forceinline__ float xor_add(float x) {
-    if (M == 1) return x + BT_DPPF(x, 0xb1);
-    if (M == 2) return x + BT_DPPF(x, 0x4e);
-    if (M == 4) {
-        int t = __builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x104, 0xf, 0x5, false);
-        t = __builtin_amdgcn_update_dpp(t, (int)__float_as_uint(x), 0x114, 0xf, 0xa, false);
-        return x + __uint_as_float((unsigned)t);
-    }
-    if (M == 8) return x + BT_DPPF(x, 0x128);
-    if (M == 16) { const uint2_t r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false); return __uint_as_float(r.x) + __uint_as_float(r.y); }
-    const uint2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-// sums over the groups of 2^lg adjacent lanes, both halves of the 2-vectors (every lane of a group gets the totals)
+// sums over the groups of 2^lg adjacent lanes, both halves of the 2-vectors (every lane of a group gets the totals): the steps
+// of group_sum (ba_wave.hpp) on the halves one by one, a packed add taking no DPP operand.  (Written on lane_dpp / lane_swap
+// themselves: through group_sum on a copy of the halves, or through a per-step function, k_edge2's runtime-lgS instantiations
+// came out with other packed multiplies or another spill count.)
 template <int N>
 __device__ __forceinline__ void group_sum2(f2 (&x)[N], int lg) {
-#define BT_GS(ctrl) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x += BT_DPPF(x[i].x, ctrl); x[i].y += BT_DPPF(x[i].y, ctrl); } }
+#define BT_GS(ctrl) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x += lane_dpp<ctrl>(0.0f, x[i].x); x[i].y += lane_dpp<ctrl>(0.0f, x[i].y); } }
     if (lg > 0) BT_GS(0xb1)
     if (lg > 1) BT_GS(0x4e)
     if (lg > 2) BT_GS(0x141)
     if (lg > 3) BT_GS(0x140)
 #undef BT_GS
-    if (lg > 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x = xor_add<16>(x[i].x); x[i].y = xor_add<16>(x[i].y); } }
-    if (lg > 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x = xor_add<32>(x[i].x); x[i].y = xor_add<32>(x[i].y); } }
-}
-// sum of x over the lanes with the same (lane mod 2^lg) (lane < 2^lg then holds the total of its residue class)
-template <int N>
-__device__ __forceinline__ void stride_sum(float (&x)[N], int lg) {
-    if (lg <= 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<32>(x[i]); }
-    if (lg <= 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<16>(x[i]); }
-    if (lg <= 3) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<8>(x[i]); }
-    if (lg <= 2) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<4>(x[i]); }
-    if (lg <= 1) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<2>(x[i]); }
-    if (lg <= 0) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<1>(x[i]); }
+    if (lg > 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x = lane_swap16(x[i].x); x[i].y = lane_swap16(x[i].y); } }
+    if (lg > 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) { x[i].x = lane_swap32(x[i].x); x[i].y = lane_swap32(x[i].y); } }
 }
 
 // 1 / x in double from the float32 hardware seed and ONE Newton step: the seed is 1 ulp (2^-23) off, the step squares that

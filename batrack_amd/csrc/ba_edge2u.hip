@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "ba_edge2.hpp"
+#include "ba_update.hpp"
 #include "dev_cache.hpp"
 
 namespace bt {
@@ -112,30 +113,18 @@ __global__ __launch_bounds__(64, 4) void k_edge2u(PlanDev pd, StepArgs a, int ti
                 float *gu = geoU + p * kGeoU;
                 if (MODE == kUUpd) {
                     // the geometry the step's Jacobian kernel left (k_edge2: R, t rounded to float32 — the linearisation point of
-                    // S and y), delta = dX_j - Ad(G_ij) dX_i, Ad(G_ij)(tau, phi) = (R tau + t x (R phi), R phi)   (se3.h:58-67)
-                    float gg[kPairGeomFloats];
-                    const float4 *src = reinterpret_cast<const float4 *>(a.pairgeo + (size_t)gp * kPairGeomFloats);
-#pragma unroll
-                    for (int c = 0; c < kPairGeomFloats / 4; ++c) { const float4 t4 = src[c]; gg[4*c] = t4.x; gg[4*c + 1] = t4.y; gg[4*c + 2] = t4.z; gg[4*c + 3] = t4.w; }
-                    const int ia = pd.pair_i[gp] - pd.fixedp, ib = pd.pair_j[gp] - pd.fixedp;
-                    float xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-                    if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = a.dx[6 * ia + c];
-                    if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = a.dx[6 * ib + c];
-                    float Rt[3], Rp[3];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        Rt[r] = gg[3*r] * xi[0] + gg[3*r + 1] * xi[1] + gg[3*r + 2] * xi[2];
-                        Rp[r] = gg[3*r] * xi[3] + gg[3*r + 1] * xi[4] + gg[3*r + 2] * xi[5];
-                    }
+                    // S and y), delta = dX_j - Ad(G_ij) dX_i (pair_delta, ba_edge.hpp)
+                    float gg[kPairGeomFloats], dl[6];
+                    load_pairgeo(a.pairgeo, gp, gg);
+                    pair_delta(gg, a.dx, pd.pair_i[gp] - pd.fixedp, pd.pair_j[gp] - pd.fixedp, dl);
 #pragma unroll
                     for (int c = 0; c < 12; ++c) gd[c] = (double)gg[c];
 #pragma unroll
                     for (int c = 0; c < 4; ++c) gd[12 + c] = (double)gg[16 + c];
                     gu[0] = gg[9]; gu[1] = gg[10]; gu[2] = gg[11]; gu[3] = gg[16]; gu[4] = gg[17];
-                    gu[5] = xj[0] - (Rt[0] + gg[10] * Rp[2] - gg[11] * Rp[1]);
-                    gu[6] = xj[1] - (Rt[1] + gg[11] * Rp[0] - gg[9]  * Rp[2]);
-                    gu[7] = xj[2] - (Rt[2] + gg[9]  * Rp[1] - gg[10] * Rp[0]);
-                    gu[8] = xj[3] - Rp[0]; gu[9] = xj[4] - Rp[1]; gu[10] = xj[5] - Rp[2]; gu[11] = 0.0f;
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) gu[5 + c] = dl[c];
+                    gu[11] = 0.0f;
                     if (p == 0) { srcK[0] = frcp((double)gg[12]); srcK[1] = frcp((double)gg[13]); srcK[2] = (double)gg[14]; srcK[3] = (double)gg[15]; }
                 } else {
                     const int ij = pd.tile_ij[(unsigned)tile * (unsigned)mtp + (unsigned)p];
@@ -267,11 +256,8 @@ __global__ __launch_bounds__(64, 4) void k_edge2u(PlanDev pd, StepArgs a, int ti
                     const float Ca = o.x + pm + lm_v;
                     a.qw[(unsigned)rec.trk0 + (unsigned)ln] = make_float2(rcp_f32(Ca), o.y - pm * (pdisp - mono_v));
                 } else {
-                    float dd = pdisp + qw_c.x * (qw_c.y - o.x);                             // ba.py:328, :333
-                    dd = dd < 1e-3f ? 1e-3f : dd;
-                    dd = dd > 10.0f ? 10.0f : dd;
                     float *dst = a.patches_out + 3u * (unsigned)kx_c;
-                    dst[0] = px; dst[1] = py; dst[2] = dd;
+                    dst[0] = px; dst[1] = py; dst[2] = new_disp(pdisp, qw_c.x, qw_c.y, o.x);
                 }
             }
         }

@@ -28,81 +28,12 @@
 #include "dev_cache.hpp"
 #include "probe.hpp"
 #include "ba_update.hpp"
+#include "ba_wave.hpp"
 
 namespace bt {
 
 enum { kEtFull = 0, kEtSO = 1, kEtUpd = 2 };
 constexpr int kEtWaves = 8, kEtThreads = 64 * kEtWaves;
-constexpr int kEtGeoUpd = 28;        // numbers per pair in LDS for kEtUpd: geometry (20), delta (6), padding
-
-// ------------------------------------------------------------------ cross-lane sums, float and double
-template <int CTRL, int BANK = 0xf, bool BOUND = true>
-__device__ __forceinline__ float et_dpp(float old, float x) {
-    return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp((int)__float_as_uint(old), (int)__float_as_uint(x), CTRL, 0xf, BANK, BOUND));
-}
-template <int CTRL, int BANK = 0xf, bool BOUND = true>
-__device__ __forceinline__ double et_dpp(double old, double x) {
-    const unsigned long long o = (unsigned long long)__double_as_longlong(old), v = (unsigned long long)__double_as_longlong(x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)v, CTRL, 0xf, BANK, BOUND);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(v >> 32), CTRL, 0xf, BANK, BOUND);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ float et_swap16(float x) {
-    const uint2_t r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ float et_swap32(float x) {
-    const uint2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r.x) + __uint_as_float(r.y);
-}
-__device__ __forceinline__ double et_mk(unsigned lo, unsigned hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
-__device__ __forceinline__ double et_swap16(double x) {
-    const unsigned long long v = (unsigned long long)__double_as_longlong(x);
-    const uint2_t rl = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    const uint2_t rh = __builtin_amdgcn_permlane16_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
-    return et_mk(rl.x, rh.x) + et_mk(rl.y, rh.y);
-}
-__device__ __forceinline__ double et_swap32(double x) {
-    const unsigned long long v = (unsigned long long)__double_as_longlong(x);
-    const uint2_t rl = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    const uint2_t rh = __builtin_amdgcn_permlane32_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
-    return et_mk(rl.x, rh.x) + et_mk(rl.y, rh.y);
-}
-// x + (x of lane ^ M)
-template <int M, typename T>
-__device__ __forceinline__ T et_xor_add(T x) {
-    if (M == 1) return x + et_dpp<0xb1>((T)0, x);
-    if (M == 2) return x + et_dpp<0x4e>((T)0, x);
-    if (M == 4) {
-        T t = et_dpp<0x104, 0x5, false>((T)0, x);             // row_shl:4 on the banks with bit 2 clear
-        t = et_dpp<0x114, 0xa, false>(t, x);                   // row_shr:4 on the others
-        return x + t;
-    }
-    if (M == 8) return x + et_dpp<0x128>((T)0, x);
-    if (M == 16) return et_swap16(x);
-    return et_swap32(x);
-}
-// sum of x over the groups of 2^lg adjacent lanes (every lane of a group gets the total); lg is wave-uniform.  Inside a row
-// the partners are quad_perm (lane ^ 1, lane ^ 2), row_half_mirror (7 - lane of the 8) and row_mirror (15 - lane of the 16)
-template <int N, typename T>
-__device__ __forceinline__ void et_group_sum(T (&x)[N], int lg) {
-    if (lg > 0) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += et_dpp<0xb1>((T)0, x[i]); }
-    if (lg > 1) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += et_dpp<0x4e>((T)0, x[i]); }
-    if (lg > 2) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += et_dpp<0x141>((T)0, x[i]); }
-    if (lg > 3) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += et_dpp<0x140>((T)0, x[i]); }
-    if (lg > 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_swap16(x[i]); }
-    if (lg > 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_swap32(x[i]); }
-}
-// sum of x over the lanes with the same (lane mod 2^lg) (lane < 2^lg then holds the total of its residue class)
-template <int N, typename T>
-__device__ __forceinline__ void et_stride_sum(T (&x)[N], int lg) {
-    if (lg <= 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<32>(x[i]); }
-    if (lg <= 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<16>(x[i]); }
-    if (lg <= 3) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<8>(x[i]); }
-    if (lg <= 2) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<4>(x[i]); }
-    if (lg <= 1) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<2>(x[i]); }
-    if (lg <= 0) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = et_xor_add<1>(x[i]); }
-}
 
 // ------------------------------------------------------------------ k_etile
 // Grid: kEtFull pd.T workgroups; kEtSO pd.T + the blocks of update_rest; kEtUpd tile_blocks + update_rest blocks + the
@@ -127,7 +58,7 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
     BT_PROBE_ET_DECL();           // (measurement hooks: probe.hpp, tools/probes/wave_times.hpp)
     long long pf[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tc = PROF ? clock64() : 0, tn;
 #define BT_PF(i) do { if (PROF) { __builtin_amdgcn_sched_barrier(0); tn = clock64(); pf[i] += tn - tc; tc = tn; __builtin_amdgcn_sched_barrier(0); } } while (0)
-    constexpr int GS = MODE == kEtUpd ? kEtGeoUpd : kPairGeomFloats;
+    constexpr int GS = MODE == kEtUpd ? kUpdGeo : kPairGeomFloats;
     const int mtp = pd.max_tile_pairs > 0 ? pd.max_tile_pairs : 1;
     const int R16max = MODE == kEtFull ? pd.max_rows16 : 0;
     // LDS: ppart [4][26][Smax] f64 (the waves' per-pair sums; LDS float64 atomics cost ~500 cycles per wave instruction, so
@@ -202,26 +133,13 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
         const int gp = pd.tile_pairs[pd.tile_pair0[tile] + p];
         if (MODE == kEtUpd) {
             // the geometry the Jacobian kernel left in the workspace, and delta = dX_j - Ad(Gij) dX_i of the pair
-            const int ia = pd.pair_i[gp] - pd.fixedp, ib = pd.pair_j[gp] - pd.fixedp;
-            R gg[kPairGeomFloats];
-            const R2 *src = reinterpret_cast<const R2 *>(reinterpret_cast<const R *>(a.pairgeo) + (size_t)gp * kPairGeomFloats);
-#pragma unroll
-            for (int c = 0; c < kPairGeomFloats / 2; ++c) { const R2 t2 = src[c]; gg[2*c] = t2.x; gg[2*c + 1] = t2.y; }
-            R xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-            if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = a.dx[6 * ia + c];
-            if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = a.dx[6 * ib + c];
-            R Rt[3], Rp[3];                                      // Ad(Gij)(tau, phi) = (R tau + t x (R phi), R phi)   (se3.h:58-67)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                Rt[r] = gg[3*r] * xi[0] + gg[3*r + 1] * xi[1] + gg[3*r + 2] * xi[2];
-                Rp[r] = gg[3*r] * xi[3] + gg[3*r + 1] * xi[4] + gg[3*r + 2] * xi[5];
-            }
+            R gg[kPairGeomFloats], dl[6];
+            load_pairgeo(a.pairgeo, gp, gg);
+            pair_delta(gg, a.dx, pd.pair_i[gp] - pd.fixedp, pd.pair_j[gp] - pd.fixedp, dl);
 #pragma unroll
             for (int c = 0; c < kPairGeomFloats; ++c) g[c] = gg[c];
-            g[20] = xj[0] - (Rt[0] + gg[10] * Rp[2] - gg[11] * Rp[1]);
-            g[21] = xj[1] - (Rt[1] + gg[11] * Rp[0] - gg[9]  * Rp[2]);
-            g[22] = xj[2] - (Rt[2] + gg[9]  * Rp[1] - gg[10] * Rp[0]);
-            g[23] = xj[3] - Rp[0]; g[24] = xj[4] - Rp[1]; g[25] = xj[5] - Rp[2];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) g[20 + c] = dl[c];
             g[26] = (R)0; g[27] = (R)0;
         } else {
             const int ij = p == tid ? ij0 : pd.tile_ij[(size_t)tile * mtp + p];
@@ -261,11 +179,7 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
     // ---- one edge of the lane's (track, pair): its share of the track's and of the pair's sums
     auto accum = [&](const EdgeQT<R> &q, bool act) {
         if (MODE == kEtUpd) {
-            if (act) {
-                const R d0 = q.a0 * g[20] + q.a2 * g[22] + q.a3 * g[23] + q.a4 * g[24] + q.a5 * g[25];
-                const R d1 = q.b1 * g[21] + q.b2 * g[22] + q.b3 * g[23] + q.b4 * g[24] + q.b5 * g[25];
-                dacc += q.W0 * q.jz0 * d0 + q.W1 * q.jz1 * d1;
-            }
+            if (act) dacc += edge_term(q, q.W0 * q.jz0, q.W1 * q.jz1, g + 20);
         } else {
             // C, w of the track (ba.py:287,292)
             sv[0] += q.W0 * q.jz0 * q.jz0 + q.W1 * q.jz1 * q.jz1;
@@ -301,13 +215,11 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
         const bool has_trk = track < ntrk;
         if (MODE == kEtUpd) {
             R dv[1] = {dacc};
-            et_group_sum(dv, lgS);
+            group_sum(dv, lgS);
             if (lead && has_trk) {
                 const R2 qw = reinterpret_cast<const R2 *>(a.qw)[pd.tile_trk0[tile] + track];
-                float dd = (float)(pdisp + qw.x * (qw.y - dv[0]));                  // ba.py:328, :333
-                dd = dd < 1e-3f ? 1e-3f : dd;
-                dd = dd > 10.0f ? 10.0f : dd;
-                a.patches_out[3 * (size_t)patch_c] = (float)px; a.patches_out[3 * (size_t)patch_c + 1] = (float)py; a.patches_out[3 * (size_t)patch_c + 2] = dd;
+                a.patches_out[3 * (size_t)patch_c] = (float)px; a.patches_out[3 * (size_t)patch_c + 1] = (float)py;
+                a.patches_out[3 * (size_t)patch_c + 2] = new_disp<R>(pdisp, qw.x, qw.y, dv[0]);
             }
             dacc = (R)0;
         } else {
@@ -330,7 +242,7 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
                     for (int c = 0; c < 6; ++c) row[c * kLdsRowStride] = Ejacc[c];
                 }
             }
-            et_group_sum(sv, lgS);
+            group_sum(sv, lgS);
             if (lead && has_trk) {                                                    // ba.py:296-311
                 const int trk = pd.tile_trk0[tile] + track;
                 const R pm = mono_v > (R)1e-2f ? (R)1 : (R)0;                         // (the prior is float32 data: compared as such)
@@ -341,10 +253,8 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
                 if constexpr (MODE == kEtSO) {                                        // ba.py:316-317, :333
                     R2 qw2; qw2.x = Q; qw2.y = wp;
                     reinterpret_cast<R2 *>(a.qw)[trk] = qw2;                          // (for a k_update<true> behind a split step)
-                    float dd = (float)(pdisp + Q * wp);
-                    dd = dd < 1e-3f ? 1e-3f : dd;
-                    dd = dd > 10.0f ? 10.0f : dd;
-                    a.patches_out[3 * (size_t)patch_c] = (float)px; a.patches_out[3 * (size_t)patch_c + 1] = (float)py; a.patches_out[3 * (size_t)patch_c + 2] = dd;
+                    a.patches_out[3 * (size_t)patch_c] = (float)px; a.patches_out[3 * (size_t)patch_c + 1] = (float)py;
+                    a.patches_out[3 * (size_t)patch_c + 2] = new_disp<R>(pdisp, Q, wp, (R)0);
                 } else if constexpr (MODE == kEtFull) {
                     R2 qw2; qw2.x = Q; qw2.y = wp;
                     reinterpret_cast<R2 *>(a.qw)[trk] = qw2;
@@ -437,7 +347,7 @@ __global__ __launch_bounds__(kEtThreads, TWO ? 1 : 2) void k_etile(PlanDev pd, S
 
     // ---- the lanes' pair sums: over the lanes with the same pair, then lane s (< S) adds them to the workgroup's float64 sums
     const int gp_l = (!pd.sp_ok && lane < np) ? pd.tile_pairs[pd.tile_pair0[tile] + lane] : 0;       // (np <= 64: one pair per lane)
-    et_stride_sum(pa, lgS);
+    stride_sum(pa, lgS);
     BT_PF(6);
     {
         double *dst = ppart + (size_t)(wave & 3) * 26 * Smax + s;
@@ -609,17 +519,15 @@ __global__ __launch_bounds__(kEuThreads) void k_etile_upd(PlanDev pd, StepArgs a
     // over the row slices: lanes with the same track are 1 << lgts apart
     for (int m = 32; m >= (1 << lgts); m >>= 1) acc += __shfl_xor(acc, m);
     if (patch >= 0) {
-        float dd = (float)((double)pdisp + qw.x * (qw.y - acc));                  // ba.py:328, :333
-        dd = dd < 1e-3f ? 1e-3f : dd;
-        dd = dd > 10.0f ? 10.0f : dd;
-        a.patches_out[3 * (size_t)patch] = px; a.patches_out[3 * (size_t)patch + 1] = py; a.patches_out[3 * (size_t)patch + 2] = dd;
+        a.patches_out[3 * (size_t)patch] = px; a.patches_out[3 * (size_t)patch + 1] = py;
+        a.patches_out[3 * (size_t)patch + 2] = new_disp<double>((double)pdisp, qw.x, qw.y, acc);      // (the sum in double on the float32 disparity)
     }
 }
 
 // ------------------------------------------------------------------ dispatch
 static size_t etile_lds_bytes(const PlanDev &pd, int mode, size_t rsz) {
     const size_t mtp = (size_t)(pd.max_tile_pairs > 0 ? pd.max_tile_pairs : 1);
-    if (mode == kEtUpd) return mtp * kEtGeoUpd * rsz + 64;
+    if (mode == kEtUpd) return mtp * kUpdGeo * rsz + 64;
     if (mode == kEtSO) return mtp * kPairGeomFloats * rsz + 64;
     return etile_full_lds_bytes(pd.max_rows16, pd.max_tile_pairs, rsz);
 }

@@ -16,6 +16,7 @@
 
 #include "ba_edge.hpp"
 #include "ba_kernels.hpp"
+#include "ba_update.hpp"
 #include "dev_cache.hpp"
 
 namespace bt {
@@ -172,32 +173,16 @@ __global__ __launch_bounds__(kThreads) void k_loose_update(PlanDev pd, StepArgs 
         const float2 wt = reinterpret_cast<const float2 *>(a.weights)[e];
         EdgeQT<double> o;
         edge_eval<double>(g, px, py, d, (double)tp[0], (double)tp[1], (double)wt.x, (double)wt.y, a, o);
-        const int ia = pd.pair_i[gp] - pd.fixedp, ib = pd.pair_j[gp] - pd.fixedp;
-        double xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-        if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = (double)a.dx[6 * ia + c];
-        if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = (double)a.dx[6 * ib + c];
-        // delta = dX_j - Ad(Gij) dX_i,  Ad (tau, phi) = (R tau + t x (R phi), R phi)                (se3.h:58-67)
-        double Rt[3], Rp[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            Rt[r] = g[3 * r] * xi[0] + g[3 * r + 1] * xi[1] + g[3 * r + 2] * xi[2];
-            Rp[r] = g[3 * r] * xi[3] + g[3 * r + 1] * xi[4] + g[3 * r + 2] * xi[5];
-        }
-        const double dl[6] = { xj[0] - (Rt[0] + g[10] * Rp[2] - g[11] * Rp[1]), xj[1] - (Rt[1] + g[11] * Rp[0] - g[9] * Rp[2]),
-                               xj[2] - (Rt[2] + g[9] * Rp[1] - g[10] * Rp[0]), xj[3] - Rp[0], xj[4] - Rp[1], xj[5] - Rp[2] };
-        const double d0 = o.a0 * dl[0] + o.a2 * dl[2] + o.a3 * dl[3] + o.a4 * dl[4] + o.a5 * dl[5];
-        const double d1 = o.b1 * dl[1] + o.b2 * dl[2] + o.b3 * dl[3] + o.b4 * dl[4] + o.b5 * dl[5];
-        acc += o.W0 * o.jz0 * d0 + o.W1 * o.jz1 * d1;
+        double dl[6];
+        pair_delta(g, a.dx, pd.pair_i[gp] - pd.fixedp, pd.pair_j[gp] - pd.fixedp, dl);
+        acc += edge_term(o, o.W0 * o.jz0, o.W1 * o.jz1, dl);
     }
     acc = block_sum(acc, red);
     if (tid == 0) {
         double Q, wp;
         if (a.prec) { const double2 qw = reinterpret_cast<const double2 *>(a.qw)[k]; Q = qw.x; wp = qw.y; }
         else { const float2 qw = a.qw[k]; Q = qw.x; wp = qw.y; }
-        float dd = (float)(d + Q * (wp - acc));                              // ba.py:328, :333
-        dd = dd < 1e-3f ? 1e-3f : dd;
-        dd = dd > 10.0f ? 10.0f : dd;
-        a.patches_out[3 * patch] = (float)px; a.patches_out[3 * patch + 1] = (float)py; a.patches_out[3 * patch + 2] = dd;
+        a.patches_out[3 * patch] = (float)px; a.patches_out[3 * patch + 1] = (float)py; a.patches_out[3 * patch + 2] = new_disp(d, Q, wp, acc);
     }
 }
 

@@ -26,11 +26,13 @@
 // off, then for real.  The first pass costs nothing (the workgroup would be waiting) and was meant to leave the second's
 // instructions in the instruction cache.  It has NOT been measured on its own: the wall-clock stamps of r22 show the first
 // (cold) pass of a phase no slower than the second, so its gain is unproven; the A/B of r22 is of the kernel with it.
-// The arithmetic is k_update's, expression by expression: fused and split steps give the same bits.
+// The arithmetic is k_update's, the same functions (pair_delta, edge_term: ba_edge.hpp; new_disp: ba_update.hpp): fused and split
+// steps give the same bits.
 // Every wait is bounded: a lane that has polled for kSuPollTicks (~100 ms) writes BT_SOLVE_HANDOFF_TIMEOUT to the status
 // block and takes dX = 0 for its granule; the workgroup writes its outputs and returns.
 #pragma once
 #include "ba_edge.hpp"
+#include "ba_update.hpp"
 
 namespace bt {
 
@@ -92,19 +94,23 @@ __device__ __forceinline__ void su_update_workgroup(const PlanDev &pd, const Ste
         if (tile >= pd.T) break;
         R *geo = baseR + (size_t)k * tileR, *sav = geo + (size_t)mtp * kUpdGeo, *trk = sav + (size_t)msl * kSuSaved * 64;
         int *lpv = baseI + (size_t)k * tileI, *pch = lpv + (size_t)msl * 64, *cam = pch + 64, *meta = cam + 2 * mtp;
-        int patch = -1, slot0 = 0, s0 = 0, s1 = 0, e_nx = -1, lp_nx = 0;
-        R px = 0, py = 0, pdisp = 0, tu_nx = 0, tv_nx = 0, w0_nx = 0, w1_nx = 0;
+        int patch = -1, slot0 = 0, s0 = 0, s1 = 0;
+        R px = 0, py = 0, pdisp = 0;
+        SlotStream<R> ss;
         if (tid < kSuTileThreads) {
             const int np = pd.tile_npair[tile], nslot = pd.tile_nslot[tile];
             patch = pd.tile_kx[(size_t)tile * kLanes + lane];
             slot0 = pd.tile_slot0[tile];
-            const int chunk = (nslot + kWaves - 1) / kWaves;
-            s0 = wave * chunk; s1 = min(nslot, s0 + chunk);
+            wave_slots(nslot, wave, kWaves, s0, s1);
             if (tid == 0) { meta[0] = nslot; meta[1] = np; }
-            if (s0 < s1) { const size_t idx = (size_t)(slot0 + s0) * kLanes + lane; e_nx = pd.slot_edge[idx]; lp_nx = pd.slot_lp[idx]; }
+            if (s0 < s1) ss.start(pd, slot0 + s0, lane);
             for (int p = tid; p < np; p += kSuTileThreads) {
                 const int gp = pd.tile_pairs[pd.tile_pair0[tile] + p];
                 cam[2 * p] = pd.pair_i[gp] - pd.fixedp; cam[2 * p + 1] = pd.pair_j[gp] - pd.fixedp;
+                // (workspace -> LDS, the values are not needed in registers here: a copy of its own, not load_pairgeo.  Through
+                //  load_pairgeo the float64 instantiations issue the ten loads in front of the stores, the scalar-register spills
+                //  around the solver's body move — some 300 instructions of k_solve_update<*, double> — and the C3 step measured
+                //  0.3 us slower, profiles/r23_update_once.txt)
                 const R2 *src = reinterpret_cast<const R2 *>(reinterpret_cast<const R *>(a.pairgeo) + (size_t)gp * kPairGeomFloats);
                 R2 *o = reinterpret_cast<R2 *>(geo + (size_t)p * kUpdGeo);
 #pragma unroll
@@ -113,12 +119,7 @@ __device__ __forceinline__ void su_update_workgroup(const PlanDev &pd, const Ste
                 o[13] = zero;
             }
             if (patch >= 0) { px = a.patches[3*patch]; py = a.patches[3*patch + 1]; pdisp = a.patches[3*patch + 2]; }
-            if (e_nx >= 0) {
-                const float *tp = a.targets + (size_t)e_nx * a.tstride;
-                tu_nx = tp[0]; tv_nx = tp[1];
-                const float2 w = reinterpret_cast<const float2 *>(a.weights)[e_nx];
-                w0_nx = w.x; w1_nx = w.y;
-            }
+            ss.fetch(a);
             if (wave == 0) {
                 R2 qw; qw.x = (R)0; qw.y = (R)0;
                 if (patch >= 0) qw = reinterpret_cast<const R2 *>(a.qw)[pd.tile_trk0[tile] + lane];
@@ -136,31 +137,12 @@ __device__ __forceinline__ void su_update_workgroup(const PlanDev &pd, const Ste
         if (tid < kSuTileThreads) {
 #pragma unroll 1
             for (int s = s0; s < s1; ++s) {
-                const int e = e_nx, lp = lp_nx;
-                const R tu = tu_nx, tv = tv_nx, w0 = w0_nx, w1 = w1_nx;
-                if (s + 1 < s1) {
-                    const size_t idn = (size_t)(slot0 + s + 1) * kLanes + lane;
-                    e_nx = pd.slot_edge[idn]; lp_nx = pd.slot_lp[idn];
-                    tu_nx = tv_nx = w0_nx = w1_nx = (R)0;
-                    if (e_nx >= 0) {
-                        const float *tp = a.targets + (size_t)e_nx * a.tstride;
-                        tu_nx = tp[0]; tv_nx = tp[1];
-                        const float2 w = reinterpret_cast<const float2 *>(a.weights)[e_nx];
-                        w0_nx = w.x; w1_nx = w.y;
-                    }
-                }
+                ss.advance(pd, a, slot0 + s + 1, s + 1 < s1, lane);
+                const int e = ss.e, lp = ss.lp;
                 R g[kPairGeomFloats];
-                if (sizeof(R) == 4) {
-                    const float4 *g4 = reinterpret_cast<const float4 *>(geo + (size_t)lp * kUpdGeo);
-#pragma unroll
-                    for (int c = 0; c < kPairGeomFloats / 4; ++c) { const float4 t4 = g4[c]; g[4*c] = t4.x; g[4*c + 1] = t4.y; g[4*c + 2] = t4.z; g[4*c + 3] = t4.w; }
-                } else {
-                    const double2 *g2 = reinterpret_cast<const double2 *>(geo + (size_t)lp * kUpdGeo);
-#pragma unroll
-                    for (int c = 0; c < kPairGeomFloats / 2; ++c) { const double2 t2 = g2[c]; g[2*c] = t2.x; g[2*c + 1] = t2.y; }
-                }
+                load16<kPairGeomFloats>(geo + (size_t)lp * kUpdGeo, g);
                 EdgeQT<R> q;
-                edge_eval<R>(g, px, py, pdisp, tu, tv, w0, w1, a, q);
+                edge_eval<R>(g, px, py, pdisp, ss.tu, ss.tv, ss.w0, ss.w1, a, q);
                 lpv[s * 64 + lane] = e < 0 ? -1 : lp;
                 if (e < 0) continue;
                 R *o = sav + (size_t)s * kSuSaved * 64 + lane;
@@ -219,47 +201,29 @@ __device__ __forceinline__ void su_update_workgroup(const PlanDev &pd, const Ste
         } else {
             // ---- tile role, after dX.  Behind the barrier above its eight waves meet only each other, through a counter in
             // LDS: the pose and zero roles of waves 8.. are off their path.  delta = dX_j - Ad(Gij) dX_i of the edge's camera
-            // pair is formed by the edge's own thread (k_update's expressions; k_update forms it once per pair, same bits).
+            // pair is formed by the edge's own thread (pair_delta, as in k_update, which forms it once per pair: same bits).
 #pragma unroll 1
             for (int k = 0; k < tpw; ++k) {
                 if (wg + k * W >= pd.T) break;
                 const R *geo = baseR + (size_t)k * tileR, *sav = geo + (size_t)mtp * kUpdGeo;
                 R *part = baseR + (size_t)k * tileR + (size_t)mtp * kUpdGeo + (size_t)msl * kSuSaved * 64 + 5 * 64;
                 const int *lpv = baseI + (size_t)k * tileI, *cam = lpv + (size_t)msl * 64 + 64, *meta = cam + 2 * mtp;
-                const int nslot = meta[0], chunk = (nslot + kWaves - 1) / kWaves;
-                const int s0 = wave * chunk, s1 = min(nslot, s0 + chunk);
+                int s0, s1;
+                wave_slots(meta[0], wave, kWaves, s0, s1);
                 R acc = 0;
 #pragma unroll 1
                 for (int s = s0; s < s1; ++s) {
                     const int lp = lpv[s * 64 + lane];
                     if (lp < 0) continue;
                     const int ia = cam[2 * lp], ib = cam[2 * lp + 1];
-                    R g[kUpdGeo];
-                    const R2 *g2 = reinterpret_cast<const R2 *>(geo + (size_t)lp * kUpdGeo);
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) { const R2 t2 = g2[c]; g[2*c] = t2.x; g[2*c + 1] = t2.y; }
-                    R xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-                    if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = dxc[6 * ia + c];
-                    if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = dxc[6 * ib + c];
-                    // Ad(Gij) (tau, phi) = (R tau + t x (R phi), R phi)        (se3.h:58-67)
-                    R Rt[3], Rp[3];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        Rt[r] = g[3*r] * xi[0] + g[3*r + 1] * xi[1] + g[3*r + 2] * xi[2];
-                        Rp[r] = g[3*r] * xi[3] + g[3*r + 1] * xi[4] + g[3*r + 2] * xi[5];
-                    }
-                    g[20] = xj[0] - (Rt[0] + g[10] * Rp[2] - g[11] * Rp[1]);
-                    g[21] = xj[1] - (Rt[1] + g[11] * Rp[0] - g[9]  * Rp[2]);
-                    g[22] = xj[2] - (Rt[2] + g[9]  * Rp[1] - g[10] * Rp[0]);
-                    g[23] = xj[3] - Rp[0]; g[24] = xj[4] - Rp[1]; g[25] = xj[5] - Rp[2];
+                    R g[12], dl[6];                                            // the pair's R and t
+                    load16<12>(geo + (size_t)lp * kUpdGeo, g);
+                    pair_delta(g, dxc, ia, ib, dl);
                     const R *o = sav + (size_t)s * kSuSaved * 64 + lane;
                     EdgeQT<R> q;
                     q.a0 = o[0]; q.a2 = o[64]; q.a3 = o[128]; q.a4 = o[192]; q.a5 = o[256];
                     q.b1 = o[320]; q.b2 = o[384]; q.b3 = o[448]; q.b4 = o[512]; q.b5 = o[576];
-                    const R wj0 = o[640], wj1 = o[704];
-                    const R d0 = q.a0 * g[20] + q.a2 * g[22] + q.a3 * g[23] + q.a4 * g[24] + q.a5 * g[25];
-                    const R d1 = q.b1 * g[21] + q.b2 * g[22] + q.b3 * g[23] + q.b4 * g[24] + q.b5 * g[25];
-                    acc += wj0 * d0 + wj1 * d1;
+                    acc += edge_term(q, o[640], o[704], dl);
                 }
                 part[wave * 64 + lane] = acc;
             }
@@ -277,10 +241,7 @@ __device__ __forceinline__ void su_update_workgroup(const PlanDev &pd, const Ste
 #pragma unroll
                 for (int w = 0; w < kWaves; ++w) tot += part[w * 64 + lane];
                 const R px = trk[lane], py = trk[64 + lane], pdisp = trk[128 + lane];
-                R2 qw; qw.x = trk[192 + lane]; qw.y = trk[256 + lane];
-                float dd = (float)(pdisp + qw.x * (qw.y - tot));                // ba.py:328, :333
-                dd = dd < 1e-3f ? 1e-3f : dd;
-                dd = dd > 10.0f ? 10.0f : dd;
+                const float dd = new_disp<R>(pdisp, trk[192 + lane], trk[256 + lane], tot);
                 if (real) { a.patches_out[3*patch] = (float)px; a.patches_out[3*patch + 1] = (float)py; a.patches_out[3*patch + 2] = dd; }
             }
         }

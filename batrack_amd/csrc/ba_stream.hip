@@ -25,6 +25,7 @@
 
 #include "ba_edge.hpp"
 #include "ba_kernels.hpp"
+#include "ba_update.hpp"
 #include "dev_cache.hpp"
 
 namespace bt {
@@ -34,7 +35,6 @@ namespace bt {
 #endif
 constexpr int kSG = 4;                 // slots per operand group (a wave's share of an 8-observation tile)
 enum { kModeFull = 0, kModeSO = 1, kModeUpd = 2 };
-constexpr int kUpdGeoS = 28;           // floats per pair in LDS for kModeUpd: geometry (20), delta (6), padding
 
 struct TileRec { int ntrk, ncam, npair, flags, slot0, nslot, cam0, pair0, trk0; };
 
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
 #define BT_PF(i) do { if (PROF) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tn = clock64(); pf[i] += tn - tc; tc = tn; __builtin_amdgcn_sched_barrier(0); } } while (0)
     const int mtp = pd.max_tile_pairs > 0 ? pd.max_tile_pairs : 1;
     const int Rmax = 6 * pd.max_cams;
-    constexpr int GS = MODE == kModeUpd ? kUpdGeoS : kPairGeomFloats;
+    constexpr int GS = MODE == kModeUpd ? kUpdGeo : kPairGeomFloats;
     // LDS carve-up (private to the two waves of the tile)
     float *geo = lds;                                                  // [mtp][GS]
     float *part = geo + mtp * GS;                                      // [2 waves][8][64]: C, w, source-camera E partials (kModeUpd: depth sums)
@@ -259,26 +259,13 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
                 const int gp = pd.tile_pairs[rec.pair0 + p];
                 float *g = geo + p * GS;
                 if (MODE == kModeUpd) {
-                    const int ia = pd.pair_i[gp] - pd.fixedp, ib = pd.pair_j[gp] - pd.fixedp;
-                    float gg[kPairGeomFloats];
-                    const float4 *src = reinterpret_cast<const float4 *>(a.pairgeo + (size_t)gp * kPairGeomFloats);
-#pragma unroll
-                    for (int c = 0; c < kPairGeomFloats / 4; ++c) { const float4 t4 = src[c]; gg[4*c] = t4.x; gg[4*c + 1] = t4.y; gg[4*c + 2] = t4.z; gg[4*c + 3] = t4.w; }
-                    float xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-                    if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = a.dx[6 * ia + c];
-                    if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = a.dx[6 * ib + c];
-                    float Rt[3], Rp[3];                                  // Ad(Gij)(tau, phi) = (R tau + t x (R phi), R phi)   (se3.h:58-67)
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        Rt[r] = gg[3*r] * xi[0] + gg[3*r + 1] * xi[1] + gg[3*r + 2] * xi[2];
-                        Rp[r] = gg[3*r] * xi[3] + gg[3*r + 1] * xi[4] + gg[3*r + 2] * xi[5];
-                    }
+                    float gg[kPairGeomFloats], dl[6];
+                    load_pairgeo(a.pairgeo, gp, gg);
+                    pair_delta(gg, a.dx, pd.pair_i[gp] - pd.fixedp, pd.pair_j[gp] - pd.fixedp, dl);
 #pragma unroll
                     for (int c = 0; c < kPairGeomFloats; ++c) g[c] = gg[c];
-                    g[20] = xj[0] - (Rt[0] + gg[10] * Rp[2] - gg[11] * Rp[1]);
-                    g[21] = xj[1] - (Rt[1] + gg[11] * Rp[0] - gg[9]  * Rp[2]);
-                    g[22] = xj[2] - (Rt[2] + gg[9]  * Rp[1] - gg[10] * Rp[0]);
-                    g[23] = xj[3] - Rp[0]; g[24] = xj[4] - Rp[1]; g[25] = xj[5] - Rp[2];
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) g[20 + c] = dl[c];
                     g[26] = 0.0f; g[27] = 0.0f;
                 } else {
                     const int ij = pd.tile_ij[(unsigned)tile * (unsigned)mtp + (unsigned)p];
@@ -322,23 +309,12 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
                 const bool act = (code >> 16) != 0;
                 const unsigned lb = code & 0xffu, lp = (code >> 8) & 0xffu;
                 float g[GS];
-                {
-                    const float4 *g4 = reinterpret_cast<const float4 *>(geo + (size_t)lp * GS);
-#pragma unroll
-                    for (int c = 0; c < GS / 4; ++c) {
-                        const float4 t4 = g4[c];
-                        g[4*c] = t4.x; g[4*c + 1] = t4.y; g[4*c + 2] = t4.z; g[4*c + 3] = t4.w;
-                    }
-                }
+                load16<GS>(geo + (size_t)lp * GS, g);
                 EdgeQ q;
                 BT_WPT_EDGE_EVAL(g, px, py, pdisp, grp.tu[s], grp.tv[s], grp.w0[s], grp.w1[s], a, q);
                 if (!act) { q.W0 = 0.0f; q.W1 = 0.0f; q.r0 = 0.0f; q.r1 = 0.0f; }
                 if (MODE == kModeUpd) {
-                    if (act) {
-                        const float d0 = q.a0 * g[20] + q.a2 * g[22] + q.a3 * g[23] + q.a4 * g[24] + q.a5 * g[25];
-                        const float d1 = q.b1 * g[21] + q.b2 * g[22] + q.b3 * g[23] + q.b4 * g[24] + q.b5 * g[25];
-                        dacc += q.W0 * q.jz0 * d0 + q.W1 * q.jz1 * d1;
-                    }
+                    if (act) dacc += edge_term(q, q.W0 * q.jz0, q.W1 * q.jz1, g + 20);
                     continue;
                 }
                 // C, w of the track (ba.py:287,292)
@@ -454,10 +430,8 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
             if (wave == 0 && has_trk) {
                 const float tot = part[lane] + part[64 + lane];
                 const float2 qw = a.qw[(unsigned)rec.trk0 + (unsigned)lane];
-                float dd = pdisp + qw.x * (qw.y - tot);                          // ba.py:328, :333
-                dd = dd < 1e-3f ? 1e-3f : dd;
-                dd = dd > 10.0f ? 10.0f : dd;
-                a.patches_out[3u * (unsigned)kx_c] = px; a.patches_out[3u * (unsigned)kx_c + 1u] = py; a.patches_out[3u * (unsigned)kx_c + 2u] = dd;
+                a.patches_out[3u * (unsigned)kx_c] = px; a.patches_out[3u * (unsigned)kx_c + 1u] = py;
+                a.patches_out[3u * (unsigned)kx_c + 2u] = new_disp(pdisp, qw.x, qw.y, tot);
             }
             stage_a();
             stage_b();
@@ -539,7 +513,7 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
 static size_t stream_lds_bytes(const PlanDev &pd, int mode) {
     const size_t mtp = (size_t)(pd.max_tile_pairs > 0 ? pd.max_tile_pairs : 1);
     const size_t Rmax = (size_t)(6 * pd.max_cams);
-    if (mode == kModeUpd) return (mtp * kUpdGeoS + 1024) * sizeof(float);
+    if (mode == kModeUpd) return (mtp * kUpdGeo + 1024) * sizeof(float);
     if (mode == kModeSO) return (mtp * kPairGeomFloats + 1024) * sizeof(float);
     return (mtp * kPairGeomFloats + 1024 + (Rmax + 1) * kLdsRowStride + 128 + ((Rmax + 3) & ~(size_t)3) + ((mtp + 3) & ~(size_t)3)) * sizeof(float) +
            2 * mtp * 32 * sizeof(double) + 16;

@@ -326,10 +326,7 @@ __global__ __launch_bounds__(WIDE ? 1024 : 512, WIDE ? 2 : (sizeof(R) == 8 ? BT_
                 wp = wv - pm * (R)a.alpha * (pdisp - mono);
                 Q = sizeof(R) == 8 ? (R)frcp((double)Ca) : (R)1 / Ca;      // (float64: seed + two Newton steps, < 1e-15; the IEEE divide is ~30 instructions)
                 if (FUSE) {                                                // ba.py:316-317, :333
-                    float dd = (float)(pdisp + Q * wp);
-                    dd = dd < 1e-3f ? 1e-3f : dd;
-                    dd = dd > 10.0f ? 10.0f : dd;
-                    a.patches_out[3*patch] = (float)px; a.patches_out[3*patch + 1] = (float)py; a.patches_out[3*patch + 2] = dd;
+                    a.patches_out[3*patch] = (float)px; a.patches_out[3*patch + 1] = (float)py; a.patches_out[3*patch + 2] = new_disp<R>(pdisp, Q, wp, (R)0);
                 } else {
                     R2 qw2; qw2.x = Q; qw2.y = wp;
                     reinterpret_cast<R2 *>(a.qw)[trk] = qw2;
@@ -410,8 +407,8 @@ __global__ __launch_bounds__(WIDE ? 1024 : 512, WIDE ? 2 : (sizeof(R) == 8 ? BT_
 //                            dZ_k = Q_k (w'_k - sum_c E[c,k]^T dX_c) (ba.py:328) is evaluated WITHOUT a stored E:
 //                            E[c,k]^T dX_c summed over the cameras of a track is, edge by edge,
 //                            Jz^T W (Jj dX_j + Ji dX_i) = Jz^T W Jj (dX_j - Ad(Gij) dX_i)  (Ji = -Jj Ad, projective_ops.py:96),
-//                            so the block forms delta = dX_j - Ad dX_i once per camera pair of the tile (from the
-//                            pair geometry k_tile left in the workspace) and re-evaluates the edge Jacobians from
+//                            so the block forms delta = dX_j - Ad dX_i (pair_delta, ba_edge.hpp) once per camera pair of the
+//                            tile (from the pair geometry k_tile left in the workspace) and re-evaluates the edge Jacobians from
 //                            targets / weights: 16 B per edge read again instead of 24 B per edge written and read back.
 //   [.., + patch_blocks)     the whole patch buffer: copy of x, y and the clamp of ba.py:333; structure-only steps
 //                            add dZ = Q w' (ba.py:316-317) here; pose+structure steps skip the patches that carry
@@ -443,79 +440,37 @@ __global__ __launch_bounds__(THREADS) void k_update(PlanDev pd, StepArgs a, int 
         R *part = lds + (size_t)pd.max_tile_pairs * kUpdGeo;        // [kWaves][64]
         const int np = pd.tile_npair[tile];
         const int patch = pd.tile_kx[(size_t)tile * kLanes + lane];
-        const int slot0 = pd.tile_slot0[tile], nslot = pd.tile_nslot[tile];
-        const int chunk = (nslot + kWaves - 1) / kWaves;
-        const int s0 = wave * chunk, s1 = min(nslot, s0 + chunk);
-        int e_nx = -1, lp_nx = 0;
-        if (s0 < s1) { const size_t idx = (size_t)(slot0 + s0) * kLanes + lane; e_nx = pd.slot_edge[idx]; lp_nx = pd.slot_lp[idx]; }
+        const int slot0 = pd.tile_slot0[tile];
+        int s0, s1;
+        wave_slots(pd.tile_nslot[tile], wave, kWaves, s0, s1);
+        SlotStream<R> ss;
+        if (s0 < s1) ss.start(pd, slot0 + s0, lane);
         for (int p = tid; p < np; p += THREADS) {
             const int gp = pd.tile_pairs[pd.tile_pair0[tile] + p];
-            const int ia = pd.pair_i[gp] - pd.fixedp, ib = pd.pair_j[gp] - pd.fixedp;
-            R g[kPairGeomFloats];
-            const R2 *src = reinterpret_cast<const R2 *>(reinterpret_cast<const R *>(a.pairgeo) + (size_t)gp * kPairGeomFloats);
-#pragma unroll
-            for (int c = 0; c < kPairGeomFloats / 2; ++c) { const R2 t2 = src[c]; g[2*c] = t2.x; g[2*c + 1] = t2.y; }
-            R xi[6] = {0, 0, 0, 0, 0, 0}, xj[6] = {0, 0, 0, 0, 0, 0};
-            if (ia >= 0) for (int c = 0; c < 6; ++c) xi[c] = a.dx[6 * ia + c];
-            if (ib >= 0) for (int c = 0; c < 6; ++c) xj[c] = a.dx[6 * ib + c];
-            // Ad(Gij) (tau, phi) = (R tau + t x (R phi), R phi)        (se3.h:58-67)
-            R Rt[3], Rp[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                Rt[r] = g[3*r] * xi[0] + g[3*r + 1] * xi[1] + g[3*r + 2] * xi[2];
-                Rp[r] = g[3*r] * xi[3] + g[3*r + 1] * xi[4] + g[3*r + 2] * xi[5];
-            }
+            R g[kPairGeomFloats], dl[6];
+            load_pairgeo(a.pairgeo, gp, g);
+            pair_delta(g, a.dx, pd.pair_i[gp] - pd.fixedp, pd.pair_j[gp] - pd.fixedp, dl);
             R *o = geo + (size_t)p * kUpdGeo;
 #pragma unroll
             for (int c = 0; c < kPairGeomFloats; ++c) o[c] = g[c];
-            o[20] = xj[0] - (Rt[0] + g[10] * Rp[2] - g[11] * Rp[1]);
-            o[21] = xj[1] - (Rt[1] + g[11] * Rp[0] - g[9]  * Rp[2]);
-            o[22] = xj[2] - (Rt[2] + g[9]  * Rp[1] - g[10] * Rp[0]);
-            o[23] = xj[3] - Rp[0]; o[24] = xj[4] - Rp[1]; o[25] = xj[5] - Rp[2];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) o[20 + c] = dl[c];
             o[26] = (R)0; o[27] = (R)0;
         }
         R px = 0, py = 0, pdisp = 0;
         if (patch >= 0) { px = a.patches[3*patch]; py = a.patches[3*patch + 1]; pdisp = a.patches[3*patch + 2]; }
-        R tu_nx = 0, tv_nx = 0, w0_nx = 0, w1_nx = 0;
-        if (e_nx >= 0) {
-            const float *tp = a.targets + (size_t)e_nx * a.tstride;
-            tu_nx = tp[0]; tv_nx = tp[1];
-            const float2 w = reinterpret_cast<const float2 *>(a.weights)[e_nx];
-            w0_nx = w.x; w1_nx = w.y;
-        }
+        ss.fetch(a);
         __syncthreads();
         R acc = 0;
 #pragma unroll 1
         for (int s = s0; s < s1; ++s) {
-            const int e = e_nx, lp = lp_nx;
-            const R tu = tu_nx, tv = tv_nx, w0 = w0_nx, w1 = w1_nx;
-            if (s + 1 < s1) {
-                const size_t idn = (size_t)(slot0 + s + 1) * kLanes + lane;
-                e_nx = pd.slot_edge[idn]; lp_nx = pd.slot_lp[idn];
-                tu_nx = tv_nx = w0_nx = w1_nx = (R)0;
-                if (e_nx >= 0) {
-                    const float *tp = a.targets + (size_t)e_nx * a.tstride;
-                    tu_nx = tp[0]; tv_nx = tp[1];
-                    const float2 w = reinterpret_cast<const float2 *>(a.weights)[e_nx];
-                    w0_nx = w.x; w1_nx = w.y;
-                }
-            }
+            ss.advance(pd, a, slot0 + s + 1, s + 1 < s1, lane);
             R g[kUpdGeo];
-            if (sizeof(R) == 4) {
-                const float4 *g4 = reinterpret_cast<const float4 *>(geo + (size_t)lp * kUpdGeo);
-#pragma unroll
-                for (int c = 0; c < kUpdGeo / 4; ++c) { const float4 t4 = g4[c]; g[4*c] = t4.x; g[4*c + 1] = t4.y; g[4*c + 2] = t4.z; g[4*c + 3] = t4.w; }
-            } else {
-                const double2 *g2 = reinterpret_cast<const double2 *>(geo + (size_t)lp * kUpdGeo);
-#pragma unroll
-                for (int c = 0; c < kUpdGeo / 2; ++c) { const double2 t2 = g2[c]; g[2*c] = t2.x; g[2*c + 1] = t2.y; }
-            }
+            load16<kUpdGeo>(geo + (size_t)ss.lp * kUpdGeo, g);
             EdgeQT<R> q;
-            edge_eval<R>(g, px, py, pdisp, tu, tv, w0, w1, a, q);
-            if (e < 0) continue;
-            const R d0 = q.a0 * g[20] + q.a2 * g[22] + q.a3 * g[23] + q.a4 * g[24] + q.a5 * g[25];
-            const R d1 = q.b1 * g[21] + q.b2 * g[22] + q.b3 * g[23] + q.b4 * g[24] + q.b5 * g[25];
-            acc += q.W0 * q.jz0 * d0 + q.W1 * q.jz1 * d1;
+            edge_eval<R>(g, px, py, pdisp, ss.tu, ss.tv, ss.w0, ss.w1, a, q);
+            if (ss.e < 0) continue;
+            acc += edge_term(q, q.W0 * q.jz0, q.W1 * q.jz1, g + 20);
         }
         part[wave * 64 + lane] = acc;
         __syncthreads();
@@ -524,10 +479,7 @@ __global__ __launch_bounds__(THREADS) void k_update(PlanDev pd, StepArgs a, int 
 #pragma unroll
             for (int w = 0; w < kWaves; ++w) tot += part[w * 64 + lane];
             const R2 qw = reinterpret_cast<const R2 *>(a.qw)[pd.tile_trk0[tile] + lane];
-            float dd = (float)(pdisp + qw.x * (qw.y - tot));                // ba.py:328, :333
-            dd = dd < 1e-3f ? 1e-3f : dd;
-            dd = dd > 10.0f ? 10.0f : dd;
-            a.patches_out[3*patch] = (float)px; a.patches_out[3*patch + 1] = (float)py; a.patches_out[3*patch + 2] = dd;
+            a.patches_out[3*patch] = (float)px; a.patches_out[3*patch + 1] = (float)py; a.patches_out[3*patch + 2] = new_disp<R>(pdisp, qw.x, qw.y, tot);
         }
         return;
     }

@@ -1,6 +1,7 @@
-// ba_update.hpp — the part of a step's last kernel that is not per tile, shared by k_update / k_tile (ba_tile.hip) and
-// k_etile (ba_etile.hip): the pose retraction Exp(dX) * G (groups.py:153-156) and the copy + clamp of the patch buffer
-// (ba.py:333).
+// ba_update.hpp — what the kernels that end a step share (k_update / k_tile, ba_tile.hip; k_etile, ba_etile.hip; k_stream,
+// k_edge2u, k_loose_update; k_solve_update, ba_solve_update.hpp): a track's new disparity and its clamp (ba.py:328, :333), the
+// walk over a tile's slots one slot ahead, dX as tagged granules, the pose retraction Exp(dX) * G (groups.py:153-156) and the
+// copy + clamp of the patch buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,48 @@
 namespace bt {
 
 constexpr int kUpdGeo = 28;          // floats per pair in the LDS of an update's tile block: the 20 of kPairGeomFloats, delta (6), padding to 16 bytes
+
+// ba.py:333.  Two selects, not fminf / fmaxf: a NaN disparity passes through, as it does in the reference.
+__device__ __forceinline__ float clamp_disp(float dd) {
+    dd = dd < 1e-3f ? 1e-3f : dd;
+    return dd > 10.0f ? 10.0f : dd;
+}
+// a track's new disparity, dZ = Q (w' - tot) applied and clamped (ba.py:328, :333); tot = sum of its edges' Jz^T W Jj delta,
+// 0 on a structure-only step (ba.py:316-317).  In R up to the rounding to float32.
+template <typename R>
+__device__ __forceinline__ float new_disp(R pdisp, R Q, R wp, R tot) { return clamp_disp((float)(pdisp + Q * (wp - tot))); }
+
+// The slots [s0, s1) of a k_tile-layout tile that wave `wave` of `waves` walks
+__device__ __forceinline__ void wave_slots(int nslot, int wave, int waves, int &s0, int &s1) {
+    const int chunk = (nslot + waves - 1) / waves;
+    s0 = wave * chunk; s1 = min(nslot, s0 + chunk);
+}
+// A lane's walk over such slots, fetched one slot ahead: the slot's edge (-1: none), local pair, target and weights.
+// start() requests the first slot's table entries and fetch() its operands — apart, so that the caller can put work that
+// needs neither between the two dependent trips to memory; advance() makes the fetched slot current and, if there is one,
+// fetches slot `next`.
+template <typename R>
+struct SlotStream {
+    int e = -1, lp = 0, e_nx = -1, lp_nx = 0;
+    R tu = 0, tv = 0, w0 = 0, w1 = 0, tu_nx = 0, tv_nx = 0, w0_nx = 0, w1_nx = 0;
+    __device__ __forceinline__ void start(const PlanDev &pd, int slot, int lane) {
+        const size_t idx = (size_t)slot * kLanes + lane;
+        e_nx = pd.slot_edge[idx]; lp_nx = pd.slot_lp[idx];
+    }
+    __device__ __forceinline__ void fetch(const StepArgs &a) {
+        tu_nx = tv_nx = w0_nx = w1_nx = (R)0;
+        if (e_nx >= 0) {
+            const float *tp = a.targets + (size_t)e_nx * a.tstride;
+            tu_nx = tp[0]; tv_nx = tp[1];
+            const float2 w = reinterpret_cast<const float2 *>(a.weights)[e_nx];
+            w0_nx = w.x; w1_nx = w.y;
+        }
+    }
+    __device__ __forceinline__ void advance(const PlanDev &pd, const StepArgs &a, int next, bool more, int lane) {
+        e = e_nx; lp = lp_nx; tu = tu_nx; tv = tv_nx; w0 = w0_nx; w1 = w1_nx;
+        if (more) { start(pd, next, lane); fetch(a); }
+    }
+};
 
 // dX as tagged granules (StepArgs::dxg; the fused solve + update launch, ba_solve_update.hpp): one 8-byte word per component,
 // {float dx, uint32 tag}, written and read whole by relaxed agent-scope atomics.  The tag travels with the value, so the
@@ -81,9 +124,8 @@ __device__ __forceinline__ void update_rest(const PlanDev &pd, const StepArgs &a
             if (a.prec) { const double2 qw = reinterpret_cast<const double2 *>(a.qw)[trk]; dd = (float)((double)d + qw.x * qw.y); }
             else { const float2 qw = a.qw[trk]; dd = d + qw.x * qw.y; }
         }
-        dd = dd < 1e-3f ? 1e-3f : dd;
-        dd = dd > 10.0f ? 10.0f : dd;
-        a.patches_out[3*gid] = x; a.patches_out[3*gid + 1] = y; a.patches_out[3*gid + 2] = dd;
+        // (clamp_disp alone, not new_disp: a patch without a track has no (Q, w') to load)
+        a.patches_out[3*gid] = x; a.patches_out[3*gid + 1] = y; a.patches_out[3*gid + 2] = clamp_disp(dd);
     } else if (do_poses && gid < pd.p_tot + pd.n_buf) {
         const int p = gid - pd.p_tot;
         if (SO) {

@@ -1,5 +1,6 @@
-// ba_wave.hpp — wave-level device helpers shared by ba_tile.hip and ba_solve.hip: DPP sums over groups of 8 lanes, the wavefront
-// fence, wave-uniform values into SGPRs, the factorisations' reciprocal square root, 6-element rows as three vector accesses.
+// ba_wave.hpp — wave-level device helpers shared by ba_tile.hip, ba_solve.hip, ba_etile.hip and the two-edges-per-lane kernels
+// (ba_edge2.hpp): sums over groups and residue classes of lanes by DPP and lane swaps (float and double), the wavefront fence,
+// wave-uniform values into SGPRs, the factorisations' reciprocal square root, 6-element rows as three vector accesses.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,23 +31,81 @@ __device__ __forceinline__ void store_row6(T *p, const T (&v)[6]) {
     reinterpret_cast<V *>(p)[0] = a; reinterpret_cast<V *>(p)[1] = b; reinterpret_cast<V *>(p)[2] = c;
 }
 
-__device__ __forceinline__ float dpp_add8(float v) {   // sum over aligned groups of 8 lanes, all lanes get it
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad xor 1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));   // quad xor 2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-    return v;
+// ------------------------------------------------------------------ cross-lane sums, float and double
+// x of the lane the DPP control names (a double as its two halves); `old` where the control leaves a lane unwritten
+template <int CTRL, int BANK = 0xf, bool BOUND = true>
+__device__ __forceinline__ float lane_dpp(float old, float x) {
+    return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp((int)__float_as_uint(old), (int)__float_as_uint(x), CTRL, 0xf, BANK, BOUND));
 }
-__device__ __forceinline__ double dpp_perm(double v, int sel) {
-    const long long b = __double_as_longlong(v);
-    int lo = (int)(b & 0xffffffffll), hi = (int)(b >> 32);
-    if (sel == 0) { lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true); }
-    else if (sel == 1) { lo = __builtin_amdgcn_update_dpp(0, lo, 0x4E, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x4E, 0xF, 0xF, true); }
-    else { lo = __builtin_amdgcn_update_dpp(0, lo, 0x141, 0xF, 0xF, true); hi = __builtin_amdgcn_update_dpp(0, hi, 0x141, 0xF, 0xF, true); }
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+template <int CTRL, int BANK = 0xf, bool BOUND = true>
+__device__ __forceinline__ double lane_dpp(double old, double x) {
+    const unsigned long long o = (unsigned long long)__double_as_longlong(old), v = (unsigned long long)__double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)o, (int)(unsigned)v, CTRL, 0xf, BANK, BOUND);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(o >> 32), (int)(unsigned)(v >> 32), CTRL, 0xf, BANK, BOUND);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-__device__ __forceinline__ double dpp_add8(double v) {
-    v += dpp_perm(v, 0); v += dpp_perm(v, 1); v += dpp_perm(v, 2);
-    return v;
+// x + (x of lane ^ 16), x + (x of lane ^ 32): v_permlane16_swap / v_permlane32_swap
+__device__ __forceinline__ float lane_swap16(float x) {
+    const uint2_t r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+__device__ __forceinline__ float lane_swap32(float x) {
+    const uint2_t r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r.x) + __uint_as_float(r.y);
+}
+__device__ __forceinline__ double lane_mk(unsigned lo, unsigned hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
+__device__ __forceinline__ double lane_swap16(double x) {
+    const unsigned long long v = (unsigned long long)__double_as_longlong(x);
+    const uint2_t rl = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+    const uint2_t rh = __builtin_amdgcn_permlane16_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    return lane_mk(rl.x, rh.x) + lane_mk(rl.y, rh.y);
+}
+__device__ __forceinline__ double lane_swap32(double x) {
+    const unsigned long long v = (unsigned long long)__double_as_longlong(x);
+    const uint2_t rl = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    const uint2_t rh = __builtin_amdgcn_permlane32_swap((unsigned)(v >> 32), (unsigned)(v >> 32), false, false);
+    return lane_mk(rl.x, rh.x) + lane_mk(rl.y, rh.y);
+}
+// x + (x of lane ^ M)
+template <int M, typename T>
+__device__ __forceinline__ T xor_add(T x) {
+    if (M == 1) return x + lane_dpp<0xb1>((T)0, x);
+    if (M == 2) return x + lane_dpp<0x4e>((T)0, x);
+    if (M == 4) {
+        T t = lane_dpp<0x104, 0x5, false>((T)0, x);           // row_shl:4 on the banks with bit 2 clear
+        t = lane_dpp<0x114, 0xa, false>(t, x);                 // row_shr:4 on the others
+        return x + t;
+    }
+    if (M == 8) return x + lane_dpp<0x128>((T)0, x);
+    if (M == 16) return lane_swap16(x);
+    return lane_swap32(x);
+}
+// sum of x over the groups of 2^lg adjacent lanes (every lane of a group gets the total); lg is wave-uniform.  Inside a row
+// the partners are quad_perm (lane ^ 1, lane ^ 2), row_half_mirror (7 - lane of the 8) and row_mirror (15 - lane of the 16)
+template <int N, typename T>
+__device__ __forceinline__ void group_sum(T (&x)[N], int lg) {
+    if (lg > 0) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += lane_dpp<0xb1>((T)0, x[i]); }
+    if (lg > 1) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += lane_dpp<0x4e>((T)0, x[i]); }
+    if (lg > 2) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += lane_dpp<0x141>((T)0, x[i]); }
+    if (lg > 3) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] += lane_dpp<0x140>((T)0, x[i]); }
+    if (lg > 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = lane_swap16(x[i]); }
+    if (lg > 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = lane_swap32(x[i]); }
+}
+// sum of x over the lanes with the same (lane mod 2^lg) (lane < 2^lg then holds the total of its residue class)
+template <int N, typename T>
+__device__ __forceinline__ void stride_sum(T (&x)[N], int lg) {
+    if (lg <= 5) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<32>(x[i]); }
+    if (lg <= 4) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<16>(x[i]); }
+    if (lg <= 3) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<8>(x[i]); }
+    if (lg <= 2) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<4>(x[i]); }
+    if (lg <= 1) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<2>(x[i]); }
+    if (lg <= 0) { _Pragma("unroll") for (int i = 0; i < N; ++i) x[i] = xor_add<1>(x[i]); }
+}
+template <typename T>
+__device__ __forceinline__ T dpp_add8(T v) {            // sum over aligned groups of 8 lanes, all lanes get it
+    T x[1] = {v};
+    group_sum(x, 3);
+    return x[0];
 }
 
 __device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); }
