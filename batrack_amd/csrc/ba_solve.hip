@@ -735,81 +735,148 @@ __device__ __forceinline__ void lds_load_system_dma(const PlanDev &pd, const Ste
     sys_dma_fixup<T>(pd, a, Lw, trl, *ntr, col_ptr, lm, zero_upper, tid, nth);
 }
 
+constexpr int kFusedCols = 2;     // columns per level k_solve_fused and k_solve_pipe handle (two-ended chains); wider levels use k_solve_lds
+
+// The back substitution's level table, behind zt: one 8-byte word per (level, column slot, lane group g), so that a lane finds
+// everything the level asks of it at an address that depends on the level number alone — nothing to look up behind a record.
+//   .x  col | #sub-blocks << 8 | kBsSync (barrier before this level: ba_plan.cpp bs_sync) | kBsNoCol (the slot has no column)
+//   .y  sub-block g of the column: its block index | its row's column << 16; kBsNone: the column has no sub-block g (block 0
+//       and row 0 then: addresses that can be read, the values are thrown away)
+// kBsPad empty levels come first (levels -kBsPad .. -1): the loop reads ahead without asking where it is.
+// Built by every attempt (the sweep's tables lie where zt and this table go).  `row_idx`: the LDS copy.
+constexpr int kBsSync = 1 << 16, kBsNoCol = 1 << 17, kBsNone = (int)0x80000000, kBsPad = 3;
+__host__ __device__ inline size_t backsub_table_bytes(const PlanDev &pd) { return (size_t)(pd.nlev + kBsPad) * kFusedCols * 8 * sizeof(int2); }
+__device__ __forceinline__ void backsub_table(const PlanDev &pd, int2 *tab, const int *row_idx, int tid, int nth) {
+    for (int i = tid; i < (pd.nlev + kBsPad) * kFusedCols * 8; i += nth) {
+        const int g = i & 7, ls = i >> 3, l = ls / kFusedCols - kBsPad, s = ls % kFusedCols;
+        int2 w = make_int2(kBsNoCol, kBsNone);
+        if (l >= 0) {
+            const int4 mm = reinterpret_cast<const int4 *>(pd.fz_meta)[2 * (l * kMaxLevelCols + s)];      // col, diag pos, #sub-blocks
+            const int sync = pd.bs_sync[l] ? kBsSync : 0;
+            w.x |= sync;
+            if (mm.x >= 0) {
+                const int b = mm.y + 1 + g;
+                w.x = mm.x | (mm.z << 8) | sync;
+                if (g < mm.z) w.y = b | ((row_idx[b] & 255) << 16);
+            }
+        }
+        tab[i] = w;
+    }
+}
+
 // Back substitution of the LDS-resident factor (diagonal blocks hold L_jj with 1/l_cc on the
 // diagonal, or the updated A_jj: RAW_DIAG): brings it into M form, then x_j = zt_j - sum_{i>j} M_ij x_i by levels, descending.
 template <typename T, bool RAW_DIAG = false>
 __device__ __forceinline__ void lds_back_substitute(const PlanDev &pd, T *Lw, T *z, T *zt, const int *row_idx,
-                                                    const int *col_ptr, const int4 *lvl_meta, int mstride, int tid, int nth, long long *tprof = nullptr) {
-    const int n = pd.n, nnzb = pd.nnzb, nlev = pd.nlev, wave = tid >> 6, lane = tid & 63;
+                                                    const int *col_ptr, const int2 *tab, int tid, int nth, long long *tprof = nullptr) {
+    const int nnzb = pd.nnzb, nlev = pd.nlev, wave = tid >> 6, lane = tid & 63;
     lds_backsub_prep<T, RAW_DIAG>(Lw, z, zt, row_idx, col_ptr, nnzb, tid, nth);
     __syncthreads();
     if (tprof) tprof[0] = tprof[1] = clock64();         // (one pass: L^-1 and the M form end together)
     // (c) x_j = zt_j - sum_{i>j} M_ij x_i, levels descending, ONE WAVE PER COLUMN SLOT and no barrier unless
-    // the level reads an x_i another slot's wave wrote since the last barrier (lvl_meta[..].w, ba_plan.cpp
-    // bs_sync): on a two-ended chain the two waves run down their chains independently.  The static
-    // operands of level l - 1 (block index, M entries) are loaded before level l's x are waited for.
-    // lane = (component c) * 8 + g, one sub-block per lane group g.
-    {
-        const bool bw = wave < kMaxLevelCols;
-        const int c = lane >> 3, g = lane & 7;
-        struct Pre { int4 ma; int rc; T m[6]; T ztj; };
-        auto preload = [&](int l, Pre &P) {           // everything of level l that does not depend on the x computed so far
-            // (per-lane copies of the level record: no scalarisation needed; operands of lanes without a
-            //  sub-block are never used)
-            P.ma = lvl_meta[(l * kMaxLevelCols + (bw ? wave : 0)) * mstride];
-            if (!bw) P.ma.x = -1;
-            if (P.ma.x >= 0 && c < 6) {
-                P.ztj = zt[6 * P.ma.x + c];
-                if (g < P.ma.z) {
-                    const int b = P.ma.y + 1 + g;
-                    P.rc = row_idx[b] & 255;
-                    const T *mb = Lw + (size_t)b * 36 + c;     // Mt[r][c]
+    // the level reads an x_i another slot's wave wrote since the last barrier (kBsSync): on a two-ended chain
+    // the two waves run down their chains independently.  lane = (component c) * 8 + g, one sub-block per lane
+    // group g.  A lone wave stands still for a whole LDS round trip at every wait, so a level has ONE: its x.
+    // The lane's word of the table is read two levels ahead, and with it (landed a level ago) the static operands
+    // — zt_j, the six M entries — one level ahead; all of that is issued right behind the level's x reads, which
+    // are waited for alone, and lands under the multiply-adds.  Lanes without a sub-block (and the lanes of c = 6, 7) read along at harmless
+    // addresses and drop the product: no divergent branch in the level.  Columns of more than 8 sub-blocks look
+    // their further rounds up in the loop.
+    const int c = lane >> 3, g = lane & 7;
+    if (__builtin_amdgcn_readfirstlane(wave) < kFusedCols) {
+        const int2 *wtab = tab + (kBsPad * kFusedCols + wave) * 8 + g;
+        struct Pre { int2 w; T m[6]; T ztj; };
+        auto word = [&](int l) { return wtab[l * (kFusedCols * 8)]; };
+        auto operands = [&](Pre &P) {                 // everything of the level of P.w that does not depend on the x computed so far
+            P.ztj = zt[6 * (P.w.x & 255) + c];
+            const T *mb = Lw + (P.w.y & 0x7fff) * 36 + c;             // Mt[r][c]
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) P.m[k] = mb[6 * k];
-                }
-            }
+            for (int k = 0; k < 6; ++k) P.m[k] = mb[6 * k];
         };
-        auto step = [&](const Pre &P) {
-            if (__builtin_amdgcn_readfirstlane(P.ma.w)) __syncthreads();
-            if (P.ma.x >= 0) {
-                const int j = P.ma.x, dpos = P.ma.y, cnt = P.ma.z;
-                T acc = (T)0;
-                if (c < 6 && g < cnt) {
-                    T x[6];
-                    load_row6(zt + 6 * P.rc, x);
-                    acc = P.m[0] * x[0] + P.m[1] * x[1] + P.m[2] * x[2] + P.m[3] * x[3] + P.m[4] * x[4] + P.m[5] * x[5];
-                    for (int sb = g + 8; sb < cnt; sb += 8) {       // wide columns: further sub-blocks of this lane group
-                        const int b = dpos + 1 + sb;
+        int2 wn;                                       // the word two levels ahead
+        // one level: P holds its word and operands; N is filled for the level after it, behind this level's x in the queue
+        auto level = [&](const Pre &P, Pre &N, int l2) {
+            const int wx = __builtin_amdgcn_readfirstlane(P.w.x);
+            if (wx & kBsSync) __syncthreads();
+            T x[6];
+            load_row6(zt + 6 * ((P.w.y >> 16) & 255), x);
+            __builtin_amdgcn_sched_barrier(0);
+            N.w = wn;
+            wn = word(l2);
+            operands(N);
+            __builtin_amdgcn_sched_barrier(0);
+            if (!(wx & kBsNoCol)) {
+                const int j = wx & 255, cnt = (wx >> 8) & 255;
+                T acc = P.m[0] * x[0] + P.m[1] * x[1] + P.m[2] * x[2] + P.m[3] * x[3] + P.m[4] * x[4] + P.m[5] * x[5];
+                asm volatile("" : "+v"(acc));                        // (every lane forms it: no branch for the lanes that drop it)
+                if (P.w.y < 0) acc = (T)0;
+                if (cnt > 8 && c < 6)
+                    for (int sb = g + 8, b = (P.w.y & 0x7fff) + 8; sb < cnt; sb += 8, b += 8) {       // wide columns: further sub-blocks of this lane group
                         load_row6(zt + 6 * (row_idx[b] & 255), x);
-                        const T *mb = Lw + (size_t)b * 36 + c;
+                        const T *mb = Lw + b * 36 + c;
                         acc += mb[0] * x[0] + mb[6] * x[1] + mb[12] * x[2] + mb[18] * x[3] + mb[24] * x[4] + mb[30] * x[5];
                     }
-                }
                 acc = dpp_add8(acc);
                 if (c < 6 && g == 0) zt[6 * j + c] = P.ztj - acc;
                 wave_fence();
             }
         };
         Pre A = {}, B = {};                            // two register sets, levels alternate between them
-        preload(nlev - 1, A);
-        for (int l = nlev - 1; l >= 0; l -= 2) {
-            if (l >= 1) preload(l - 1, B);
-            step(A);
-            if (l >= 1) {
-                if (l >= 2) preload(l - 2, A);
-                step(B);
-            }
+        A.w = word(nlev - 1);
+        wn = word(nlev - 2);
+        operands(A);
+        for (int l = nlev - 1; l >= 0; l -= 2) {       // (an odd count ends on an empty level of the padding)
+            level(A, B, l - 2);
+            level(B, A, l - 3);
         }
-        __syncthreads();
+    } else {
+        // (the other waves only keep the barriers company: the same for every slot of a level, so they follow slot 0)
+        for (int l = nlev - 1; l >= 0; --l)
+            if (__builtin_amdgcn_readfirstlane(tab[(kBsPad + l) * kFusedCols * 8].x) & kBsSync) __syncthreads();
     }
+    __syncthreads();
 }
 
 // ---- what the sweeps of k_solve_fused and k_solve_pipe share (the probe macros stay with the kernels, between the calls)
+// Where the first pending pair of the row wave's lane rw is found in pfirst: its own block, or the diagonal block for y_j and
+// for the lanes without a row.  `ma`: the column's record word (col | #sub-blocks << 8 | ...), dpos: its diagonal block.
+__device__ __forceinline__ int pfirst_index(int ma, int dpos, int rw) { return rw < ((ma >> 8) & 255) * 6 ? dpos + 1 + rw / 6 : dpos; }
+
+// What a wave looks at in front of operands that other waves write.  look() issues the flag reads and passed() tests them, with
+// the operand reads issued in between: the CU's LDS executes a wave's instructions in order and the producers drain their
+// stores before they raise a flag, so operands read behind a flag that had the value are good — the first look that passes
+// costs ONE round trip, not the flags' and then the operands'.  After a miss the operands are thrown away and both are read
+// again.  The compiler keeps the order (and reads again in every round) because of the two barriers; checked in the ISA.
+struct NoPoll {                                         // k_solve_fused: the workgroup barrier has ordered everything
+    __device__ __forceinline__ void look() {}
+    __device__ __forceinline__ bool passed() { return true; }
+};
+struct LevelPoll {                                      // k_solve_pipe, start of a level: colready[0] >= need0, colready[1] >= need1, hcnt >= needh
+    int *colready, *hcnt;
+    int need0, need1, needh, f0, f1, fh, lastfail;
+    __device__ __forceinline__ void look() {
+        f0 = __hip_atomic_load(&colready[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        f1 = __hip_atomic_load(&colready[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        fh = __hip_atomic_load(hcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        asm volatile("" ::: "memory");
+    }
+    __device__ __forceinline__ bool passed() {
+        asm volatile("" ::: "memory");
+        if (f0 >= need0 && f1 >= need1 && fh >= needh) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            return true;
+        }
+        lastfail = fh < needh ? 1 : 0;                   // (PROF: what the wait was for: 1 = the helpers' batch, 0 = a column)
+        __builtin_amdgcn_s_sleep(1);
+        return false;
+    }
+};
+
 // Row wave: the pending update of panel row rw of the column (record ma, diagonal block at dpos), or of y_j for rw = 6 cnt, in
-// registers.  Returns where the row lives; `valid`: the lane has a row at all.
-template <typename T>
-__device__ __forceinline__ T *row_wave_pending(T *Lw, T *z, const int *row_idx, const int *pfirst, const int *psecond, int ma, int dpos, int rw,
-                                               bool &valid, T (&in)[6]) {
+// registers.  Returns where the row lives; `valid`: the lane has a row at all.  `pfo`: the lane's word of pfirst (pfirst_index).
+template <typename T, typename Poll>
+__device__ __forceinline__ T *row_wave_pending(T *Lw, T *z, const int *row_idx, unsigned pfo, const int *psecond, int ma, int dpos, int rw,
+                                               bool &valid, T (&in)[6], Poll &poll) {
     const int j = ma & 255, cnt = (ma >> 8) & 255, ysrc = (ma >> 16) & 255;
     const bool isy = rw == cnt * 6;
     valid = rw <= cnt * 6;
@@ -817,16 +884,18 @@ __device__ __forceinline__ T *row_wave_pending(T *Lw, T *z, const int *row_idx, 
     T *p = isy ? z + 6 * j : Lw + (size_t)bown * 36 + 6 * r;
     // in[c] -= sum_e avec[e] M[c][e] with avec = row r of src1 and M = src2, or for the y row
     // avec = y of the source column and M = src1; every load is in flight before the first FMA
-    const unsigned pfo = (unsigned)pfirst[valid && !isy ? bown : dpos];
     const int s1 = pfo & 0x7fff, s2 = (pfo >> 15) & 0x7fff, no = valid ? (int)(pfo >> 30) : 0;
     T avec[6], m[36];
-    load_row6(p, in);
-    load_row6(isy ? z + 6 * ysrc : Lw + (size_t)s1 * 36 + 6 * r, avec);
-    {
-        const T *M = Lw + (size_t)(isy ? s1 : s2) * 36;
+    const T *ap = isy ? z + 6 * ysrc : Lw + (size_t)s1 * 36 + 6 * r, *M = Lw + (size_t)(isy ? s1 : s2) * 36;
+    auto look_and_load = [&]() {
+        poll.look();
+        load_row6(p, in);
+        load_row6(ap, avec);
 #pragma unroll
         for (int c = 0; c < 6; ++c) load_row6(M + 6 * c, reinterpret_cast<T (&)[6]>(m[6 * c]));
-    }
+    };
+    look_and_load();                                  // (the first look stands by itself: a loop's head waits for the wave's stores)
+    while (!poll.passed()) look_and_load();
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         T acc = avec[0] * m[6 * c];
@@ -858,15 +927,13 @@ __device__ __forceinline__ T *row_wave_pending(T *Lw, T *z, const int *row_idx, 
 __host__ __device__ inline size_t sweep_work_bytes(const PlanDev &pd) {
     const size_t b = 2 * 36 * sizeof(double) +          // published diagonal blocks of the level's two columns
                      (size_t)pd.fz_nlazy * 4 * sizeof(unsigned short) + 16;
-    const size_t zt = (size_t)pd.D * sizeof(double) + (size_t)pd.nlev * kMaxLevelCols * sizeof(int4);   // zt + compact level table
+    const size_t zt = (size_t)((pd.D + 1) & ~1) * sizeof(double) + backsub_table_bytes(pd);   // zt + the back substitution's level table
     return ((b > zt ? b : zt) + 15) / 16 * 16;
 }
 size_t solve_fused_lds_bytes(const PlanDev &pd, int) {
     return ((size_t)pd.nnzb * 36 + (size_t)pd.D) * sizeof(double) + sweep_work_bytes(pd) +
            (5 * (size_t)pd.nnzb + (size_t)pd.n + 1) * sizeof(int) + 64;       // row_idx, pfirst, psecond, col_ptr, bsrc, trl
 }
-
-constexpr int kFusedCols = 2;     // columns per level k_solve_fused handles (two-ended chains); wider levels use k_solve_lds
 
 template <bool PROF, bool PUB>
 __device__ __forceinline__ void solve_fused_body(const PlanDev &pd, const StepArgs &a) {
@@ -972,7 +1039,9 @@ __device__ __forceinline__ void solve_fused_body(const PlanDev &pd, const StepAr
                     const int ma = q ? c1a : c0a, dpos = (q ? c1b : c0b) & 0xffff;
                     bool valid;
                     T in[6];
-                    T *p = row_wave_pending(Lw, z, row_idx, pfirst, psecond, ma, dpos, part * 64 + lane, valid, in);
+                    NoPoll nopoll;
+                    T *p = row_wave_pending(Lw, z, row_idx, (unsigned)pfirst[pfirst_index(ma, dpos, part * 64 + lane)], psecond, ma, dpos,
+                                            part * 64 + lane, valid, in, nopoll);
                     BT_SUB(3);
                     while (__hip_atomic_load(&lready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) <= l) __builtin_amdgcn_s_sleep(1);
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1050,14 +1119,10 @@ __device__ __forceinline__ void solve_fused_body(const PlanDev &pd, const StepAr
         }
         if (PROF) tsweep = clock64() - tall;
 
-        int4 *bmeta = reinterpret_cast<int4 *>(zt + ((D + 1) & ~1));          // compact level table behind zt
-        for (int i = tid; i < nlev * kMaxLevelCols; i += nth) {          // (col, diag pos, #sub-blocks, barrier before this level)
-            int4 mm = reinterpret_cast<const int4 *>(pd.fz_meta)[2 * i];
-            mm.w = pd.bs_sync[i / kMaxLevelCols];
-            bmeta[i] = mm;
-        }
+        int2 *btab = reinterpret_cast<int2 *>(zt + ((D + 1) & ~1));          // the level table behind zt
+        backsub_table(pd, btab, row_idx, tid, nth);
         long long tbs[2] = {0, 0};
-        lds_back_substitute<T, true>(pd, Lw, z, zt, row_idx, col_ptr, bmeta, 1, tid, nth, PROF ? tbs : nullptr);
+        lds_back_substitute<T, true>(pd, Lw, z, zt, row_idx, col_ptr, btab, tid, nth, PROF ? tbs : nullptr);
         if (PROF) { sub[0] = tbs[0] - tall; sub[1] = tbs[1] - tall; sub[2] = clock64() - tall; }
         for (int i = tid; i < D; i += nth) if (zt[i] != zt[i]) flags[1] = 1;
         __syncthreads();
@@ -1110,7 +1175,11 @@ __global__ __launch_bounds__(768) void k_solve_fused(PlanDev pd, StepArgs a) { s
 //                           hcnt >= nh b (the whole group has finished the batches before: two batches may
 //                           read-modify-write the same destination row from different waves)
 // A chain's row wave therefore never waits for anything but its diagonal wave in steady state; the barrier
-// (~240 cycles by itself) and the wait for the slowest wave of every level are gone.  Requires columns of at
+// (~240 cycles by itself) and the wait for the slowest wave of every level are gone.  What it does pay for is every LDS
+// round trip it stands still for (a lone wave, and eight helper waves keep the LDS busy), so a level of the row wave has two:
+// its flags with the operands of its pending update behind them, and lready with the published block behind it (LevelPoll);
+// the lane's pfirst word and the next level's record are read a level ahead, under the factorisation
+// (profiles/r24_solver_round_trips.txt).  Requires columns of at
 // most 64 panel rows and levels of at most two columns (plan flag fzp_ok); other systems use k_solve_fused.
 size_t solve_pipe_lds_bytes(const PlanDev &pd) {
     return ((size_t)pd.nnzb * 36 + (size_t)pd.D) * sizeof(double) + sweep_work_bytes(pd) +
@@ -1127,7 +1196,7 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int flags[2];
     __shared__ int lready[2], colready[2], hcnt, ntr;
-    const int tid = threadIdx.x, nth = blockDim.x, wave = tid >> 6, lane = tid & 63, nw = nth >> 6;
+    const int tid = threadIdx.x, nth = blockDim.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nth >> 6;
     const int n = pd.n, D = pd.D, nnzb = pd.nnzb, nlev = pd.nlev;
     T *Lw = reinterpret_cast<T *>(smem);
     T *z = Lw + (size_t)nnzb * 36, *scr = z + D, *zt = scr;
@@ -1149,7 +1218,7 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
         // (inside k_solve_update the copy loop's trip count, hoisted out of the attempt loop, was the one value the register
         //  allocator spilled: 8 bytes of scratch per lane that k_solve_pipe alone does not have, 0 with the value opaque here and
         //  formed per attempt — compiler figures in profiles/r22_solve_update.txt.  k_solve_pipe itself compiles as before.)
-        if (PUB) asm volatile("" : "+s"(nlazy));
+        asm volatile("" : "+s"(nlazy));
         for (int i = tid; i < nlazy; i += nth)                // one 8-byte word per triple: src1, src2, dst | shared << 15
             reinterpret_cast<ushort4 *>(lazy)[i] = make_ushort4((unsigned short)pd.fz_lazy[3 * i], (unsigned short)pd.fz_lazy[3 * i + 1],
                                                                (unsigned short)pd.fz_lazy[3 * i + 2], 0);
@@ -1166,43 +1235,41 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
             int4 vrec = lrec4[q];                                // this wave's record and slot 0's (it carries the number of columns)
             int vnc = lrec[1];
             int npc = 0;                                         // columns of the level below
+            // row wave: the lane's word of pfirst, read a level ahead (its address needs the level's record alone, which is
+            // here a level ahead too) and carried in a register: the operand reads of a level follow its flags directly
+            unsigned pfn = is_row ? (unsigned)pfirst[pfirst_index(vrec.x, vrec.y & 0xffff, lane)] : 0u;
             for (int l = 0; l < nlev; ++l) {
                 const int ma = __builtin_amdgcn_readfirstlane(vrec.x), mb = __builtin_amdgcn_readfirstlane(vrec.y),
                           md = __builtin_amdgcn_readfirstlane(vrec.w), ncl = (__builtin_amdgcn_readfirstlane(vnc) >> 24) & 3;
-                if (l + 1 < nlev) { vrec = lrec4[2 * (l + 1) + q]; vnc = lrec[8 * (l + 1) + 1]; }   // next level's, in flight during this one
+                // next level's record, in flight during this one (the row wave asks for it once its operands are in registers:
+                // during their reads every register counts)
+                auto next_record = [&]() { if (l + 1 < nlev) { vrec = lrec4[2 * (l + 1) + q]; vnc = lrec[8 * (l + 1) + 1]; } };
+                if (!is_row) next_record();
                 if (q < ncl) {
-                    if (l > 0) {
-                        // only the columns of the level below that hold pending sources of this column (the record's
-                        // dependency bits: on a chain its own predecessor, which this very row wave wrote) and the
-                        // helpers' batches; the three flags in one LDS round trip
-                        // (the diagonal wave also waits for the row wave that last read its scratch slot)
-                        const int dep = ((md >> 20) & 3) | ((!is_row && q < npc) ? 1 << q : 0);
-                        const int need0 = (dep & 1) ? l : 0, need1 = (dep & 2) ? l : 0, needh = nh * (l - 1);
-                        const long long tw0 = PROF ? clock64() : 0;
-                        int lastfail = -1;                           // (PROF: what the wait was for: 1 = the helpers' batch, 0 = a column)
-                        for (;;) {
-                            const int f0 = __hip_atomic_load(&colready[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const int f1 = __hip_atomic_load(&colready[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const int fh = __hip_atomic_load(&hcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            if (f0 >= need0 && f1 >= need1 && fh >= needh) break;
-                            if (PROF) lastfail = fh < needh ? 1 : 0;
-                            __builtin_amdgcn_s_sleep(1);
-                        }
-                        if (PROF && lastfail >= 0) wsplit[lastfail] += clock64() - tw0;
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    }
-                    BT_TW(twait);
+                    // What the level waits for: only the columns of the level below that hold pending sources of this column
+                    // (the record's dependency bits: on a chain its own predecessor, which this very row wave wrote) and the
+                    // helpers' batches; the three flags and the operands behind them in one LDS round trip (LevelPoll)
+                    // (the diagonal wave also waits for the row wave that last read its scratch slot)
+                    const int dep = l > 0 ? ((md >> 20) & 3) | ((!is_row && q < npc) ? 1 << q : 0) : 0;
+                    LevelPoll poll = {colready, &hcnt, (dep & 1) ? l : 0, (dep & 2) ? l : 0, l > 0 ? nh * (l - 1) : 0, 0, 0, 0, -1};
+                    const long long tw0 = PROF ? clock64() : 0;
                     const int dpos = mb & 0xffff;
                     if (!is_row) {
                         // ---- diagonal wave: bring the diagonal block up to date with its pending updates (lanes 0..35,
                         // one element each) and publish it to the row wave
-                        // (same text in k_solve_fused: as one function it changed both kernels' instruction streams (resources equal); not measured on the GPU, so it stays twice -- profiles/r15_kernels_split.txt)
+                        // (same text in k_solve_fused but for the poll: as one function it changed both kernels' instruction streams (resources equal); not measured on the GPU, so it stays twice -- profiles/r15_kernels_split.txt)
                         const int el = lane < 36 ? lane : lane - 36, dr = el / 6, dc = el - 6 * dr;
                         const int sd = md & 0x7fff, nd = (md >> 15) & 3;
                         T x[6], yv[6];
-                        T v = Lw[(size_t)dpos * 36 + el];
+                        T v;
+                        // (the flags alone, then the operands: this wave is ahead of its row wave and misses nearly every first
+                        //  look; with the seven operand reads in every round the C3 solve measured 0.8 us slower)
+                        do poll.look(); while (!poll.passed());
+                        v = Lw[(size_t)dpos * 36 + el];
                         load_row6(Lw + (size_t)sd * 36 + 6 * dr, x);
                         load_row6(Lw + (size_t)sd * 36 + 6 * dc, yv);
+                        if (PROF && poll.lastfail >= 0) wsplit[poll.lastfail] += clock64() - tw0;
+                        BT_TW(twait);
                         if (nd > 0) {
                             T acc = x[0] * yv[0];
 #pragma unroll
@@ -1231,14 +1298,15 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
                         // substitution of the row
                         bool valid;
                         T in[6];
-                        T *p = row_wave_pending(Lw, z, row_idx, pfirst, psecond, ma, dpos, lane, valid, in);
+                        T *p = row_wave_pending(Lw, z, row_idx, pfn, psecond, ma, dpos, lane, valid, in, poll);
+                        if (PROF && poll.lastfail >= 0) wsplit[poll.lastfail] += clock64() - tw0;
                         BT_TW(sub[0]);
-                        wait_ge(&lready[q], l + 1);
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                        BT_TW(sub[1]);
-                        // (this and the substitution below: same text in k_solve_fused: as one function it changed both kernels' instruction streams (resources equal); not measured on the GPU, so it stays twice -- profiles/r15_kernels_split.txt)
+                        // (the factorisation and the substitution below: same text in k_solve_fused but for the poll: as one function it changed both kernels' instruction streams (resources equal); not measured on the GPU, so it stays twice -- profiles/r15_kernels_split.txt)
                         T L[21];
-                        {
+                        int lrf;
+                        auto look_and_load = [&]() {            // lready[q], and the published block behind it in the same round trip
+                            lrf = __hip_atomic_load(&lready[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            asm volatile("" ::: "memory");
                             const T *dblk = scr + q * 36;
 #pragma unroll
                             for (int rr = 0; rr < 6; ++rr) {
@@ -1247,7 +1315,14 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
 #pragma unroll
                                 for (int c = 0; c <= rr; ++c) L[BT_LT(rr, c)] = row[c];
                             }
-                        }
+                            next_record();                      // (static, behind the block in the same round trip)
+                            asm volatile("" ::: "memory");
+                        };
+                        look_and_load();
+                        while (lrf <= l) { __builtin_amdgcn_s_sleep(1); look_and_load(); }       // (waits for lready[q] >= l + 1)
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                        if (l + 1 < nlev) pfn = (unsigned)pfirst[pfirst_index(vrec.x, vrec.y & 0xffff, lane)];      // (lands under the factorisation)
+                        BT_TW(sub[1]);
                         const bool ok = chol6_packed<T>(L);
                         // (substitution computed by every lane, only the store is predicated: one basic block, so the
                         //  compiler can slot its FMAs into the latency gaps of the factorisation)
@@ -1265,6 +1340,10 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
                         if (lane == 0) __hip_atomic_store(&colready[q], l + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         BT_TW(sub[2]);
                     }
+                } else if (is_row && l + 1 < nlev) {
+                    next_record();
+                    pfn = (unsigned)pfirst[pfirst_index(vrec.x, vrec.y & 0xffff, lane)];
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pfn));       // (here, not at the top of every level)
                 }
                 npc = ncl;
             }
@@ -1325,13 +1404,9 @@ __device__ __forceinline__ void solve_pipe_body(const PlanDev &pd, const StepArg
         if (PROF) tsweep = clock64() - tall;
 
         // (same text in k_solve_fused: as one function it changed both kernels' instruction streams (and k_solve_fused<false>'s registers, 167 -> 168); not measured on the GPU, so it stays twice -- profiles/r15_kernels_split.txt)
-        int4 *bmeta = reinterpret_cast<int4 *>(zt + ((D + 1) & ~1));          // compact level table behind zt
-        for (int i = tid; i < nlev * kMaxLevelCols; i += nth) {          // (col, diag pos, #sub-blocks, barrier before this level)
-            int4 mm = reinterpret_cast<const int4 *>(pd.fz_meta)[2 * i];
-            mm.w = pd.bs_sync[i / kMaxLevelCols];
-            bmeta[i] = mm;
-        }
-        lds_back_substitute<T, true>(pd, Lw, z, zt, row_idx, col_ptr, bmeta, 1, tid, nth, nullptr);
+        int2 *btab = reinterpret_cast<int2 *>(zt + ((D + 1) & ~1));          // the level table behind zt
+        backsub_table(pd, btab, row_idx, tid, nth);
+        lds_back_substitute<T, true>(pd, Lw, z, zt, row_idx, col_ptr, btab, tid, nth, nullptr);
         for (int i = tid; i < D; i += nth) if (zt[i] != zt[i]) flags[1] = 1;
         __syncthreads();
         const bool failed = flags[0] != 0, has_nan = flags[1] != 0;
