@@ -1,4 +1,4 @@
-// ba_dense.hip — the reduced camera system of MORE THAN 255 free poses (plans with `wide` set, ba_plan.cpp): a dense, blocked,
+// ba_dense.hip — the reduced camera system of MORE THAN 255 free poses (plans with `wide` set, ba_plan_solver.cpp): a dense, blocked,
 // right-looking Cholesky in double in the global workspace, then the two triangular solves.  The block-sparse solvers
 // (ba_solve.hip) keep pose numbers in 8 bits and live in one CU's LDS; the reference's solve (ba.py:60-70: torch.linalg.cholesky
 // of the dense 6n x 6n matrix) has no size clause, so neither may this backend — a global / loop-closing adjustment of 300 or 1000

@@ -3,7 +3,9 @@
 #pragma once
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <cstddef>
+#include <cstdio>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -28,10 +30,10 @@ constexpr int kPrivY = 16, kPrivP = 4;
 // behind them: one arrival counter per SIMD of the chip (k_edge2: which of a SIMD's two waves am I — see "wave priority" there)
 constexpr int kPrivArrive = 8192;   // ints: xcc (3 bits) | se (3) | sh (1) | cu (4) | simd (2)
 constexpr int kPairGeomFloats = 20; // R(9) t(3) Ki(4) Kj(4)
-constexpr int kLdsRowStride = 66;
-constexpr int kMaxLevelCols = 4;
+constexpr int kLdsRowStride = 66;   // floats per local E row (bank-conflict-free)
+constexpr int kMaxLevelCols = 4;    // columns of the reduced system factored concurrently (one critical wave each)
 // LDS a solver workgroup may ask for (160 KB a CU), and what the block-sparse factor with its tables takes there at `elem` bytes
-// per number: the planner sends systems whose factor does not fit as double to the dense solver (ba_plan.cpp: `wide`).
+// per number: the planner sends systems whose factor does not fit as double to the dense solver (ba_plan_solver.cpp: `wide`).
 constexpr size_t kLdsBudget = 160 * 1024 - 512;
 inline size_t solve_lds_bytes_raw(size_t nnzb, size_t D, size_t nupd, size_t n, size_t nlev, size_t ndp, size_t elem) {
     size_t b = (nnzb * 36 + 2 * D) * elem;                                 // Lw, z, zt
@@ -44,10 +46,8 @@ inline size_t solve_lds_bytes_raw(size_t nnzb, size_t D, size_t nupd, size_t n, 
     return b + 64;
 }
 constexpr int kSpGroupMax = 32;     // tiles per group of k_pair_finalize's positional sums of the tiles' Schur products
-constexpr int kMaxTilePairs = 192;  // distinct camera pairs per tile whose geometry is kept in LDS    // columns of the reduced system factored concurrently (one critical wave each)   // floats per local E row (bank-conflict-free)
+constexpr int kMaxTilePairs = 192;  // distinct camera pairs per tile whose geometry is kept in LDS
 
-// doubles per tile of StepArgs::spart (plans with sp_ok): the tile's Schur product (ntl lower 16x16 tiles of 256), E Q w'
-// (max_rows16) and its per-pair sums (max_tile_pairs x 32: 27 used)
 #ifdef __HIPCC__
 #define BT_HD __host__ __device__
 #else
@@ -56,6 +56,8 @@ constexpr int kMaxTilePairs = 192;  // distinct camera pairs per tile whose geom
 // doubles of the private region (WsLayout::priv): the copies of y, of the per-pair sums, the arrival counters
 BT_HD inline size_t priv_copy_doubles(size_t D, size_t pairs) { return (size_t)kPrivY * D + (size_t)kPrivP * pairs * kPairAccStride; }
 BT_HD inline size_t priv_doubles(size_t D, size_t pairs) { return priv_copy_doubles(D, pairs) + kPrivArrive / 2; }
+// doubles per tile of StepArgs::spart (plans with sp_ok): the tile's Schur product (ntl lower 16x16 tiles of 256), E Q w'
+// (max_rows16) and its per-pair sums (max_tile_pairs x 32: 27 used)
 BT_HD inline size_t sp_tile_doubles(int max_rows16, int max_tile_pairs) {
     const size_t nt = (size_t)max_rows16 / 16;
     return nt * (nt + 1) / 2 * 256 + (size_t)max_rows16 + (size_t)(max_tile_pairs > 0 ? max_tile_pairs : 1) * 32;
@@ -155,7 +157,7 @@ struct WsLayout {
 };
 
 // The tables a plan uploads, in their order in the device buffer (ba_api.cpp: upload_plan): element type, name, and 1 for the
-// tables of the block-sparse reduced solver (a wide plan has none: ba_plan.cpp, go_wide).  Each name is a vector of bt_plan, a
+// tables of the block-sparse reduced solver (a wide plan has none: ba_plan_solver.cpp, go_wide).  Each name is a vector of bt_plan, a
 // pointer of PlanDev and a name bt_plan_array answers to.
 #define BT_PLAN_TABLES(X)                                                                                                      \
     X(int32_t, kx, 0) X(uint32_t, act_bits, 0) X(int32_t, act_rank, 0) X(int32_t, pair_i, 0) X(int32_t, pair_j, 0)              \
@@ -267,6 +269,16 @@ struct Force {
 const Force &force();
 // BT_PLAN_PROF: time per planner phase on stderr (measurement)
 bool plan_prof();
+struct PhaseTimer {                // tick("name"): the time since the tick before, under the label of the phase that comes next
+    bool on = plan_prof();
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    void operator()(const char *name) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "plan phase before %s: %.3f ms\n", name, std::chrono::duration<double, std::milli>(now - prev).count());
+        prev = now;
+    }
+};
 // Tile counts from which the wave-per-tile kernels take a graph (k_edge2, k_stream; the environment overrides are for
 // measurement and tests).  The planner lays out their tables only for plans that will use them.
 int edge_min_tiles();
@@ -297,6 +309,15 @@ struct DevPlanStats {
     int pattern_words;
 };
 enum { BT_NEED_EDGES = 2 };
+// fn(frame) for every target frame of a track's masks, ascending (bit b of mask | mask2 << 64: frame base + b)
+template <class F> inline void for_targets(uint64_t mask, uint64_t mask2, int32_t base, F &&fn) {
+    for (uint64_t mk = mask; mk; mk &= mk - 1) fn((int32_t)(base + __builtin_ctzll(mk)));
+    for (uint64_t mk = mask2; mk; mk &= mk - 1) fn((int32_t)(base + 64 + __builtin_ctzll(mk)));
+}
+// The reduced camera system of a plan whose tiles, pairs and loose tracks are laid out (ba_plan_solver.cpp; called by
+// build_plan_host): the block-sparse solvers' tables, or `wide`.  `pk` / `E`: the packed edge list, read by a sharded plan
+// without `dstats` only.
+int plan_reduced_system(bt_plan *plan, bool sharded, const DevPlanStats *dstats, const uint64_t *pk, int64_t E, PhaseTimer &tick);
 int build_plan_host(const int64_t *ii, const int64_t *jj, const int64_t *kk, int64_t E,
                     int64_t n_buf, int64_t p_tot, int64_t fixedp, int64_t n_all_min,
                     int64_t own_lo, int64_t own_hi, bt_plan *plan, const uint64_t *packed = nullptr, bool keep_slots = false,

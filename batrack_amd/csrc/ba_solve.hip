@@ -645,7 +645,7 @@ __global__ __launch_bounds__(768) void k_solve_lds(PlanDev pd, StepArgs a) { sol
 
 // ------------------------------------------------------------------ k_solve_fused
 // The LDS-resident factorisation with ONE phase and one barrier per level (levels of at most
-// two columns: two-ended chains).  Updates are split by destination (ba_plan.cpp, fz_*):
+// two columns: two-ended chains).  Updates are split by destination (ba_plan_solver.cpp, fz_*):
 // "pending" = the destination column is factored in the very next level, "lazy" = later.
 //   diagonal wave  one per column: lanes 0..35 apply the pending updates to the column's diagonal
 //                  block (one element each) and publish it through LDS + a flag
@@ -739,7 +739,7 @@ constexpr int kFusedCols = 2;     // columns per level k_solve_fused and k_solve
 
 // The back substitution's level table, behind zt: one 8-byte word per (level, column slot, lane group g), so that a lane finds
 // everything the level asks of it at an address that depends on the level number alone — nothing to look up behind a record.
-//   .x  col | #sub-blocks << 8 | kBsSync (barrier before this level: ba_plan.cpp bs_sync) | kBsNoCol (the slot has no column)
+//   .x  col | #sub-blocks << 8 | kBsSync (barrier before this level: ba_plan_solver.cpp bs_sync) | kBsNoCol (the slot has no column)
 //   .y  sub-block g of the column: its block index | its row's column << 16; kBsNone: the column has no sub-block g (block 0
 //       and row 0 then: addresses that can be read, the values are thrown away)
 // kBsPad empty levels come first (levels -kBsPad .. -1): the loop reads ahead without asking where it is.
@@ -974,7 +974,7 @@ __device__ __forceinline__ void solve_fused_body(const PlanDev &pd, const StepAr
         __syncthreads();
         if (PROF) tload = clock64() - tall;
 
-        // wave-uniform packed level metadata in SGPRs (ba_plan.cpp: fz_pmeta): current, next and previous level
+        // wave-uniform packed level metadata in SGPRs (ba_plan_solver.cpp: fz_pmeta): current, next and previous level
         int c0a, c0b, c0c, c0d, c1a, c1b, c1c, c1d, n0a = 0, n0b = 0, n0c = 0, n0d = 0, n1a = 0, n1b = 0, n1c = 0, n1d = 0;
         int p0a = 0, p0b = 0, p0c = 0, p1a = 0, p1b = 0, p1c = 0, pnc = 0;
         auto take_next = [&](int l) {

@@ -12,7 +12,7 @@ namespace bt {
 // ------------------------------------------------------------------ k_pack_system
 // Dense [S | y] (caller order, lower triangle) <-> the plan's non-zero blocks in factor order followed by
 // y in factor order: the multi-GPU exchange buffer (include/batrack_ba.h: bt_ba_pack).  One thread per element.
-// block b of a WIDE plan's packed form (ba_plan.cpp: no symbolic factorisation, every lower block): b = rn (rn + 1) / 2 + cn
+// block b of a WIDE plan's packed form (ba_plan_solver.cpp: no symbolic factorisation, every lower block): b = rn (rn + 1) / 2 + cn
 __device__ __forceinline__ void wide_block(int b, int &rn, int &cn) {
     rn = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
     while ((rn + 1) * (rn + 2) / 2 <= b) ++rn;

@@ -378,7 +378,7 @@ def sparse_chol_solve_fused(A, S_lower, y, n, ep, lm):
 
 
 def pipe_schedule_applies(A):
-    """The plan-side condition of k_solve_pipe (ba_plan.cpp: fzp_ok)."""
+    """The plan-side condition of k_solve_pipe (ba_plan_solver.cpp: fzp_ok)."""
     col_ptr, lvl_ptr = A["col_ptr"], A["lvl_ptr"]
     n = len(col_ptr) - 1
     return (n > 0 and np.diff(lvl_ptr).max() <= 2 and np.diff(A["fz_pend_ptr"]).max(initial=0) <= 2 and
