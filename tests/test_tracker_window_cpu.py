@@ -121,6 +121,33 @@ def test_repack_is_a_permutation():
         tracker.pack_weights(torch.zeros(128, 128, 3, 3))
 
 
+def test_one_hot_convolutions_cover_every_pair_and_select_what_the_convolution_does():
+    """The limits suite's one-hot convolutions: every (input channel, tap) pair has a weight of 1 in some convolution, and
+    the expectation built by padding and slicing is what the restated convolution computes with those weights in float64."""
+    taps = U.one_hot_taps()
+    assert taps.shape == (U.ONE_HOT_CONVS, U.C, 3)
+    flat = (taps[..., 0] * 9 + taps[..., 1] * 3 + taps[..., 2]).flatten()
+    count = torch.bincount(flat, minlength=(U.C + U.EMB) * 9)
+    assert count.numel() == 1719 and int(count.min()) >= 1 and int((count - 1).sum()) == 73
+    assert int(taps[..., 0].max()) == 190 and int(taps[..., 1:].max()) == 2 and int(taps.min()) == 0
+    S, frame0, F, h, w = 3, 1, 2, 9, 17
+    g = torch.Generator().manual_seed(84)
+    fnet = torch.randn(F, U.C, h, w, generator=g, dtype=torch.float64)
+    dm = torch.rand(S, h, w, generator=g, dtype=torch.float64) * 17
+    zr = (dm.min(), dm.max())
+    inp = torch.cat([fnet, U.embedding(dm, zr)[frame0:frame0 + F]], 1)
+    worst = 0.0
+    for k in range(U.ONE_HOT_CONVS):
+        weight, bias = U.one_hot_weight(taps[k], torch.float64), torch.rand(U.C, generator=g, dtype=torch.float64) - 0.5
+        assert int((weight != 0).sum()) == U.C and float(weight.sum()) == U.C
+        want = U.one_hot_select(inp, taps[k]) + bias[None, :, None, None]
+        got = U.embed_conv(fnet, dm, zr, frame0, weight, bias)
+        worst = max(worst, float((got - want).abs().max()))
+        assert torch.equal(U.pack_weights(weight).permute(3, 0, 2, 1).reshape(U.C, 192, 3, 3)[:, :191], weight)
+    print(f"one-hot convolutions: max |conv2d - selection| {worst:.3e} (float64)")
+    assert worst <= 8 * 2.0 ** -53 * 5                              # values below 5 (|N(0, 1)| + |bias|): a few float64 roundings
+
+
 def test_repack_is_cached_on_pointer_and_version():
     from batrack_amd.frontend import tracker
     conv = torch.nn.Conv2d(191, 128, 3, padding=1)

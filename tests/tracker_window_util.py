@@ -174,6 +174,35 @@ def pack_weights(weight):
     return out
 
 
+# ------------------------------------------------------------------------------------- one-hot convolutions (the limits suite)
+ONE_HOT_CONVS = 14           # 14 x 128 = 1792 output channels for the 191 x 9 = 1719 (channel, tap) pairs: 73 pairs come twice
+
+
+def one_hot_taps(seed=83):
+    """[14, 128, 3] int64: the (c, ky, kx) whose weight is 1 for each output channel of each convolution.  Every pair of an
+    input channel and a tap occurs once, 73 drawn ones a second time, assigned to the output channels in a seeded shuffle."""
+    g = torch.Generator().manual_seed(seed)
+    pairs = (C + EMB) * 9
+    every = torch.cat([torch.arange(pairs), torch.randint(0, pairs, (ONE_HOT_CONVS * C - pairs,), generator=g)])
+    every = every[torch.randperm(every.numel(), generator=g)]
+    return torch.stack([every // 9, (every % 9) // 3, every % 3], -1).reshape(ONE_HOT_CONVS, C, 3)
+
+
+def one_hot_weight(taps, dtype=torch.float32):
+    """taps [128, 3] -> the weight [128, 191, 3, 3] that is zero except W[o, c(o), ky(o), kx(o)] = 1."""
+    w = torch.zeros(C, C + EMB, 3, 3, dtype=dtype)
+    w[torch.arange(C), taps[:, 0], taps[:, 1], taps[:, 2]] = 1
+    return w
+
+
+def one_hot_select(inp, taps):
+    """inp [F, 191 or fewer, h, w], taps [k, 3] -> [F, k, h, w]: in[f, c(o), y + ky(o) - 1, x + kx(o) - 1], zero outside the
+    map — what a one-hot convolution leaves of its input before the bias, by padding and slicing."""
+    h, w = inp.shape[-2:]
+    padded = Fn.pad(inp, (1, 1, 1, 1))
+    return torch.stack([padded[:, c, ky:ky + h, kx:kx + w] for c, ky, kx in taps.tolist()], 1)
+
+
 def forward(me, rgbds, queries, iters=4):
     """The window loop on a StandIn, in the dtype of `rgbds`; returns the reference's tuple.  rgbds is normalised in place."""
     dt, dev = rgbds.dtype, rgbds.device
