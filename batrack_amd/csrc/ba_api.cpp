@@ -432,6 +432,7 @@ static int clone_shifted(const bt_plan *src, const uint64_t *d_words, int64_t E,
     pl->info = src->info; pl->info.fixedp = fixedp; pl->info.n_all = src->info.n_all + di;
     pl->ws = src->ws; pl->off = src->off; pl->len = src->len; pl->dev_bytes = src->dev_bytes; pl->pk_off = src->pk_off; pl->pm_rounds = src->pm_rounds;
     pl->dev = src->dev;
+    pl->is_clone = 1;
     pl->k_hi = src->k_hi >= 0 ? src->k_hi + dk : -1;
     size_t cap = 0;
     hipEvent_t reuse_after = nullptr;
@@ -720,9 +721,11 @@ int bt_plan_get_info(const bt_plan *pl, bt_plan_info *info) {
 
 size_t bt_plan_workspace_bytes(const bt_plan *pl) { return pl ? pl->ws.total : 0; }
 
-// The tables bt_plan_array reads back from the plan's buffer: those the device wrote or amended (upload_plan)
+// The tables bt_plan_array reads back from the plan's buffer: those the device wrote or amended (upload_plan), and every
+// table of a shifted clone (clone_shifted: its host vectors are empty)
 static bool device_written(const bt_plan *pl, int t) {
     if (!pl->dev_base) return false;
+    if (pl->is_clone) return true;
     switch (t) {
     case tab::pm_edge: case tab::pm_rec: return pl->dev_pm != 0;
     case tab::slot_edge: case tab::slot_pair: case tab::slot_lab: case tab::slot_lp: case tab::tile_cut8: case tab::tile_cut16: return pl->dev_slots != 0;
@@ -758,15 +761,24 @@ int64_t bt_plan_array(const bt_plan *pl, const char *name, const void **data) {
         *data = pl->dev_readback.data();
         return 1;
     }
-    // an uploaded table: the host's vector, or — a table the device wrote — read back on request (tests, tooling)
+    // `count` elements of `esz` bytes at `off` of the plan's buffer, read back on request (tests, tooling).  A clone's copies
+    // and shift kernels are queued on the plan stream, which is non-blocking: a hipMemcpy on the null stream is not ordered
+    // behind it, so the stream is waited for (the plan's `ready` event is left alone: its hand-off is mark_launch's)
+    const auto readback = [&](size_t off, size_t count, size_t esz) -> int64_t {
+        const size_t bytes = count * esz;
+        std::vector<int32_t> &r = pl->dev_readback;
+        r.assign((bytes + 7) / 8 * 2, 0);
+        if (pl->is_clone && hipStreamSynchronize(copy_stream()) != hipSuccess) return -1;
+        if (bytes && hipMemcpy(r.data(), static_cast<const char *>(pl->dev_base) + off, bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        *data = r.data();
+        return (int64_t)count;
+    };
+    if (std::strcmp(name, "edge_words") == 0)                 // the kept packed edge list (kk << 32 | ii << 16 | jj, uint64), empty where none is kept
+        return readback(pl->pk_off, pl->dev_base && pl->pk_off ? (size_t)pl->dev.e_all : 0, sizeof(uint64_t));
+    // an uploaded table: the host's vector, or — a table the device wrote, any table of a clone — the buffer's
     const auto table = [&](int t, const auto &v) -> int64_t {
         if (!device_written(pl, t)) { *data = v.data(); return (int64_t)v.size(); }
-        const size_t bytes = pl->len[t] * sizeof(v[0]);
-        std::vector<int32_t> &r = pl->dev_readback;
-        r.assign((bytes + 3) / 4, 0);
-        if (hipMemcpy(r.data(), static_cast<const char *>(pl->dev_base) + pl->off[t], bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        *data = r.data();
-        return (int64_t)pl->len[t];
+        return readback(pl->off[t], pl->len[t], sizeof(v[0]));
     };
 #define BT_ARR(T, n, solver) if (std::strcmp(name, #n) == 0) return table(tab::n, pl->n);
     BT_PLAN_TABLES(BT_ARR)

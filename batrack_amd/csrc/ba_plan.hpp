@@ -214,6 +214,7 @@ struct bt_plan_scalars {
     int spec_epoch = 0;                                       // > 0: no event — the verdict is complete when spec_flag[2] holds this (bt_plan_spec_bind)
     void *spec_stream = nullptr;                              //   (the stream the comparison was launched on: what a poll that runs out of patience waits for)
     int spec_unbound = 0;                                     // made AHEAD of its list (bt_plan_preshift): no step before bt_plan_spec_bind
+    int is_clone = 0;                                         // made by clone_shifted (ba_api.cpp): the host vectors are empty, bt_plan_array reads every table from the buffer
     bt::PlanDev dev{};            // the planner's scalars; upload_plan adds the table pointers
 };
 

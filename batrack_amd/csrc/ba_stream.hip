@@ -247,14 +247,18 @@ __global__ __launch_bounds__(128, MODE == kModeFull ? BT_STREAM_FULL_WAVES : 4) 
         const int flags = tile == t_begin ? 0 : flags_t;
         const int R = 6 * rec.ncam;
         const bool has_next = tile + 1 < t_end;
-        // ---- new cameras / new pair list (the barrier at the end of the previous tile has passed: nobody reads the old ones)
-        if (MODE == kModeFull && !(flags & 1)) {
-            flush_schur();
+        // ---- new cameras / new pair list.  The flushes READ the old gidx / gpl, each wave for its own accumulators, and the
+        // new ones are written by whichever threads the loops below give them to (wave 0 alone for up to 64 rows / pairs): a
+        // barrier in between, or a wave still flushing sends the rest of its sums to the NEW tile's rows of S and pairs
+        const bool new_cams = MODE == kModeFull && !(flags & 1), new_pairs = !(flags & 2);
+        if (new_cams) flush_schur();
+        if (new_pairs) flush_pairs();
+        if (MODE == kModeFull && (new_cams || new_pairs)) __syncthreads();
+        if (new_cams) {
             const int *cams = pd.tile_cams + rec.cam0;
             for (int i = tid; i < R; i += 128) gidx[i] = 6 * cams[i / 6] + i % 6;
         }
-        if (!(flags & 2)) {
-            flush_pairs();
+        if (new_pairs) {
             for (int p = tid; p < rec.npair; p += 128) {
                 const int gp = pd.tile_pairs[rec.pair0 + p];
                 float *g = geo + p * GS;

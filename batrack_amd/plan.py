@@ -14,7 +14,7 @@ from . import _lib
 
 _USE_CTYPES = os.environ.get("BT_PY_BINDING", "") == "ctypes"      # measurement only: the ctypes route for every step
 
-_NP_TYPES = {"ws_layout": np.int64, "slot_lab": np.uint16, "slot_lp": np.uint8, "act_bits": np.uint32, "slot_code": np.uint16, "tile_la": np.uint8, "tile_sinfo": np.uint32, "tile_cut8": np.uint16, "tile_cut16": np.uint16, "pm_lb": np.uint8, "pm_la": np.uint8}
+_NP_TYPES = {"ws_layout": np.int64, "slot_lab": np.uint16, "slot_lp": np.uint8, "act_bits": np.uint32, "slot_code": np.uint16, "tile_la": np.uint8, "tile_sinfo": np.uint32, "tile_cut8": np.uint16, "tile_cut16": np.uint16, "pm_lb": np.uint8, "pm_la": np.uint8, "edge_words": np.uint64}
 PLAN_ARRAYS = ("kx", "trk_of_patch", "trk_loc", "pair_i", "pair_j", "tile_trk0", "tile_ntrk", "tile_ncam",
                "tile_cam0", "tile_slot0", "tile_nslot", "tile_erow0", "tile_cams", "slot_edge", "slot_pair",
                "slot_lab", "col_ptr", "row_idx", "upd_ptr", "upd", "blk_col", "upd_next", "perm", "blk_src",

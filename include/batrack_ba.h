@@ -107,7 +107,8 @@ int bt_plan_create(const int64_t *ii, const int64_t *jj, const int64_t *kk, int6
  * numbers shifted (one comparison kernel, one device-to-device copy, two small kernels: ~0.1 ms instead of ~1 ms) and BT_OK
  * is returned; otherwise BT_NO_MATCH (> 0) and *out = NULL: call bt_plan_create.  src must be an uploaded, unsharded plan
  * built from device indices (plans of up to 4M edges keep their packed edge list for this comparison); it is only read.
- * The new plan has no host arrays (bt_plan_array returns empty ones). */
+ * The new plan has no host arrays: bt_plan_array reads its tables back from the device buffer (and waits for the copies on
+ * the plan stream to do so); the two host-only names, "trk_of_patch" and "trk_loc", name no track there. */
 int bt_plan_create_shifted(const bt_plan *src, const int64_t *ii, const int64_t *jj, const int64_t *kk, int64_t E,
                            int64_t n_buf, int64_t p_tot, int64_t fixedp, bt_plan **out);
 /* The same against up to four candidate source plans at once (the caller's most recent plans, most likely first): the list is
@@ -155,7 +156,9 @@ size_t bt_plan_workspace_bytes(const bt_plan *plan);
  * count, or -1 for an unknown name.  Element type is int32 unless noted in
  * DESIGN.md ("slot_lab" is uint16). */
 int64_t bt_plan_array(const bt_plan *plan, const char *name, const void **data);
-/* Two more names of bt_plan_array, read-only (tests / tooling, not the step path):
+/* Three more names of bt_plan_array, read-only (tests / tooling, not the step path):
+ *   "edge_words"   E uint64: the packed edge list kk << 32 | ii << 16 | jj that an uploaded plan of device indices keeps in
+ *                  its buffer (what the next list is compared with, bt_plan_create_shifted); empty where none is kept
  *   "ws_layout"    4 int64: byte offsets in the workspace of the accumulators (sys), their length (zero_bytes: zero
  *                  after bt_ba_workspace_init and after every completed step), the status block (status, 1024 bytes),
  *                  and the workspace's size (total = bt_plan_workspace_bytes)
