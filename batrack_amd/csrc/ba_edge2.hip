@@ -796,7 +796,7 @@ static int launch_t(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEve
             }
         }
     }
-    const int max_waves = n_cu * per_cu;
+    const int max_waves = force().cap_waves(n_cu * per_cu);
     const int tpw = (pd.T + max_waves - 1) / max_waves, nw = (pd.T + tpw - 1) / tpw, nb = (nw + W - 1) / W;
     if (ev0) hipExtLaunchKernelGGL((k_edge2<NT, LGS, LOSS>), dim3(nb), dim3(64 * W), lds, st, ev0, ev1, 0, pd, a, tpw, (int)(lds_w / sizeof(double)));
     else hipLaunchKernelGGL((k_edge2<NT, LGS, LOSS>), dim3(nb), dim3(64 * W), lds, st, pd, a, tpw, (int)(lds_w / sizeof(double)));

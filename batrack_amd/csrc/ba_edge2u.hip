@@ -291,7 +291,7 @@ static int launch_u(const PlanDev &pd, const StepArgs &a, hipStream_t st, hipEve
         per_cu = nb;
         per_cu_c[dslot].store(nb, std::memory_order_relaxed); per_cu_lds[dslot].store(lds, std::memory_order_release);
     }
-    const int max_waves = dp.n_cu * per_cu;
+    const int max_waves = force().cap_waves(dp.n_cu * per_cu);
     const int tpw = (pd.T + max_waves - 1) / max_waves, nw = (pd.T + tpw - 1) / tpw;
     if (ev0) hipExtLaunchKernelGGL((k_edge2u<MODE, LGS, LOSS>), dim3(nw), dim3(64), lds, st, ev0, ev1, 0, pd, a, tpw);
     else hipLaunchKernelGGL((k_edge2u<MODE, LGS, LOSS>), dim3(nw), dim3(64), lds, st, pd, a, tpw);

@@ -55,6 +55,7 @@ const Force &force() {
             else if (tok == "plan=host") r.host_plan = 1; else if (tok == "wpt=0") r.wpt_off = 1;
             else if (tok == "upd=split") r.upd_split = 1;
             else if (tok.rfind("updwg=", 0) == 0 && std::atoi(tok.c_str() + 6) > 0) r.upd_wgs = std::atoi(tok.c_str() + 6);
+            else if (tok.rfind("wptwaves=", 0) == 0 && std::atoi(tok.c_str() + 9) >= 0) r.wpt_waves = std::atoi(tok.c_str() + 9);
             else if (!tok.empty()) std::fprintf(stderr, "batrack: unknown BT_FORCE token '%s'\n", tok.c_str());
         }
         return r;

@@ -261,11 +261,15 @@ namespace bt {
 //   upd=split                                      solver and k_update as two launches where the route would fuse them (A/B, tests)
 //   updwg=N                                        at most N update workgroups in the fused launch, so that a small graph puts
 //                                                  several tiles on one workgroup (test hook only)
+//   wptwaves=N                                     at most N waves in the launches of k_edge2, k_edge2u and k_stream, so that a small
+//                                                  graph puts several tiles on one wave (test hook only; nothing else of a launch changes)
 struct Force {
     int kernel = -1;        // -1 the plan's own choice, 0 k_tile, 1 k_stream, 2 k_edge2, 3 k_etile
     int solver = -1;        // -1 default, 0 k_solve_fused (barrier per level), 1 k_solve_lds<double>, 2 k_solve_lds<float>, 3 k_solve_global
     int natural_order = 0, f32_edges = 0, tile_wide = -1, host_plan = 0, wpt_off = 0;
     int upd_split = 0, upd_wgs = 0;     // upd=split; updwg=N (0: no cap)
+    int wpt_waves = 0;                  // wptwaves=N (0: no cap)
+    int cap_waves(int max_waves) const { return wpt_waves > 0 && wpt_waves < max_waves ? wpt_waves : max_waves; }
 };
 const Force &force();
 // BT_PLAN_PROF: time per planner phase on stderr (measurement)

@@ -541,7 +541,7 @@ static int launch_stream_t(const PlanDev &pd, const StepArgs &a, hipStream_t st,
         per_cu = nb;
         per_cu_c[dslot].store(nb, std::memory_order_relaxed); per_cu_lds[dslot].store(lds, std::memory_order_release);
     }
-    const int max_waves = n_cu * per_cu;
+    const int max_waves = force().cap_waves(n_cu * per_cu);
     const int tpw = (pd.T + max_waves - 1) / max_waves, nw = (pd.T + tpw - 1) / tpw;
     if (ev0) hipExtLaunchKernelGGL((k_stream<MODE, NT, PROF>), dim3(nw), dim3(128), lds, st, ev0, ev1, 0, pd, a, tpw);
     else hipLaunchKernelGGL((k_stream<MODE, NT, PROF>), dim3(nw), dim3(128), lds, st, pd, a, tpw);
