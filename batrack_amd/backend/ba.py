@@ -108,7 +108,7 @@ def _speculate(ii, jj, kk, n_buf, p_tot, fixedp, probe=False):
     for st, _ in reversed(cached):
         inf = st.plan.info
         if (inf["E"] == E and inf["n_buf"] == nb and inf["p_tot"] == pt and fp - inf["fixedp"] == _LAST_SHIFT[0]
-                and not st.plan.__dict__.get("speculative")):
+                and not st.plan.speculative):
             if probe:                         # (prefetch_plan asking: is there a clone made ahead for this list?  Nothing is touched)
                 pre = _PRE.get(id(st))
                 return (pre[1], st.ws) if pre is not None and pre[0] is st and pre[1].plan.info["fixedp"] == fp else None
@@ -181,7 +181,7 @@ def _preshift(stepper):
     if stepper._repeats + 1 < at:
         return
     df = _LAST_SHIFT[0]
-    if df is None or stepper.plan.__dict__.get("speculative"):
+    if df is None or stepper.plan.speculative:
         return
     stepper._pre_tried = True
     if os.environ.get("BT_PLAN_SHIFT", "1") == "0" or os.environ.get("BT_PLAN_SPECULATE", "1") == "0" or os.environ.get("BT_PLAN_PRESHIFT", "1") == "0":
@@ -356,7 +356,7 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
         else:
             # a per-track tensor is checked against the plan's track count: a speculative clone carries its SOURCE's count, so
             # the speculation is settled first (a wrong guess is rebuilt here, before anything is enqueued)
-            if stepper.plan.__dict__.get("speculative") and not _confirm(stepper):
+            if stepper.plan.speculative and not _confirm(stepper):
                 stepper = _plan_for(ii, jj, kk, n_buf, p_tot, fixedp, dev)
         if isinstance(lmbda, float):
             pass
@@ -374,7 +374,7 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
                                                        float(alpha), _lib.LOSS[loss], so, lm_trk)
         if PRINT:
             _print_residual(poses, patches, intrinsics, targets_2d, ii, jj, kk, bounds)
-        if stepper.plan.__dict__.get("speculative") and not _confirm(stepper):
+        if stepper.plan.speculative and not _confirm(stepper):
             # the list was no shifted copy after all: what was just enqueued is void (the inputs are untouched) — once more, properly
             return BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targets_disp, weights, lmbda_in, ii, jj, kk, bounds,
                                  ep=ep, PRINT=False, fixedp=fixedp, structure_only=structure_only, loss=loss, alpha=alpha)
@@ -406,7 +406,7 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
                  bounds, lmbda, ep, alpha, loss, so, lmbda_per_track=lm_trk)
     if PRINT:
         _print_residual(poses, patches, intrinsics, targets_2d, ii, jj, kk, bounds)
-    if stepper.plan.__dict__.get("speculative") and not _confirm(stepper):
+    if stepper.plan.speculative and not _confirm(stepper):
         return BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targets_disp, weights, lmbda_in, ii, jj, kk, bounds,
                              ep=ep, PRINT=False, fixedp=fixedp, structure_only=structure_only, loss=loss, alpha=alpha)
     if _REPEAT[0]:

@@ -1,5 +1,5 @@
 // ba_plan.hpp — structure of one BA edge list, shared by the host planner
-// (ba_plan.cpp), the kernels (ba_tile.hip and the other ba_*.hip) and the C ABI (ba_api.cpp).
+// (ba_plan.cpp), the kernels (ba_tile.hip and the other ba_*.hip) and the C ABI (ba_api.cpp, plan_shift.cpp).
 #pragma once
 #include <array>
 #include <atomic>
@@ -184,6 +184,22 @@ enum : int { BT_PLAN_TABLES(BT_TAB_ID) kCount };
 }  // namespace tab
 constexpr int kNumTables = tab::kCount;
 
+// Where a shifted clone stands with the proof that its list is the one it was made for (plan_shift.cpp).  Host side only.
+struct SpecState {
+    enum State : int {
+        kNone,       // no speculation, or one that bt_plan_spec_confirm has settled
+        kUnbound,    // made AHEAD of its list (bt_plan_preshift): no step before bt_plan_spec_bind
+        kPolled,     // bound: no event — the verdict is complete when flag[2] holds `epoch` (bt_plan_spec_bind)
+        kEvent       // the verdict lies behind `event` (bt_plan_create_shifted_spec)
+    };
+    State state = kNone;
+    int *flag = nullptr;          // the verdict's pinned ints: [0] list differs, [1] index out of range, [2] the epoch of a polled one
+    void *event = nullptr;        // kEvent: a hipEvent_t
+    int epoch = 0;                // kPolled: > 0
+    void *stream = nullptr;       // kPolled: the stream the comparison was launched on — what a poll that runs out of patience waits for
+    bool unsettled() const { return state != kNone; }      // neither a shift source nor a confirmed plan
+};
+
 }  // namespace bt
 
 // All of a plan but its vectors: what bt_plan::recycle resets in one assignment.  The scalars the kernels read live in `dev` only.
@@ -208,13 +224,9 @@ struct bt_plan_scalars {
     mutable void *last_stream = nullptr;
     mutable bool launched = false;
     size_t dev_cap = 0;
-    int64_t k_hi = -1;                                        // largest patch index the plan's tables hold (bt_plan_create_shifted_spec checks k_hi + dk < p_tot)
-    void *spec_ev = nullptr;                                  // hipEvent_t behind the verdict of a speculative clone (bt_plan_spec_confirm), else null
-    int *spec_flag = nullptr;                                 // its two pinned ints: list differs / index out of range
-    int spec_epoch = 0;                                       // > 0: no event — the verdict is complete when spec_flag[2] holds this (bt_plan_spec_bind)
-    void *spec_stream = nullptr;                              //   (the stream the comparison was launched on: what a poll that runs out of patience waits for)
-    int spec_unbound = 0;                                     // made AHEAD of its list (bt_plan_preshift): no step before bt_plan_spec_bind
-    int is_clone = 0;                                         // made by clone_shifted (ba_api.cpp): the host vectors are empty, bt_plan_array reads every table from the buffer
+    int64_t k_hi = -1;                                        // largest patch index the plan's tables hold (plan_shift.cpp: shift_fits checks k_hi + dk < p_tot)
+    bt::SpecState spec{};                                     // a speculative clone's state (bt_plan_spec_confirm settles it)
+    int is_clone = 0;                                         // made by clone_shifted (plan_shift.cpp): the host vectors are empty, bt_plan_array reads every table from the buffer
     bt::PlanDev dev{};            // the planner's scalars; upload_plan adds the table pointers
 };
 
@@ -274,13 +286,16 @@ struct Force {
 const Force &force();
 // BT_PLAN_PROF: time per planner phase on stderr (measurement)
 bool plan_prof();
-struct PhaseTimer {                // tick("name"): the time since the tick before, under the label of the phase that comes next
+// tick("name"): the time since the tick before.  The planner's lines carry the label of the phase that comes next ("plan phase
+// before"), the C ABI's (PhaseTimer tick{"plan api"}) that of the work just done.
+struct PhaseTimer {
+    const char *prefix = "plan phase before";
     bool on = plan_prof();
     std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
     void operator()(const char *name) {
         if (!on) return;
         const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "plan phase before %s: %.3f ms\n", name, std::chrono::duration<double, std::milli>(now - prev).count());
+        std::fprintf(stderr, "%s %s: %.3f ms\n", prefix, name, std::chrono::duration<double, std::milli>(now - prev).count());
         prev = now;
     }
 };
@@ -354,6 +369,7 @@ int plan_device_slots_fill(const bt_plan *pl, int64_t E, int32_t *d_slot_edge, i
                            uint16_t *d_cut8, uint16_t *d_cut16, void *stream, const DevWptOut *wpt = nullptr);
 // after the stream of plan_device_slots_fill has been waited for: 1 = some tile is not slot-uniform (no k_edge2 for this plan)
 int plan_device_em_verdict();
-// Copies the arrays to the device and fills plan->dev (ba_api.cpp).
-int upload_plan(bt_plan *plan);
+// Copies the arrays to the device and fills plan->dev (ba_api.cpp).  `d_packed` (optional): the packed edge list on the device,
+// kept behind the tables where the plan may become a shift source.
+int upload_plan(bt_plan *plan, const uint64_t *d_packed = nullptr);
 }  // namespace bt

@@ -32,8 +32,38 @@ def wave_per_tile_kernels(enable=None):
     return bool(_lib.lib().bt_config_wave_per_tile_kernels(-1 if enable is None else int(bool(enable))))
 
 
+def _raw_stream(device):
+    """hipStream_t of PyTorch's current stream on `device` (without building a Stream object per call: that costs more than
+    the C calls it is made for)."""
+    import torch
+    try:
+        return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
+    except AttributeError:
+        return torch.cuda.current_stream(device).cuda_stream
+
+
+def _dev_i64(tensors, contiguous=False):
+    """True where every one of `tensors` is an int64 torch tensor on a GPU — with `contiguous`, one the library can read in place
+    (for the callers that must not copy: their tensors are read by kernels queued without a host wait)."""
+    import torch
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and (not contiguous or t.is_contiguous())):
+            return False
+    return True
+
+
+def _read_info(lib, h):
+    info = _lib.PlanInfo()
+    _lib.check(lib.bt_plan_get_info(h, ctypes.byref(info)), "bt_plan_get_info")
+    return {n: int(getattr(info, n)) for n, _ in _lib.PlanInfo._fields_}
+
+
 class Plan:
     """bt_plan handle.  ii/jj/kk: int64 torch tensors (CPU or GPU) or numpy arrays."""
+
+    # The state of a speculative clone (shifted_spec, preshift): `speculative` until confirm() has said yes, `unbound` until a
+    # clone made ahead of its list was given it (bind), `invalid` once confirm() has said no.  False on every other plan.
+    speculative = unbound = invalid = False
 
     def __init__(self, ii, jj, kk, n_buf, p_tot, fixedp, upload=True, n_all_min=0, own=(0, 0), sync=True):
         L = _lib.lib()
@@ -61,10 +91,22 @@ class Plan:
                               int(n_all_min), int(own[0]), int(own[1]), on_device, 1 if upload else 0, ctypes.byref(self._h))
         _lib.check(rc, "bt_plan_create")
         self._keep = None
-        info = _lib.PlanInfo()
-        _lib.check(L.bt_plan_get_info(self._h, ctypes.byref(info)), "bt_plan_get_info")
-        self.info = {n: int(getattr(info, n)) for n, _ in _lib.PlanInfo._fields_}
+        self.info = _read_info(L, self._h)
         self.uploaded = bool(upload)
+
+    @classmethod
+    def _wrap(cls, lib, h, info, df=0, keep=None, speculative=False, unbound=False):
+        """The uploaded plan behind handle `h` (a shifted clone: no __init__).  `info`, `df`: its figures are its source's but for the
+        two that a shift by `df` frames moves (no bt_plan_get_info: the clones are made on the critical path of every frame); df = 0:
+        `info` is the clone's own.  `keep`: tensors that kernels still queued read."""
+        self = cls.__new__(cls)
+        self._lib, self._h, self._keep, self.uploaded = lib, h, keep, True
+        self.info = dict(info, fixedp=info["fixedp"] + df, n_all=info["n_all"] + df) if df else info
+        if speculative:
+            self.speculative = True
+        if unbound:
+            self.unbound = True
+        return self
 
     @classmethod
     def shifted(cls, src, ii, jj, kk, n_buf, p_tot, fixedp, sync=True):
@@ -72,9 +114,9 @@ class Plan:
         another (the caller's sliding window in steady state): a device-side copy of `src`'s tables with those numbers
         shifted, no host analysis (bt_plan_create_shifted).  Returns None when the list is no such copy."""
         import torch
-        if not (src.uploaded and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 for t in (ii, jj, kk))):
+        if not (src.uploaded and _dev_i64((ii, jj, kk))):
             return None
-        arrs = [a.contiguous() for a in (ii, jj, kk)]
+        arrs = [a.contiguous() for a in (ii, jj, kk)]                # (a copy is fine here: the call below waits for the device)
         if arrs[0].numel() != src.E:
             return None
         if sync:
@@ -85,13 +127,7 @@ class Plan:
         if rc > 0:
             return None
         _lib.check(rc, "bt_plan_create_shifted")
-        self = cls.__new__(cls)
-        self._lib, self._h, self._keep = src._lib, h, None
-        info = _lib.PlanInfo()
-        _lib.check(self._lib.bt_plan_get_info(self._h, ctypes.byref(info)), "bt_plan_get_info")
-        self.info = {n: int(getattr(info, n)) for n, _ in _lib.PlanInfo._fields_}
-        self.uploaded = True
-        return self
+        return cls._wrap(src._lib, h, _read_info(src._lib, h))
 
     @classmethod
     def shifted_any(cls, srcs, ii, jj, kk, n_buf, p_tot, fixedp, sync=True):
@@ -100,9 +136,9 @@ class Plan:
         candidates that were never uploaded are skipped here, so a position would not be one in the caller's list."""
         import torch
         srcs = [s for s in srcs if s.uploaded][:4]
-        if not srcs or not (ii.is_cuda and ii.dtype == jj.dtype == kk.dtype == torch.int64 and jj.is_cuda and kk.is_cuda):
+        if not srcs or not _dev_i64((ii, jj, kk)):
             return None, None
-        arrs = [a if a.is_contiguous() else a.contiguous() for a in (ii, jj, kk)]
+        arrs = [a.contiguous() for a in (ii, jj, kk)]
         if sync:
             torch.cuda.current_stream(arrs[0].device).synchronize()
         lib = srcs[0]._lib
@@ -113,14 +149,8 @@ class Plan:
         if rc > 0:
             return None, None
         _lib.check(rc, "bt_plan_create_shifted_any")
-        self = cls.__new__(cls)
-        self._lib, self._h, self._keep = lib, h, None
-        # (the clone's figures are its source's but for the two the shift moves: this is on the critical path of every frame)
         matched = srcs[which.value]
-        src = matched.info
-        self.info = dict(src, fixedp=int(fixedp), n_all=src["n_all"] + int(fixedp) - src["fixedp"])
-        self.uploaded = True
-        return self, matched
+        return cls._wrap(lib, h, matched.info, int(fixedp) - matched.info["fixedp"]), matched
 
     @classmethod
     def shifted_spec(cls, src, ii, jj, kk, n_buf, p_tot, fixedp):
@@ -128,58 +158,38 @@ class Plan:
         synchronisation, no host wait — the comparison that proves the assumption runs on the GPU beside the clone's copies.
         The plan can be stepped at once; `confirm()` must be called before its results are used (it returns False where the
         assumption was wrong: discard the plan and what it computed).  None where the shift is not of that form."""
-        import torch
-        if not (src.uploaded and ii.is_cuda and jj.is_cuda and kk.is_cuda and ii.dtype == jj.dtype == kk.dtype == torch.int64
-                and ii.is_contiguous() and jj.is_contiguous() and kk.is_contiguous()):
+        if not (src.uploaded and _dev_i64((ii, jj, kk), contiguous=True)):       # (no copy: nothing here waits for one to be made)
             return None
         h = ctypes.c_void_p()
-        # (the raw handle of the current stream: building a torch.cuda.Stream object for it costs more than the C call's share)
-        stream = torch._C._cuda_getCurrentRawStream(ii.device.index if ii.device.index is not None else torch.cuda.current_device())
         rc = src._lib.bt_plan_create_shifted_spec(src._h, ii.data_ptr(), jj.data_ptr(), kk.data_ptr(), ii.numel(), int(n_buf), int(p_tot),
-                                                  int(fixedp), stream, ctypes.byref(h))
+                                                  int(fixedp), _raw_stream(ii.device), ctypes.byref(h))
         if rc > 0:
             return None
         _lib.check(rc, "bt_plan_create_shifted_spec")
-        self = cls.__new__(cls)
-        self._lib, self._h, self._keep = src._lib, h, (ii, jj, kk)       # (the index tensors are read by kernels still queued)
-        s = src.info
-        self.info = dict(s, fixedp=int(fixedp), n_all=s["n_all"] + int(fixedp) - s["fixedp"])
-        self.uploaded = True
-        self.speculative = True
-        return self
+        # (keep: the index tensors are read by kernels still queued)
+        return cls._wrap(src._lib, h, src.info, int(fixedp) - src.info["fixedp"], keep=(ii, jj, kk), speculative=True)
 
     @classmethod
     def preshift(cls, src, df):
         """The clone of `src` for a list that does not exist yet: src's moved up by `df` frames (bt_plan_preshift) — enqueued now, on
         the library's plan stream, so that the call that brings the list only has to `bind` it.  None where no such shift fits the
         buffers.  The plan cannot be stepped before `bind`."""
-        if not src.uploaded or src.__dict__.get("speculative"):
+        if not src.uploaded or src.speculative:
             return None
         h = ctypes.c_void_p()
         rc = src._lib.bt_plan_preshift(src._h, int(df), ctypes.byref(h))
         if rc > 0:
             return None
         _lib.check(rc, "bt_plan_preshift")
-        self = cls.__new__(cls)
-        self._lib, self._h, self._keep = src._lib, h, None
-        s = src.info
-        self.info = dict(s, fixedp=s["fixedp"] + int(df), n_all=s["n_all"] + int(df))
-        self.uploaded = True
-        self.speculative = True
-        self.unbound = True
-        return self
+        return cls._wrap(src._lib, h, src.info, int(df), speculative=True, unbound=True)
 
     def bind(self, ii, jj, kk, n_buf, p_tot, fixedp):
         """Give a pre-shifted clone its list (bt_plan_spec_bind: one comparison kernel, no host wait).  True: step it, then `confirm()`
         as after `shifted_spec`.  False: the list cannot be the one the clone was made for (size, buffers or fixedp differ)."""
-        import torch
-        if not self.__dict__.get("unbound"):
+        if not (self.unbound and _dev_i64((ii, jj, kk), contiguous=True)):
             return False
-        if not (ii.is_cuda and jj.is_cuda and kk.is_cuda and ii.dtype == jj.dtype == kk.dtype == torch.int64
-                and ii.is_contiguous() and jj.is_contiguous() and kk.is_contiguous()):
-            return False
-        stream = torch._C._cuda_getCurrentRawStream(ii.device.index if ii.device.index is not None else torch.cuda.current_device())
-        rc = self._lib.bt_plan_spec_bind(self._h, ii.data_ptr(), jj.data_ptr(), kk.data_ptr(), ii.numel(), int(n_buf), int(p_tot), int(fixedp), stream)
+        rc = self._lib.bt_plan_spec_bind(self._h, ii.data_ptr(), jj.data_ptr(), kk.data_ptr(), ii.numel(), int(n_buf), int(p_tot), int(fixedp),
+                                         _raw_stream(ii.device))
         if rc > 0:
             return False
         _lib.check(rc, "bt_plan_spec_bind")
@@ -189,9 +199,9 @@ class Plan:
 
     def confirm(self):
         """True: the plan is the list's plan (always, unless it came from `shifted_spec`).  False: the speculation failed."""
-        if not self.__dict__.get("speculative"):
+        if not self.speculative:
             return True
-        if self.__dict__.get("invalid"):
+        if self.invalid:
             return False
         rc = self._lib.bt_plan_spec_confirm(self._h)
         self._keep = None
@@ -272,15 +282,6 @@ class Plan:
 
 
 _WS_STREAM = {}            # workspace address -> raw stream it was last handed to a Stepper under
-
-
-def _raw_stream(device):
-    """hipStream_t of PyTorch's current stream on `device` (without building a Stream object per call)."""
-    import torch
-    try:
-        return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
-    except AttributeError:
-        return torch.cuda.current_stream(device).cuda_stream
 
 
 class Stepper:

@@ -99,6 +99,48 @@ def test_error_codes_not_crashes():
     L.bt_plan_destroy(None)
 
 
+def test_shifted_family_refusals_before_any_hip_call():
+    """The refusals of bt_plan_create_shifted{,_any,_spec}, bt_plan_preshift, bt_plan_spec_bind and bt_plan_spec_confirm that are
+    decided before anything touches the device, on a host-only plan: the return code of each, and that `*out` / `*which` are
+    overwritten where the call has them."""
+    L = _lib.lib()
+    OK, EINVAL, NO_MATCH = _lib.BT_OK, _lib.BT_EINVAL, 1
+    vp = ctypes.c_void_p
+    ii, jj, kk = np.array([0, 1], np.int64), np.array([1, 0], np.int64), np.array([0, 4], np.int64)
+    I, J, K = ii.ctypes.data, jj.ctypes.data, kk.ctypes.data
+    h = vp()
+    assert L.bt_plan_create(I, J, K, 2, 4, 8, 1, 0, 0, 0, 0, 0, ctypes.byref(h)) == OK
+
+    def out():                                        # a non-null start value the call has to overwrite
+        return vp(1)
+
+    o = out()
+    assert L.bt_plan_create_shifted_spec(h, I, J, K, 2, 4, 8, 2, None, ctypes.byref(o)) == NO_MATCH and o.value is None
+    assert L.bt_plan_create_shifted_spec(None, I, J, K, 2, 4, 8, 2, None, ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_create_shifted_spec(h, I, J, K, 2, 4, 8, 2, None, None) == EINVAL
+    assert L.bt_plan_create_shifted_spec(h, I, J, K, 0, 4, 8, 2, None, ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_create_shifted_spec(h, I, J, K, 2, 32769, 32769, 2, None, ctypes.byref(out())) == NO_MATCH
+    assert L.bt_plan_create_shifted_spec(h, I, J, K, 2, 4, 9, 2, None, ctypes.byref(out())) == NO_MATCH
+    o = out()
+    assert L.bt_plan_preshift(h, 1, ctypes.byref(o)) == NO_MATCH and o.value is None
+    assert L.bt_plan_preshift(None, 1, ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_preshift(h, 1, None) == EINVAL
+    one, null = (vp * 1)(h), (vp * 1)(None)
+    o, which = out(), ctypes.c_int32(7)
+    assert L.bt_plan_create_shifted_any(one, 1, I, J, K, 2, 4, 8, 2, ctypes.byref(which), ctypes.byref(o)) == NO_MATCH
+    assert which.value == -1 and o.value is None
+    assert L.bt_plan_create_shifted_any(null, 1, I, J, K, 2, 4, 8, 2, ctypes.byref(which), ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_create_shifted_any(one, 0, I, J, K, 2, 4, 8, 2, ctypes.byref(which), ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_create_shifted_any(one, 1, I, J, K, 2, 32769, 32769, 2, ctypes.byref(which), ctypes.byref(out())) == NO_MATCH
+    assert L.bt_plan_create_shifted(h, I, J, K, 2, 4, 8, 2, ctypes.byref(out())) == NO_MATCH
+    assert L.bt_plan_create_shifted(None, I, J, K, 2, 4, 8, 2, ctypes.byref(out())) == EINVAL
+    assert L.bt_plan_spec_bind(h, I, J, K, 2, 4, 8, 1, None) == EINVAL          # not made ahead of its list
+    assert L.bt_plan_spec_bind(None, I, J, K, 2, 4, 8, 1, None) == EINVAL
+    assert L.bt_plan_spec_confirm(h) == OK
+    assert L.bt_plan_spec_confirm(None) == EINVAL
+    L.bt_plan_destroy(h)
+
+
 def test_unsupported_graphs_are_reported():
     L = _lib.lib()
     h = ctypes.c_void_p()

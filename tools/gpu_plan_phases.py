@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phases of ONE plan build (BT_PLAN_PROF / BT_PLAN_API_PROF on stderr): `large` = 8.4M edges, optional `shard` = rank 3 of 8."""
+"""Phases of ONE plan build (BT_PLAN_PROF: the planner's "plan phase before ..." and the C ABI's "plan api ..." lines on stderr): `large` = 8.4M edges, optional `shard` = rank 3 of 8."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
