@@ -1,8 +1,8 @@
 """`BA_rgbd_droid` — the reference's bundle-adjustment entry point
-(/root/reference/main/backend/ba.py:217-339), same signature and argument
+(main/backend/ba.py:217-339), same signature and argument
 meaning, executed by the gfx950 kernels behind include/batrack_ba.h.
 
-Called exactly as BATRACK.update() does (/root/reference/main/batrack.py:869-875):
+Called exactly as BATRACK.update() does (main/batrack.py:869-875):
 
     Gs, patches = BA_rgbd_droid(Gs, patches, patches_monodisp, intrinsics,
                                 targets_3d[..., :2], targets_3d[..., 2:], weights, lmbda,
@@ -28,199 +28,284 @@ from .. import _lib
 from ..plan import Plan, Stepper
 from .lietorch import SE3
 
-_CACHE = {}          # key -> (stepper, (weakref ii, jj, kk))
-_CACHE_MAX = 8
-_PENDING = {}        # key -> (future, result box, (ii, jj, kk)): plans being built by prefetch_plan
-_LAST_SHIFT = [None]  # frame shift of the last plan that was made as a shifted copy
-_PRE = {}            # id(source stepper) -> (source stepper, its clone for the NEXT list, made ahead: Plan.preshift) — a handful at most
 _WORKER = None       # one long-lived host thread (the planner keeps edge-sized scratch per thread)
+_cuda = torch.cuda   # (the waits for the index tensors go through this name: a test of the cache's policy puts a fake there)
+
+# How far down the ladder a new list's plan may be looked for: built only, as a shifted copy of a cached plan, as a copy ASSUMED to
+# be one (no wait for the comparison), as such a copy made AHEAD of the list.  Each rung above the first has its switch.
+BUILD_ONLY, SHIFTED, SPECULATIVE, AHEAD = range(4)
+_SWITCHES = ("BT_PLAN_SHIFT", "BT_PLAN_SPECULATE", "BT_PLAN_PRESHIFT")
+
+
+def _ladder(upto=AHEAD):
+    """How far the ladder goes, as far as `upto`.  The switches are read when the decision is made (tests and tools flip them between
+    calls), and no more of them than the caller asks about (a read costs most of a microsecond)."""
+    for rung in range(upto):
+        if os.environ.get(_SWITCHES[rung], "1") == "0":
+            return rung
+    return upto
+
+
+def _ident(ii, jj, kk):
+    """What an in-place edit or a reallocation of the index tensors changes (their identity is checked beside it)."""
+    return (ii._version, jj._version, kk._version, ii.data_ptr(), jj.data_ptr(), kk.data_ptr())
 
 
 def _key(ii, jj, kk, n_buf, p_tot, fixedp, device):
-    return (id(ii), id(jj), id(kk), ii._version, jj._version, kk._version,
-            ii.data_ptr(), jj.data_ptr(), kk.data_ptr(), ii.numel(), int(fixedp), int(n_buf), int(p_tot), str(device))
+    return (id(ii), id(jj), id(kk)) + _ident(ii, jj, kk) + (ii.numel(), int(fixedp), int(n_buf), int(p_tot), str(device))
 
 
-def _store(key, stepper, ii, jj, kk):
-    if len(_CACHE) >= _CACHE_MAX:
-        old = _CACHE.pop(next(iter(_CACHE)))
-        _PRE.pop(id(old[0]), None)                # (a clone made ahead from a plan that has left the cache is of no use either)
-    _CACHE[key] = (stepper, tuple(weakref.ref(t) for t in (ii, jj, kk)))
+class _Entry:
+    """One cached plan."""
+    __slots__ = ("stepper", "refs", "calls", "pre_tried")
+
+    def __init__(self, stepper, ii, jj, kk):
+        self.stepper = stepper
+        self.refs = tuple(weakref.ref(t) for t in (ii, jj, kk))   # the list the plan is of (a key's id()s may be another tensor's by now)
+        self.calls = 0               # calls that found the plan in place, counted behind their steps
+        self.pre_tried = False       # the clone ahead has been decided on (made or not): once per plan
 
 
-_CALLS_BEFORE = [0]  # how many calls the previous edge list got (an update() makes 2 x ITER): decides when the next clone is made
-_REPEAT = [False]    # the call in progress found the plan of the call before it in place (not the first call of an update())
-_LAST = [None]       # (ii, jj, kk, versions, fixedp, n_buf, p_tot, device, stepper) of the last call: an update() makes 2*ITER calls on one list
+class _Call:
+    """The last call's list and plan: an update() makes 2 x ITER calls on one list."""
+    __slots__ = ("entry", "ii", "jj", "kk", "ident", "fixedp", "n_buf", "p_tot", "device")
+
+    def __init__(self, entry, ii, jj, kk, fixedp, n_buf, p_tot, device):
+        self.entry, self.ii, self.jj, self.kk, self.ident = entry, ii, jj, kk, _ident(ii, jj, kk)
+        self.fixedp, self.n_buf, self.p_tot, self.device = fixedp, n_buf, p_tot, device
 
 
-def _plan_for(ii, jj, kk, n_buf, p_tot, fixedp, device):
-    """One plan per (edge list, fixedp): the caller keeps self.ii/jj/kk alive and
-    unmodified across the 2*ITER calls of an update() (batrack.py:869-875) and
-    replaces the tensors when edges are appended/removed (batrack.py:189-204)."""
-    last = _LAST[0]
-    if (last is not None and last[0] is ii and last[1] is jj and last[2] is kk and last[3] == (ii._version, jj._version, kk._version, ii.data_ptr(), jj.data_ptr(), kk.data_ptr())
-            and last[4] == fixedp and last[5] == n_buf and last[6] == p_tot and last[7] == device):
-        _REPEAT[0] = True
-        return last[8]
-    _REPEAT[0] = False
-    if last is not None:
-        _CALLS_BEFORE[0] = last[8].__dict__.get("_repeats", 0) + 1
-    stepper = _plan_lookup(ii, jj, kk, n_buf, p_tot, fixedp, device)
-    _LAST[0] = (ii, jj, kk, (ii._version, jj._version, kk._version, ii.data_ptr(), jj.data_ptr(), kk.data_ptr()), fixedp, n_buf, p_tot, device, stepper)
-    return stepper
+class PlanCache:
+    """The plans behind `BA_rgbd_droid`, one per (edge list, fixedp): the caller keeps self.ii/jj/kk alive and unmodified across the
+    2*ITER calls of an update() (batrack.py:869-875) and replaces the tensors when edges are appended / removed (batrack.py:189-204).
 
+    Threads: `prefetch(background=True)` runs its `build` on the worker thread — `_build(speculate=False)`, i.e. the synchronous
+    shifted copy or the planner, and the `Stepper` around the plan.  That reads a snapshot of `plans` (`_candidates`) and may set
+    `last_shift`; the caller's thread takes the result from the pending entry's box.  All else belongs to the caller's thread."""
 
-def _plan_lookup(ii, jj, kk, n_buf, p_tot, fixedp, device):
-    key = _key(ii, jj, kk, n_buf, p_tot, fixedp, device)
-    hit = _CACHE.get(key)
-    if hit is not None:
-        stepper, refs = hit
-        if all(r() is t for r, t in zip(refs, (ii, jj, kk))):
-            return stepper
-        del _CACHE[key]
-    pend = _PENDING.pop(key, None)
-    if pend is not None:                          # prefetch_plan is building exactly this one: wait for it
-        future, box, held = pend
-        future.result()
-        if "stepper" in box and all(h is t for h, t in zip(held, (ii, jj, kk))):
-            _store(key, box["stepper"], ii, jj, kk)
-            return box["stepper"]
-        if "error" in box and not isinstance(box["error"], Exception):
-            raise box["error"]                    # KeyboardInterrupt and the like; ordinary errors are re-raised by the build below
-    pl, ws = _build_plan(ii, jj, kk, n_buf, p_tot, fixedp, True)
-    stepper = pl if isinstance(pl, Stepper) else Stepper(pl, device, ws)
-    _store(key, stepper, ii, jj, kk)
-    return stepper
+    def __init__(self):
+        self.plans = {}           # key -> _Entry, oldest first; 8 at most
+        self.ahead = {}           # _Entry -> the stepper of its clone for the NEXT list, made ahead (Plan.preshift); 3 at most
+        self.pending = {}         # key -> (future, result box, (ii, jj, kk)): plans being built by prefetch; 4 at most
+        self.last = None          # _Call
+        self.last_shift = None    # frame shift of the last plan that was made as a shifted copy (survives `clear`)
+        self.calls_before = 0     # how many calls the previous list got: decides when the next clone is made (survives `clear`)
 
+    def get(self, ii, jj, kk, n_buf, p_tot, fixedp, device):
+        """(the list's stepper, it was found in place as the plan of the call before — this is not the first call of an update())."""
+        c = self.last
+        # (`_ident` spelled out: seven of an update()'s eight calls end here, in front of the GPU's work)
+        if (c is not None and c.ii is ii and c.jj is jj and c.kk is kk
+                and c.ident == (ii._version, jj._version, kk._version, ii.data_ptr(), jj.data_ptr(), kk.data_ptr())
+                and c.fixedp == fixedp and c.n_buf == n_buf and c.p_tot == p_tot and c.device == device):
+            return c.entry.stepper, True
+        if c is not None:
+            self.calls_before = c.entry.calls + 1
+        entry = self._lookup(ii, jj, kk, n_buf, p_tot, fixedp, device)
+        self.last = _Call(entry, ii, jj, kk, fixedp, n_buf, p_tot, device)
+        return entry.stepper, False
 
-def _speculate(ii, jj, kk, n_buf, p_tot, fixedp, probe=False):
-    """The plan of a list ASSUMED to be an earlier one moved up by the shift that was right last time — no synchronisation, no host
-    wait, `confirm()` after the first step: a clone made ahead (Plan.preshift, with its stepper) bound to the list by one comparison
-    kernel, else a clone made here (Plan.shifted_spec).  (plan or stepper, workspace to share) or None.  `probe`: only say whether a
-    clone made ahead is there (its stepper), touching nothing."""
-    if _LAST_SHIFT[0] is None or os.environ.get("BT_PLAN_SHIFT", "1") == "0" or os.environ.get("BT_PLAN_SPECULATE", "1") == "0":
-        return None
-    E, nb, pt, fp = ii.numel(), int(n_buf), int(p_tot), int(fixedp)
-    try:
-        cached = list(_CACHE.values())
-    except RuntimeError:
-        return None
-    for st, _ in reversed(cached):
-        inf = st.plan.info
-        if (inf["E"] == E and inf["n_buf"] == nb and inf["p_tot"] == pt and fp - inf["fixedp"] == _LAST_SHIFT[0]
-                and not st.plan.speculative):
-            if probe:                         # (prefetch_plan asking: is there a clone made ahead for this list?  Nothing is touched)
-                pre = _PRE.get(id(st))
-                return (pre[1], st.ws) if pre is not None and pre[0] is st and pre[1].plan.info["fixedp"] == fp else None
-            pre = _PRE.pop(id(st), None)
-            if pre is not None and pre[0] is st and pre[1].plan.info["fixedp"] == fp and pre[1].plan.bind(ii, jj, kk, n_buf, p_tot, fixedp):
-                return pre[1], st.ws          # made (stepper and all) while the previous update()'s steps ran: only the comparison is left
-            pl = Plan.shifted_spec(st.plan, ii, jj, kk, n_buf, p_tot, fixedp)
-            if pl is not None:
-                return pl, st.ws
-            return None
-    return None
-
-
-def _build_plan(ii, jj, kk, n_buf, p_tot, fixedp, sync, speculate=True):
-    """A new plan: first as a shifted copy of one of the most recent plans (the caller's window in steady state repeats its
-    edge list with all frame / patch indices moved up, batrack.py:189-212 — ~0.1 ms on the device), else from scratch
-    (host analysis, ~1 ms for the 138k-edge window).  Returns (plan, workspace to share or None).
-
-    Steady state of the caller's window: the list is the one of an earlier update() moved up by as many frames as `fixedp`
-    moved (batrack.py:189-212, :858).  That is ASSUMED of the most recent plan whose fixedp differs by the shift that was right
-    last time (Plan.shifted_spec: the clone is enqueued with no synchronisation and no host wait, the comparison that proves the
-    assumption runs on the GPU beside it); BA_rgbd_droid confirms after it has enqueued the call's step and repeats the call on a
-    properly built plan where the assumption was wrong."""
-    if speculate:
-        got = _speculate(ii, jj, kk, n_buf, p_tot, fixedp)
-        if got is not None:
-            return got
-    if sync:
-        # once, here: the index tensors must be complete before any of the builds below reads them on the plan stream
-        # (Plan.shifted may return before it gets to synchronise, so nothing below relies on it having done so)
-        torch.cuda.current_stream(ii.device).synchronize()
-        sync = False
-    if os.environ.get("BT_PLAN_SHIFT", "1") != "0":
-        E = ii.numel()
+    def settle(self, stepper):
+        """Settle a speculative plan.  True: it is the list's plan.  False: the guess was wrong — the plan is out of the cache.  An
+        error of the confirmation itself (an index out of range in the new list) also takes it out before it is raised again: a
+        caller that catches it and calls once more must not step on the unconfirmed clone."""
         try:
-            cached = list(_CACHE.values())             # (prefetch_plan calls this from its worker thread while the cache may change)
+            ok = stepper.plan.confirm()
+        except Exception:
+            self._discard(stepper)
+            raise
+        if not ok:
+            self._discard(stepper)
+        return ok
+
+    def after_step(self):
+        """Behind the enqueued step of a call that found its plan in place: counts the call and, behind ONE call per plan, makes the
+        clone for the list the NEXT update() will most likely bring — this plan's, moved up by the shift that was right last time
+        (~45 us).  The first call of the next update(), which has the GPU idle behind it, is left with one comparison kernel."""
+        e = self.last.entry
+        e.calls += 1                                  # this was call number e.calls + 1 on the plan
+        if e.pre_tried:
+            return
+        # WHEN: behind a call that leaves the host ~45 us it can spend unnoticed, i.e. with that much GPU work queued in front of it.  The
+        # first call of an update() is late by its plan; the host catches up by ~10-25 us a call (a structure-only step is 19 us of
+        # kernels, a pose+structure one 61): behind call 2 the clone cost the update() 16-37 us (the GPU ran dry before call 3 arrived),
+        # behind call 5 or 7 nothing (tools/gpu_update_floor.py, AB_AT).  So: call 5 where the update()s have that many calls (how many the
+        # previous list got), else call 3, else 2.  BT_PLAN_PRESHIFT_AT: the measurement's override.
+        at = os.environ.get("BT_PLAN_PRESHIFT_AT")
+        at = int(at) if at else (5 if self.calls_before >= 6 else 3 if self.calls_before >= 4 else 2)
+        if e.calls + 1 < at:
+            return
+        df, stepper = self.last_shift, e.stepper
+        if df is None or stepper.plan.speculative:
+            return
+        e.pre_tried = True
+        if _ladder() < AHEAD:
+            return
+        pl = Plan.preshift(stepper.plan, df)
+        if pl is not None:
+            while len(self.ahead) >= 3:
+                self.ahead.pop(next(iter(self.ahead)))
+            # (the clone shares its source's workspace, as a clone made in the call does: same layout, same stream, taking turns)
+            self.ahead[e] = Stepper(pl, stepper.device, stepper.ws)
+            # ... and the room the next update()'s plan will need in the cache is made now (destroying a plan is not free either)
+            old = next(iter(self.plans), None)
+            if len(self.plans) >= 8 and self.plans[old] is not e:
+                self._evict(old)
+
+    def prefetch(self, ii, jj, kk, n_buf, p_tot, fixedp, dev, background):
+        key = _key(ii, jj, kk, n_buf, p_tot, fixedp, dev)
+        if key in self.plans or key in self.pending:
+            return
+        # A clone made ahead for this list (during the previous update()) waits for it: nothing to build.  It is NOT bound
+        # here — measured (tools/gpu_update_floor.py, PREFETCH=1 AB=1): with the comparison launched at prefetch time the update() took
+        # 0.412 ms against 0.38-0.39 with the first BA call launching it — in front of the step the comparison also wakes the idle GPU
+        # while the host is still preparing the step's launches.
+        if self._clone_ahead(ii, n_buf, p_tot, fixedp) is not None:
+            return
+        ready, caller_stream = _cuda.Event(), _cuda.current_stream(dev)
+        ready.record(caller_stream)                                # the indices are complete once this has passed
+        box = {}
+
+        def build():
+            try:
+                ready.synchronize()
+                # the current device and stream are per host thread: the workspace is allocated and zero-filled on the stream
+                # the steps will run on, so its accumulators are clear before the first of them whatever stream that is
+                with _cuda.device(dev), _cuda.stream(caller_stream):
+                    box["stepper"] = Stepper(self._build(ii, jj, kk, n_buf, p_tot, fixedp, False, speculate=False)[0], dev)
+            except BaseException as e:                              # reported (or retried in the open) by _lookup
+                box["error"] = e
+
+        while len(self.pending) >= 4:                              # stale prefetches (edge lists that were never used)
+            self.pending.pop(next(iter(self.pending)))[0].result()
+        if background:
+            global _WORKER
+            if _WORKER is None:
+                _WORKER = ThreadPoolExecutor(max_workers=1, thread_name_prefix="batrack-plan")
+            self.pending[key] = (_WORKER.submit(build), box, (ii, jj, kk))
+        else:
+            build()
+            if "error" in box:
+                raise box["error"]
+            self._store(key, box["stepper"], ii, jj, kk)
+
+    def clear(self):
+        """Forgets every plan, clone and prefetch, but not `last_shift` and `calls_before`: the caller's window goes on as it did."""
+        for fut, _, _ in list(self.pending.values()):
+            fut.result()
+        self.pending.clear()
+        self.ahead.clear()
+        self.plans.clear()
+        self.last = None
+
+    def _store(self, key, stepper, ii, jj, kk):
+        if len(self.plans) >= 8:
+            self._evict(next(iter(self.plans)))
+        entry = self.plans[key] = _Entry(stepper, ii, jj, kk)
+        return entry
+
+    def _evict(self, key):
+        """A plan leaves the cache, and the clone made ahead from it with it (it is of no use without its source)."""
+        entry = self.plans.pop(key, None)
+        self.ahead.pop(entry, None)                   # (first: the clone goes before its source)
+
+    def _discard(self, stepper):
+        """A plan whose speculation failed: out of the cache, with the shift that was assumed and the clones made ahead under it."""
+        for key in [k for k, e in list(self.plans.items()) if e.stepper is stepper]:
+            self._evict(key)
+        if self.last is not None and self.last.entry.stepper is stepper:
+            self.last = None
+        self.last_shift = None
+        self.ahead.clear()
+
+    def _lookup(self, ii, jj, kk, n_buf, p_tot, fixedp, device):
+        key = _key(ii, jj, kk, n_buf, p_tot, fixedp, device)
+        hit = self.plans.get(key)
+        if hit is not None:
+            if all(r() is t for r, t in zip(hit.refs, (ii, jj, kk))):
+                return hit
+            self._evict(key)
+        pend = self.pending.pop(key, None)
+        if pend is not None:                          # prefetch is building exactly this one: wait for it
+            future, box, held = pend
+            future.result()
+            if "stepper" in box and all(h is t for h, t in zip(held, (ii, jj, kk))):
+                return self._store(key, box["stepper"], ii, jj, kk)
+            if "error" in box and not isinstance(box["error"], Exception):
+                raise box["error"]                    # KeyboardInterrupt and the like; ordinary errors are re-raised by the build below
+        pl, ws = self._build(ii, jj, kk, n_buf, p_tot, fixedp, True)
+        return self._store(key, pl if isinstance(pl, Stepper) else Stepper(pl, device, ws), ii, jj, kk)
+
+    def _candidates(self, ii, n_buf, p_tot):
+        """The cached plans a list may be a shift of — as many edges, in the same buffers — most recent first.  (The figures straight
+        from the plans' dicts: every frame passes here.  A snapshot: the worker thread comes here while the cache may change.)"""
+        E, nb, pt = ii.numel(), int(n_buf), int(p_tot)
+        try:
+            cached = list(self.plans.values())
         except RuntimeError:
-            cached = []
-        nb, pt, fp = int(n_buf), int(p_tot), int(fixedp)
-        cands = []
-        for st, _ in reversed(cached):                 # most recent first (the figures straight from the plans' dicts: every frame passes here)
-            inf = st.plan.info
-            if inf["E"] == E and inf["n_buf"] == nb and inf["p_tot"] == pt and inf["fixedp"] < fp:
-                cands.append(st.plan)
-        # (with a keyframe stride of 2 the match is two updates back: the frame shift that worked last time is tried first)
-        cands.sort(key=lambda pl: fp - pl.info["fixedp"] != _LAST_SHIFT[0])
-        if cands:                                      # (one comparison pass and one host wait for all of them; a list that matches none is built the ordinary way)
-            pl, matched = Plan.shifted_any(cands[:3], ii, jj, kk, n_buf, p_tot, fixedp, sync=False)
-            if pl is not None:
-                _LAST_SHIFT[0] = fp - matched.info["fixedp"]
-                return pl, None
-    return Plan(ii, jj, kk, n_buf, p_tot, fixedp, sync=False), None
+            return
+        for e in reversed(cached):
+            inf = e.stepper.plan.info
+            if inf["E"] == E and inf["n_buf"] == nb and inf["p_tot"] == pt:
+                yield e
+
+    def _assumed_source(self, ii, n_buf, p_tot, fixedp):
+        """The cached plan a list is ASSUMED to be a shift of: the most recent one `last_shift` frames behind `fixedp` that is itself
+        settled — the first such candidate, whatever becomes of the attempt."""
+        if self.last_shift is None or _ladder(SPECULATIVE) < SPECULATIVE:
+            return None
+        fp = int(fixedp)
+        for e in self._candidates(ii, n_buf, p_tot):
+            if fp - e.stepper.plan.info["fixedp"] == self.last_shift and not e.stepper.plan.speculative:
+                return e
+        return None
+
+    def _clone_ahead(self, ii, n_buf, p_tot, fixedp):
+        """The probe: the clone made ahead that `_speculate` would try to bind to this list, or None.  Nothing is touched."""
+        clone = self.ahead.get(self._assumed_source(ii, n_buf, p_tot, fixedp))
+        return clone if clone is not None and clone.plan.info["fixedp"] == int(fixedp) else None
+
+    def _speculate(self, ii, jj, kk, n_buf, p_tot, fixedp):
+        """The plan of a list ASSUMED to be an earlier one moved up by the shift that was right last time — no synchronisation, no host
+        wait, `settle` after the first step: a clone made ahead (with its stepper) bound to the list by one comparison kernel, else a
+        clone made here (Plan.shifted_spec).  (plan or stepper, workspace to share) or None."""
+        e = self._assumed_source(ii, n_buf, p_tot, fixedp)
+        if e is None:
+            return None
+        clone = self.ahead.pop(e, None)
+        if clone is not None and clone.plan.info["fixedp"] == int(fixedp) and clone.plan.bind(ii, jj, kk, n_buf, p_tot, fixedp):
+            return clone, e.stepper.ws                # made (stepper and all) while the previous update()'s steps ran: only the comparison is left
+        pl = Plan.shifted_spec(e.stepper.plan, ii, jj, kk, n_buf, p_tot, fixedp)
+        return (pl, e.stepper.ws) if pl is not None else None
+
+    def _build(self, ii, jj, kk, n_buf, p_tot, fixedp, sync, speculate=True):
+        """A new plan: as a shifted copy of one of the most recent plans (the caller's window in steady state repeats its edge list
+        with all frame / patch indices moved up, batrack.py:189-212, :858 — ~0.1 ms on the device), else from scratch (host analysis,
+        ~1 ms for the 138k-edge window).  With `speculate` the copy is first made on an assumption (`_speculate`): BA_rgbd_droid settles
+        it behind the call's step and repeats the call on a properly built plan where the assumption was wrong.
+        Returns (plan or stepper, workspace to share or None)."""
+        if speculate:
+            got = self._speculate(ii, jj, kk, n_buf, p_tot, fixedp)
+            if got is not None:
+                return got
+        if sync:
+            # once, here: the index tensors must be complete before any of the builds below reads them on the plan stream
+            # (Plan.shifted_any may return before it gets to synchronise, so nothing below relies on it having done so)
+            _cuda.current_stream(ii.device).synchronize()
+        if _ladder(SHIFTED) >= SHIFTED:
+            fp = int(fixedp)
+            cands = [e.stepper.plan for e in self._candidates(ii, n_buf, p_tot) if e.stepper.plan.info["fixedp"] < fp]
+            # (with a keyframe stride of 2 the match is two updates back: the frame shift that worked last time is tried first)
+            cands.sort(key=lambda pl: fp - pl.info["fixedp"] != self.last_shift)
+            if cands:                                  # (one comparison pass and one host wait for all of them; a list that matches none is built the ordinary way)
+                pl, matched = Plan.shifted_any(cands[:3], ii, jj, kk, n_buf, p_tot, fixedp, sync=False)
+                if pl is not None:
+                    self.last_shift = fp - matched.info["fixedp"]
+                    return pl, None
+        return Plan(ii, jj, kk, n_buf, p_tot, fixedp, sync=False), None
 
 
-def _preshift(stepper):
-    """Make the clone for the list the NEXT update() will most likely bring — this plan's, moved up by the shift that was right last
-    time — now, while this update()'s steps run: called after the step of every call that found its plan in place has been enqueued, it
-    picks ONE of them (below) to spend its ~45 us behind; the first call of the next update(), which has the GPU idle behind it, is
-    left with one comparison kernel.  Once per plan."""
-    stepper._repeats = stepper.__dict__.get("_repeats", 0) + 1          # this is call number _repeats + 1 on the plan
-    if stepper.__dict__.get("_pre_tried"):
-        return
-    # WHEN: behind a call that leaves the host ~45 us it can spend unnoticed, i.e. with that much GPU work queued in front of it.  The
-    # first call of an update() is late by its plan; the host catches up by ~10-25 us a call (a structure-only step is 19 us of
-    # kernels, a pose+structure one 61): behind call 2 the clone cost the update() 16-37 us (the GPU ran dry before call 3 arrived),
-    # behind call 5 or 7 nothing (tools/gpu_update_floor.py, AB_AT).  So: call 5 where the update()s have that many calls (how many the
-    # previous list got), else call 3, else 2.  BT_PLAN_PRESHIFT_AT: the measurement's override.
-    at = os.environ.get("BT_PLAN_PRESHIFT_AT")
-    at = int(at) if at else (5 if _CALLS_BEFORE[0] >= 6 else 3 if _CALLS_BEFORE[0] >= 4 else 2)
-    if stepper._repeats + 1 < at:
-        return
-    df = _LAST_SHIFT[0]
-    if df is None or stepper.plan.speculative:
-        return
-    stepper._pre_tried = True
-    if os.environ.get("BT_PLAN_SHIFT", "1") == "0" or os.environ.get("BT_PLAN_SPECULATE", "1") == "0" or os.environ.get("BT_PLAN_PRESHIFT", "1") == "0":
-        return
-    pl = Plan.preshift(stepper.plan, df)
-    if pl is not None:
-        while len(_PRE) >= 3:
-            _PRE.pop(next(iter(_PRE)))
-        # (the clone shares its source's workspace, as a clone made in the call does: same layout, same stream, taking turns)
-        _PRE[id(stepper)] = (stepper, Stepper(pl, stepper.device, stepper.ws))
-        # ... and the room the next update()'s plan will need in the cache is made now (destroying a plan is not free either)
-        if len(_CACHE) >= _CACHE_MAX:
-            old = next(iter(_CACHE))
-            if _CACHE[old][0] is not stepper:
-                _PRE.pop(id(_CACHE.pop(old)[0]), None)
-
-
-def _discard(stepper):
-    """A plan whose speculation failed: out of every cache (and the shift that was assumed with it)."""
-    for k in [k for k, (st, _) in list(_CACHE.items()) if st is stepper]:
-        _CACHE.pop(k, None)
-    if _LAST[0] is not None and _LAST[0][8] is stepper:
-        _LAST[0] = None
-    _LAST_SHIFT[0] = None
-    _PRE.clear()                                 # (clones made ahead under the shift that just proved wrong)
-
-
-def _confirm(stepper):
-    """Settle a speculative plan.  True: it is the list's plan.  False: the guess was wrong — the plan is out of every cache.
-    An error of the confirmation itself (an index out of range in the new list) also takes the plan out of the caches before
-    it is raised again: a caller that catches it and calls once more must not step on the unconfirmed clone."""
-    try:
-        ok = stepper.plan.confirm()
-    except Exception:
-        _discard(stepper)
-        raise
-    if not ok:
-        _discard(stepper)
-    return ok
+_PLANS = PlanCache()
 
 
 def _print_residual(poses, patches, intrinsics, targets_2d, ii, jj, kk, bounds):
@@ -253,52 +338,12 @@ def prefetch_plan(ii, jj, kk, n_buf, p_tot, fixedp, device=None, background=True
         raise RuntimeError("prefetch_plan: the edge list must be on the GPU (no CPU fallback in batrack_amd)")
     if ii.numel() == 0:
         return
-    key = _key(ii, jj, kk, n_buf, p_tot, fixedp, dev)
-    if key in _CACHE or key in _PENDING:
-        return
     _lib.lib()
-    # A clone made ahead for this list (Plan.preshift, during the previous update()) waits for it: nothing to build.  It is NOT bound
-    # here — measured (tools/gpu_update_floor.py, PREFETCH=1 AB=1): with the comparison launched at prefetch time the update() took
-    # 0.412 ms against 0.38-0.39 with the first BA call launching it — in front of the step the comparison also wakes the idle GPU
-    # while the host is still preparing the step's launches.
-    if _speculate(ii, jj, kk, n_buf, p_tot, fixedp, probe=True) is not None:
-        return
-    ready = torch.cuda.Event()
-    caller_stream = torch.cuda.current_stream(dev)
-    ready.record(caller_stream)                                # the indices are complete once this has passed
-    box = {}
-
-    def build():
-        try:
-            ready.synchronize()
-            # the current device and stream are per host thread: the workspace is allocated and zero-filled on the stream
-            # the steps will run on, so its accumulators are clear before the first of them whatever stream that is
-            with torch.cuda.device(dev), torch.cuda.stream(caller_stream):
-                box["stepper"] = Stepper(_build_plan(ii, jj, kk, n_buf, p_tot, fixedp, False, speculate=False)[0], dev)
-        except BaseException as e:                              # reported (or retried in the open) by _plan_for
-            box["error"] = e
-
-    while len(_PENDING) >= 4:                                  # stale prefetches (edge lists that were never used)
-        _PENDING.pop(next(iter(_PENDING)))[0].result()
-    if background:
-        global _WORKER
-        if _WORKER is None:
-            _WORKER = ThreadPoolExecutor(max_workers=1, thread_name_prefix="batrack-plan")
-        _PENDING[key] = (_WORKER.submit(build), box, (ii, jj, kk))
-    else:
-        build()
-        if "error" in box:
-            raise box["error"]
-        _store(key, box["stepper"], ii, jj, kk)
+    _PLANS.prefetch(ii, jj, kk, n_buf, p_tot, fixedp, dev, background)
 
 
 def clear_plan_cache():
-    for fut, _, _ in list(_PENDING.values()):
-        fut.result()
-    _PENDING.clear()
-    _PRE.clear()
-    _CACHE.clear()
-    _LAST[0] = None
+    _PLANS.clear()
 
 
 def _f32c(t, what):
@@ -307,6 +352,42 @@ def _f32c(t, what):
     if t.dtype != torch.float32:
         raise TypeError(f"BA_rgbd_droid: `{what}` must be float32 (batrack.py:74-91), got {t.dtype}")
     return t
+
+
+def _enqueue(stepper, P, patches, patches_monodisp, intrinsics, targets_2d, weights, bounds, lmbda, ep, alpha, loss, so, lm_trk):
+    """The step of one call, enqueued on the current stream: (poses_out [1, n_buf, 7] — the input's where `so` —, out_patches
+    [1, p_tot, 3, 1, 1])."""
+    if stepper._ops is not None:
+        # the whole call in ONE operator (csrc/torch_ops.cpp ba_droid: the views the ABI needs, the output tensors, the step):
+        # the tensor operations below cost 28 us of host time a call, more than a structure-only step takes on the GPU
+        return stepper._ops.ba_droid.default(stepper.plan.handle.value, stepper.ws, P, patches, patches_monodisp, intrinsics,
+                                             targets_2d, weights, [float(b) for b in bounds], float(lmbda), float(ep),
+                                             float(alpha), _lib.LOSS[loss], so, lm_trk)
+    n_buf, p_tot, E = P.shape[1], patches.shape[1], targets_2d.numel() // 2
+    Pc = P.contiguous()
+    pat = patches.reshape(p_tot, 3).contiguous()
+    mono = patches_monodisp
+    if mono.numel() == p_tot and not mono.is_contiguous() and p_tot > 1:
+        # the caller's prior is a strided view (patches_local[:, :, mid, 2:], batrack.py:866): used in place through mono_stride
+        # (only a genuine stride >= 1: an expanded tensor — stride 0 — or a negative stride is materialised instead)
+        d = [i for i, n in enumerate(mono.shape) if n == p_tot]
+        if len(d) == 1 and mono.stride(d[0]) >= 1:
+            mono = torch.as_strided(mono, (p_tot,), (mono.stride(d[0]),), mono.storage_offset())
+        else:
+            mono = mono.reshape(-1).contiguous()
+    else:
+        mono = mono.reshape(-1)
+    intr = intrinsics.reshape(-1, 4).contiguous()
+    tg = targets_2d
+    tg = tg.reshape(E, 2) if tg.is_contiguous() else tg[0]
+    if tg.stride(1) != 1:                          # the caller's view has strides (3, 1): used in place
+        tg = tg.contiguous()
+    w = weights.reshape(E, 2).contiguous()
+    patches_out = torch.empty_like(pat)
+    poses_out = Pc if so else torch.empty_like(Pc)
+    stepper.step(Pc, pat, mono, intr, tg, tg.stride(0), w, poses_out, patches_out,
+                 bounds, lmbda, ep, alpha, loss, so, lmbda_per_track=lm_trk)
+    return poses_out.view(1, n_buf, 7), patches_out.view(1, p_tot, 3, 1, 1)
 
 
 def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targets_disp, weights, lmbda,
@@ -347,7 +428,7 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
         raise ValueError("patches_monodisp / intrinsics do not match the patch / pose buffers")
     if targets_2d.shape[-1] != 2 or targets_2d.numel() != 2 * E:
         raise ValueError("targets_2d must be [1, E, 2]")
-    stepper = _plan_for(ii, jj, kk, n_buf, p_tot, fixedp, dev)
+    stepper, in_place = _PLANS.get(ii, jj, kk, n_buf, p_tot, fixedp, dev)
     lmbda_in = lmbda                             # (what a repeated call after a failed speculation must be given again)
     lm_trk = None
     if isinstance(lmbda, torch.Tensor):
@@ -356,8 +437,8 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
         else:
             # a per-track tensor is checked against the plan's track count: a speculative clone carries its SOURCE's count, so
             # the speculation is settled first (a wrong guess is rebuilt here, before anything is enqueued)
-            if stepper.plan.speculative and not _confirm(stepper):
-                stepper = _plan_for(ii, jj, kk, n_buf, p_tot, fixedp, dev)
+            if stepper.plan.speculative and not _PLANS.settle(stepper):
+                stepper, in_place = _PLANS.get(ii, jj, kk, n_buf, p_tot, fixedp, dev)
         if isinstance(lmbda, float):
             pass
         elif lmbda.numel() == stepper.plan.m:           # ba.py:299-300: lmbda.reshape(*C.shape), one value per distinct track
@@ -366,52 +447,14 @@ def BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targ
         else:
             raise ValueError(f"a lmbda tensor must hold 1 or m = {stepper.plan.m} values (ba.py:299-300), got {lmbda.numel()}")
     so = bool(structure_only) or stepper.plan.n == 0
-    if stepper._ops is not None:
-        # the whole call in ONE operator (csrc/torch_ops.cpp ba_droid: the views the ABI needs, the output tensors, the step):
-        # the tensor operations below cost 28 us of host time a call, more than a structure-only step takes on the GPU
-        poses_out, out_patches = stepper._ops.ba_droid.default(stepper.plan.handle.value, stepper.ws, P, patches, patches_monodisp, intrinsics,
-                                                       targets_2d, weights, [float(b) for b in bounds], float(lmbda), float(ep),
-                                                       float(alpha), _lib.LOSS[loss], so, lm_trk)
-        if PRINT:
-            _print_residual(poses, patches, intrinsics, targets_2d, ii, jj, kk, bounds)
-        if stepper.plan.speculative and not _confirm(stepper):
-            # the list was no shifted copy after all: what was just enqueued is void (the inputs are untouched) — once more, properly
-            return BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targets_disp, weights, lmbda_in, ii, jj, kk, bounds,
-                                 ep=ep, PRINT=False, fixedp=fixedp, structure_only=structure_only, loss=loss, alpha=alpha)
-        if _REPEAT[0]:
-            _preshift(stepper)                   # (behind this call's launches: the clone for the next update()'s list)
-        return (poses, out_patches) if so else (SE3(poses_out), out_patches)
-    Pc = P.contiguous()
-    pat = patches.reshape(p_tot, 3).contiguous()
-    mono = patches_monodisp
-    if mono.numel() == p_tot and not mono.is_contiguous() and p_tot > 1:
-        # the caller's prior is a strided view (patches_local[:, :, mid, 2:], batrack.py:866): used in place through mono_stride
-        # (only a genuine stride >= 1: an expanded tensor — stride 0 — or a negative stride is materialised instead)
-        d = [i for i, n in enumerate(mono.shape) if n == p_tot]
-        if len(d) == 1 and mono.stride(d[0]) >= 1:
-            mono = torch.as_strided(mono, (p_tot,), (mono.stride(d[0]),), mono.storage_offset())
-        else:
-            mono = mono.reshape(-1).contiguous()
-    else:
-        mono = mono.reshape(-1)
-    intr = intrinsics.reshape(-1, 4).contiguous()
-    tg = targets_2d
-    tg = tg.reshape(E, 2) if tg.is_contiguous() else tg[0]
-    if tg.stride(1) != 1:                          # the caller's view has strides (3, 1): used in place
-        tg = tg.contiguous()
-    w = weights.reshape(E, 2).contiguous()
-    patches_out = torch.empty_like(pat)
-    poses_out = Pc if so else torch.empty_like(Pc)
-    stepper.step(Pc, pat, mono, intr, tg, tg.stride(0), w, poses_out, patches_out,
-                 bounds, lmbda, ep, alpha, loss, so, lmbda_per_track=lm_trk)
+    poses_out, out_patches = _enqueue(stepper, P, patches, patches_monodisp, intrinsics, targets_2d, weights, bounds, lmbda, ep, alpha,
+                                      loss, so, lm_trk)
     if PRINT:
         _print_residual(poses, patches, intrinsics, targets_2d, ii, jj, kk, bounds)
-    if stepper.plan.speculative and not _confirm(stepper):
+    if stepper.plan.speculative and not _PLANS.settle(stepper):
+        # the list was no shifted copy after all: what was just enqueued is void (the inputs are untouched) — once more, properly
         return BA_rgbd_droid(poses, patches, patches_monodisp, intrinsics, targets_2d, targets_disp, weights, lmbda_in, ii, jj, kk, bounds,
                              ep=ep, PRINT=False, fixedp=fixedp, structure_only=structure_only, loss=loss, alpha=alpha)
-    if _REPEAT[0]:
-        _preshift(stepper)
-    out_patches = patches_out.view(1, p_tot, 3, 1, 1)
-    if so:
-        return poses, out_patches
-    return SE3(poses_out.view(1, n_buf, 7)), out_patches
+    if in_place:
+        _PLANS.after_step()                      # (behind this call's launches: the clone for the next update()'s list)
+    return (poses, out_patches) if so else (SE3(poses_out), out_patches)

@@ -61,9 +61,18 @@ def _read_info(lib, h):
 class Plan:
     """bt_plan handle.  ii/jj/kk: int64 torch tensors (CPU or GPU) or numpy arrays."""
 
-    # The state of a speculative clone (shifted_spec, preshift): `speculative` until confirm() has said yes, `unbound` until a
-    # clone made ahead of its list was given it (bind), `invalid` once confirm() has said no.  False on every other plan.
+    # The state of a speculative clone, one of four (SpecState on the C side, which tells apart two ways to wait where this says "bound"):
+    # "none" — an ordinary plan, or a speculation confirm() has said yes to; "unbound" — made ahead of its list (preshift), until bind
+    # gives it one; "bound" — it has its list (shifted_spec, bind), confirm() has not spoken; "invalid" — confirm() has said no.
+    # `speculative`, `unbound`, `invalid`: what callers ask, plain attributes written by `_set_spec` alone (the repeat path of
+    # BA_rgbd_droid reads `speculative` twice a call).
+    _SPEC = {"none": (False, False, False), "unbound": (True, True, False), "bound": (True, False, False), "invalid": (True, False, True)}
+    spec = "none"
     speculative = unbound = invalid = False
+
+    def _set_spec(self, state):
+        self.spec = state
+        self.speculative, self.unbound, self.invalid = self._SPEC[state]
 
     def __init__(self, ii, jj, kk, n_buf, p_tot, fixedp, upload=True, n_all_min=0, own=(0, 0), sync=True):
         L = _lib.lib()
@@ -95,17 +104,15 @@ class Plan:
         self.uploaded = bool(upload)
 
     @classmethod
-    def _wrap(cls, lib, h, info, df=0, keep=None, speculative=False, unbound=False):
+    def _wrap(cls, lib, h, info, df=0, keep=None, spec="none"):
         """The uploaded plan behind handle `h` (a shifted clone: no __init__).  `info`, `df`: its figures are its source's but for the
         two that a shift by `df` frames moves (no bt_plan_get_info: the clones are made on the critical path of every frame); df = 0:
         `info` is the clone's own.  `keep`: tensors that kernels still queued read."""
         self = cls.__new__(cls)
         self._lib, self._h, self._keep, self.uploaded = lib, h, keep, True
         self.info = dict(info, fixedp=info["fixedp"] + df, n_all=info["n_all"] + df) if df else info
-        if speculative:
-            self.speculative = True
-        if unbound:
-            self.unbound = True
+        if spec != "none":
+            self._set_spec(spec)
         return self
 
     @classmethod
@@ -167,7 +174,7 @@ class Plan:
             return None
         _lib.check(rc, "bt_plan_create_shifted_spec")
         # (keep: the index tensors are read by kernels still queued)
-        return cls._wrap(src._lib, h, src.info, int(fixedp) - src.info["fixedp"], keep=(ii, jj, kk), speculative=True)
+        return cls._wrap(src._lib, h, src.info, int(fixedp) - src.info["fixedp"], keep=(ii, jj, kk), spec="bound")
 
     @classmethod
     def preshift(cls, src, df):
@@ -181,7 +188,7 @@ class Plan:
         if rc > 0:
             return None
         _lib.check(rc, "bt_plan_preshift")
-        return cls._wrap(src._lib, h, src.info, int(df), speculative=True, unbound=True)
+        return cls._wrap(src._lib, h, src.info, int(df), spec="unbound")
 
     def bind(self, ii, jj, kk, n_buf, p_tot, fixedp):
         """Give a pre-shifted clone its list (bt_plan_spec_bind: one comparison kernel, no host wait).  True: step it, then `confirm()`
@@ -194,7 +201,7 @@ class Plan:
             return False
         _lib.check(rc, "bt_plan_spec_bind")
         self._keep = (ii, jj, kk)                                    # (the index tensors are read by a kernel still queued)
-        self.unbound = False
+        self._set_spec("bound")
         return True
 
     def confirm(self):
@@ -208,11 +215,11 @@ class Plan:
         if rc != 0:
             # wrong guess (rc > 0) or an invalid list (rc < 0): either way this object is no plan of the caller's list — it stays
             # marked speculative and `invalid`, so that nobody who still holds it steps on it as a confirmed plan
-            self.invalid = True
+            self._set_spec("invalid")
             if rc > 0:
                 return False
             _lib.check(rc, "bt_plan_spec_confirm")
-        self.speculative = False
+        self._set_spec("none")
         return True
 
     def __getattr__(self, name):

@@ -164,7 +164,7 @@ def test_a_wrong_guess_inside_BA_rgbd_droid_is_repeated_on_a_proper_plan(monkeyp
     monkeypatch.setenv("BT_PLAN_SPECULATE", "1")
     hip_ba.clear_plan_cache()
     call(poses0, patches0, mono0, intr0, t3, w, ii0, jj0, kk0, fixedp)        # the cached plan the guess will be made from
-    hip_ba._LAST_SHIFT[0] = 2                                                   # "the shift that was right last time"
+    hip_ba._PLANS.last_shift = 2                                                # "the shift that was right last time"
     tried = {"n": 0}
     real_spec = Plan.shifted_spec.__func__
 
@@ -175,7 +175,7 @@ def test_a_wrong_guess_inside_BA_rgbd_droid_is_repeated_on_a_proper_plan(monkeyp
     monkeypatch.setattr(Plan, "shifted_spec", classmethod(spec))
     got = call(poses2, patches2, mono2, intr2, t3B, wB, iiB, jjB, kkB, fixedp + 2)
     torch.cuda.synchronize()
-    assert tried["n"] == 1 and hip_ba._LAST_SHIFT[0] is None                    # the guess was made, found wrong, and forgotten
+    assert tried["n"] == 1 and hip_ba._PLANS.last_shift is None                 # the guess was made, found wrong, and forgotten
     rel = lambda x, y: float((x.double() - y.double()).norm() / y.double().norm())
     assert rel(got[0].data, want[0]) < 1e-6 and rel(got[1], want[1]) < 1e-6
     hip_ba.clear_plan_cache()

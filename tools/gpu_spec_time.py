@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host time of the pieces of a frame's first BA call (the one that needs the new plan) in the replay's steady state:
-perf_counter around Plan.shifted_spec, _build_plan, _plan_lookup, _store, Stepper.__init__ and Plan.confirm (no profiler: cProfile
+perf_counter around Plan.shifted_spec, the plan cache's _build, _lookup and _store, Stepper.__init__ and Plan.confirm (no profiler: cProfile
 multiplies the cost of the many small Python calls).  GPU box:  python tools/gpu_spec_time.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,9 +22,9 @@ def wrap(obj, name, key, cls=False):
 
 
 wrap(P.Plan, "shifted_spec", "Plan.shifted_spec (incl. the C call)", cls=True)
-wrap(hip_ba, "_build_plan", "_build_plan")
-wrap(hip_ba, "_plan_lookup", "_plan_lookup")
-wrap(hip_ba, "_store", "_store (incl. destroying the evicted plan)")
+wrap(hip_ba._PLANS, "_build", "_build")
+wrap(hip_ba._PLANS, "_lookup", "_lookup")
+wrap(hip_ba._PLANS, "_store", "_store (incl. destroying the evicted plan)")
 wrap(P.Stepper, "__init__", "Stepper.__init__")
 wrap(P.Plan, "confirm", "Plan.confirm")
 per, st = [[] for _ in range(8)], dict(k=0)

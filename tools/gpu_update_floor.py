@@ -44,9 +44,9 @@ timed(plan_mod.Plan, "shifted_any", "Plan.shifted_any")
 timed(plan_mod.Plan, "__init__", "Plan.__init__")
 timed(plan_mod.Stepper, "__init__", "Stepper.__init__")
 timed(torch.cuda, "synchronize", "synchronize")
-timed(hip_ba, "_preshift", "_preshift")
-timed(hip_ba, "_plan_lookup", "_plan_lookup")
-timed(hip_ba, "_store", "_store")
+timed(hip_ba._PLANS, "after_step", "after_step")
+timed(hip_ba._PLANS, "_lookup", "_lookup")
+timed(hip_ba._PLANS, "_store", "_store")
 AB = os.environ.get("AB", "0") == "1"          # alternate: clones made ahead (Plan.preshift) on / off, update() by update()
 pf = hip_ba.prefetch_plan if os.environ.get("PREFETCH", "0") == "1" else None
 obs = SyntheticObservations(n_frames=int(os.environ.get("FRAMES", 200)), M=256, seed=0)
