@@ -8,14 +8,15 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "window_fmaps.hip"]
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "window_fmaps.hip", "encoder_head.hip"]
 HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "plan_host.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", "ba_solve_update.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
            os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h"),
            os.path.join("..", "..", "include", "batrack_patches.h"), os.path.join("..", "..", "include", "batrack_track.h"),
-           os.path.join("..", "..", "include", "batrack_attn.h"), os.path.join("..", "..", "include", "batrack_window.h")]
+           os.path.join("..", "..", "include", "batrack_attn.h"), os.path.join("..", "..", "include", "batrack_window.h"),
+           os.path.join("..", "..", "include", "batrack_encoder.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -33,7 +34,9 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
                            "patch generation: more than 1024 candidates per cell (8 * patches per cell), or an image side above 32768; "
                            "tracker iteration: more than 144 flow columns, more than 128 feature channels in the state update, or 2^31 - 16 or more tokens; "
                            "attention: a head size other than 48, a size, stride or row index above 2^31 - 1, or more than 2^24 - 1 workgroups; "
-                           "tracker window: a channel count other than 128, or a size, stride or element count above 2^31 - 1)"}
+                           "tracker window: a channel count other than 128, or a size, stride or element count above 2^31 - 1; "
+                           "encoder head: channel counts other than 64 / 96 / 128 / 128 -> 256 -> 128, more than 65535 frames, or a size, stride, "
+                           "offset or element count above 2^31 - 1)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -88,6 +91,10 @@ class PatchArgs(ctypes.Structure):                   # == bt_patch_args in inclu
                [(n, ctypes.c_int64) for n in ("H", "W", "stride_c", "stride_y", "stride_x")] + \
                [(n, ctypes.c_void_p) for n in ("depth", "ux", "uy")] + [("G", ctypes.c_int64), ("gm", ctypes.c_int64)] + \
                [(n, ctypes.c_void_p) for n in ("patches", "clr", "colors", "coords", "sel")]
+
+
+class EncoderLevel(ctypes.Structure):                # == bt_encoder_level in include/batrack_encoder.h
+    _fields_ = [("data", ctypes.c_void_p)] + [(n, ctypes.c_int64) for n in ("C", "h", "w", "sf", "sc", "sy", "sx")]
 
 
 class RowBuffer(ctypes.Structure):                   # == bt_row_buffer
@@ -362,6 +369,10 @@ def lib():
     L.bt_embed_conv.argtypes = [vp] + [i64] * 4 + [vp] * 5 + [i64] * 6 + [vp, vp]
     L.bt_feat_sample.restype = i32
     L.bt_feat_sample.argtypes = [vp] + [i64] * 4 + [vp, vp, i64, i64, vp, vp]
+    L.bt_encoder_head_workspace_bytes.restype = ctypes.c_size_t
+    L.bt_encoder_head_workspace_bytes.argtypes = [i64, i64, i64]
+    L.bt_encoder_head.restype = i32
+    L.bt_encoder_head.argtypes = [ctypes.POINTER(EncoderLevel)] * 4 + [vp, vp, i64, vp, vp, i64, i64, i64, i64, vp, vp, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

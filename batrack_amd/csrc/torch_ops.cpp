@@ -63,6 +63,10 @@
 //       bt_embed_conv: fnet_maps [F, 128, h, w], any strides; dmaps [S, h, w]; wpacked [24, 9, 8, 128]; out [F, 128, h, w] contiguous
 //   batrack_hip::feat_sample(Tensor fmaps, Tensor frames, Tensor xy) -> Tensor
 //       bt_feat_sample: fmaps [S, 128, h, w] contiguous, frames [n] int32, xy [n, >= 2] with unit last stride -> [n, 128]
+//   batrack_hip::encoder_head(Tensor a, Tensor b, Tensor c, Tensor d, Tensor w2_packed, Tensor bias2, Tensor w3_packed, Tensor bias3,
+//                             Tensor(a!) out) -> ()
+//       bt_encoder_head (include/batrack_encoder.h): the levels [F, 64 / 96 / 128 / 128, h_l, w_l], any strides; w2_packed
+//       [52, 9, 8, 256]; w3_packed [256, 128]; out [F, 128, h, w] contiguous, whose h and w are the output map's
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -74,6 +78,7 @@
 #include "../../include/batrack_attn.h"
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_corr.h"
+#include "../../include/batrack_encoder.h"
 #include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
 #include "../../include/batrack_track.h"
@@ -511,6 +516,39 @@ at::Tensor feat_sample(const at::Tensor &fmaps, const at::Tensor &frames, const 
     return out;
 }
 
+void encoder_head(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor &d, const at::Tensor &w2_packed,
+                  const at::Tensor &bias2, const at::Tensor &w3_packed, const at::Tensor &bias3, at::Tensor out) {
+    const char *op = "batrack_hip::encoder_head: ";
+    const at::Tensor *all[] = {&a, &b, &c, &d, &w2_packed, &bias2, &w3_packed, &bias3, &out};
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->device() == a.device(), op, "tensors must be on one device");
+    }
+    TORCH_CHECK(out.dim() == 4 && out.is_contiguous() && out.size(1) == BT_ENC_COUT && out.numel() > 0, op,
+                "out must be a contiguous [F, 128, h, w] and not empty");
+    const int64_t F = out.size(0), h = out.size(2), w = out.size(3);
+    const at::Tensor *lv[4] = {&a, &b, &c, &d};
+    const int64_t ch[4] = {BT_ENC_CA, BT_ENC_CB, BT_ENC_CC, BT_ENC_CD};
+    bt_encoder_level L[4];
+    for (int i = 0; i < 4; ++i) {
+        const at::Tensor &t = *lv[i];
+        TORCH_CHECK(t.dim() == 4 && t.size(0) == F && t.size(1) == ch[i] && t.size(2) >= 1 && t.size(3) >= 1, op,
+                    "the levels must be [F, 64 / 96 / 128 / 128, h_l, w_l] with out's F");
+        L[i] = bt_encoder_level{t.data_ptr<float>(), t.size(1), t.size(2), t.size(3), t.stride(0), t.stride(1), t.stride(2), t.stride(3)};
+    }
+    TORCH_CHECK(w2_packed.is_contiguous() && w2_packed.numel() == (int64_t)9 * BT_ENC_CIN * BT_ENC_CMID && bias2.is_contiguous()
+                && bias2.numel() == BT_ENC_CMID && w3_packed.is_contiguous() && w3_packed.numel() == (int64_t)BT_ENC_CMID * BT_ENC_COUT
+                && bias3.is_contiguous() && bias3.numel() == BT_ENC_COUT, op,
+                "w2_packed [52, 9, 8, 256], bias2 [256], w3_packed [256, 128], bias3 [128], all contiguous");
+    const size_t bytes = bt_encoder_head_workspace_bytes(F, h, w);
+    TORCH_CHECK(bytes > 0, op, "F * 256 * h * w must not pass 2^31 - 1");
+    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, a.options().dtype(at::kDouble));      // needs no initialisation
+    const int rc = bt_encoder_head(&L[0], &L[1], &L[2], &L[3], w2_packed.data_ptr<float>(), bias2.data_ptr<float>(), BT_ENC_CMID,
+                                   w3_packed.data_ptr<float>(), bias3.data_ptr<float>(), BT_ENC_COUT, F, h, w, ws.data_ptr(),
+                                   out.data_ptr<float>(), c10::hip::getCurrentHIPStream(a.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_encoder_head failed with status ", rc);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -544,4 +582,6 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("embed_conv(Tensor fnet_maps, Tensor dmaps, Tensor zrange, Tensor wpacked, Tensor bias, Tensor freqs, int frame0, "
           "Tensor(a!) out) -> ()", &embed_conv);
     m.def("feat_sample(Tensor fmaps, Tensor frames, Tensor xy) -> Tensor", &feat_sample);
+    m.def("encoder_head(Tensor a, Tensor b, Tensor c, Tensor d, Tensor w2_packed, Tensor bias2, Tensor w3_packed, Tensor bias3, "
+          "Tensor(a!) out) -> ()", &encoder_head);
 }

@@ -12,7 +12,10 @@
   batrack_amd.frontend.tracker.embed_conv             `embedConv` with the Fourier embedding of (x, y, z) computed in the kernel
   batrack_amd.frontend.tracker.sample_features        each new track's features from its own frame
   batrack_amd.frontend.tracker.install                make the reference's MDTracker use `forward`
-  batrack_amd.frontend.observe.window_observations  tracker output -> the BA's targets and weights
+  batrack_amd.frontend.encoder.encoder_head           the encoder's head: pyramid resize, 416 -> 256 conv, instance norm, 1 x 1, two launches
+  batrack_amd.frontend.encoder.forward                `BasicEncoder.forward` around it (the residual layers called as they are)
+  batrack_amd.frontend.encoder.install                make the reference's BasicEncoder use `forward`
+  batrack_amd.frontend.observe.window_observations tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning
   batrack_amd.frontend.patches.generate_patches      patch selection, depth initialisation and colours of a new frame
   batrack_amd.frontend.patches.image_gradient        the pooled gradient-magnitude map it ranks by
