@@ -1,0 +1,416 @@
+// encoder_trunk.hip — one residual block of the feature encoder's layer1..4 (include/batrack_encoder.h holds the
+// specification): k_res_conv, k_res_stats, k_res_join.
+//
+// k_res_conv<NORM, S, SHORT, NT> is a 3 x 3 convolution with zero padding 1 and stride S from c_in to 16 NT channels, an
+// implicit GEMM on v_mfma_f32_16x16x4_f32 with k_head_conv's tile (csrc/conv_tile.hpp): rows are output pixels, columns
+// output channels, K = 9 taps x c_in.
+//   tile     a workgroup (4 waves) owns a 16 x 8 tile of OUTPUT pixels of one frame and all 16 NT <= 128 columns.
+//   K-chunk  8 input channels at a time: their halo tile (18 x 10 input pixels at stride 1, 33 x 17 at stride 2) is staged in
+//            LDS beside their 9 x 8 x 16 NT weights.  NORM: a halo element inside the input map is
+//            max(fl(fl(v - mean) * rstd), 0) with the (frame, channel)'s statistics, one outside is 0: the padding is of the
+//            normalised, rectified map, which is never in memory.  Otherwise v, or 0 outside; the input is a strided view.
+//            At stride 1 the chunk's global loads go into registers while the chunk before it is multiplied and reach LDS
+//            (normalised) when that one is done; at stride 2, with three accumulator sets, they are staged directly, six
+//            unconditional loads at a time.
+//   stride 2 a halo row is kept as its 17 even columns, then its 16 odd ones: output x reads column 2x + kx, which is
+//            element x of the even part (kx = 0), x of the odd part (kx = 1) or x + 1 of the even part (kx = 2): the A operand
+//            is one ds_read_b32 at unit lane stride, as at stride 1.  (Read from the code, not measured against the
+//            interleaved row: the split costs the staging one select.)
+//   order    chunk ascending, tap, group of four channels; every CT_FLUSH = 2 chunks (144 products) the accumulators are
+//            added into a second set and start again from zero; the bias last.  k_head_conv's order.
+//   SHORT    the block's 1 x 1 stride-2 shortcut reads exactly the centre tap's staged pixel: a second GEMM from the same
+//            chunk with the chunk's 8 x 16 NT shortcut weights, ONE fma chain over c_in products, the bias last, into a
+//            second raw map with its own statistics.
+//   output   raw = conv + bias as [F][16 NT][ho * wo] planes, and per (frame, tile, column) the float64 sum and sum of
+//            squares of the stored values (tile_store_stats).
+// k_res_stats: one thread per (map, frame, channel) adds the tiles' partials in tile order and stores mean and rstd as floats.
+// A launch of its own: at 192 x 256 a frame has 384 tiles, and every workgroup re-reducing them would read more than it stages.
+// k_res_join: out = max(fl(s + max(fl(fl(raw2 - m2) * r2), 0)), 0); s = x (stride 1) or fl(fl(rawd - md) * rd) (stride 2).
+// What they leave on the table is in DESIGN.md.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/batrack_ba.h"
+#include "../../include/batrack_encoder.h"
+#include "conv_tile.hpp"
+
+namespace bt {
+
+struct ResView {                 // a strided [F, C, h, w] view, by value in the kernel's arguments
+    const float *p;
+    long long sf, sc, sy, sx;
+    int h, w;
+};
+
+template <int S> struct ResGeom {
+    static constexpr int HW = S * (CT_TW - 1) + 3, HH = S * (CT_TH - 1) + 3, HALO = HW * HH;    // 18 x 10, 33 x 17
+    static constexpr int EVEN = (HW + 1) / 2;                                                  // stride 2: the even columns first
+    static constexpr int PL = ((HALO + 15) / 32) * 32 + 16;                                    // plane stride, 16 mod 32
+    static_assert(PL >= HALO && PL % 32 == 16, "LDS plane stride");
+};
+
+constexpr int RC_MAXC = 128;
+
+// -------------------------------------------------------------------------------------------------------------- k_res_conv
+template <bool NORM, int S, bool SHORT, int NT>
+__global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHORT ? 1 : 2))) void k_res_conv(const ResView X, int c_in, const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                         const float *__restrict__ wp, const float *__restrict__ bias,
+                                                         const float *__restrict__ wd, const float *__restrict__ bd, int ho, int wo, int tiles_x,
+                                                         float *__restrict__ raw, double *__restrict__ part, float *__restrict__ rawd,
+                                                         double *__restrict__ partd) {
+    using G = ResGeom<S>;
+    constexpr int COLS = 16 * NT, WLD = COLS + 16, HW = G::HW, HALO = G::HALO, PL = G::PL;
+    static_assert(WLD % 32 == 16, "LDS weight row stride");
+    static_assert(9 * CT_KC * WLD * sizeof(float) >= (CT_THREADS / 64) * COLS * 2 * sizeof(double), "the statistics reuse the weights' LDS");
+    static_assert(!SHORT || S == 2, "the shortcut belongs to the stride-2 block");
+    __shared__ __attribute__((aligned(16))) float w_l[9 * CT_KC * WLD];          // [tap][channel of the chunk][WLD]
+    __shared__ __attribute__((aligned(16))) float wd_l[SHORT ? CT_KC * WLD : 4];  // [channel of the chunk][WLD]
+    __shared__ float in_l[CT_KC * PL];                                            // [channel of the chunk][halo pixel]
+    __shared__ float mean_l[NORM ? RC_MAXC : 1], rstd_l[NORM ? RC_MAXC : 1];
+    static_assert(sizeof(float) * (9 * CT_KC * WLD + (SHORT ? CT_KC * WLD : 4) + CT_KC * PL + (NORM ? 2 * RC_MAXC : 2)) <= 65536, "static LDS");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
+    const int f = blockIdx.y, ty0 = (blockIdx.x / tiles_x) * CT_TH, tx0 = (blockIdx.x % tiles_x) * CT_TW;
+    const int iy0 = S * ty0 - 1, ix0 = S * tx0 - 1;              // the halo's first input row and column
+    const long long hwo = (long long)ho * wo;
+
+    if constexpr (NORM) {
+        for (int c = tid; c < c_in; c += CT_THREADS) { mean_l[c] = mean[(long long)f * c_in + c]; rstd_l[c] = rstd[(long long)f * c_in + c]; }
+    }
+
+    ct_f32x4 acc[2][NT], tot[2][NT], accd[SHORT ? 2 : 1][SHORT ? NT : 1];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) acc[r][ct] = tot[r][ct] = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (SHORT) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int ct = 0; ct < NT; ++ct) accd[r][ct] = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+
+    // Staging is split in two: the global loads of a chunk go into registers (`fetch`) while the chunk before it is
+    // multiplied, and reach LDS (`stage`, which normalises) when that one is done.  The order of the sums does not change.
+    constexpr int W4 = 9 * CT_KC * (COLS / 4), D4 = CT_KC * (COLS / 4), HE = CT_KC * HALO;
+    constexpr int WN = (W4 + CT_THREADS - 1) / CT_THREADS, HN = (HE + CT_THREADS - 1) / CT_THREADS;
+    static_assert(D4 <= CT_THREADS && HN <= 32, "one shortcut float4 a thread; the inside mask is 32 bits");
+    ct_f32x4 wreg[WN], dreg = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float hreg[HN];
+    unsigned inside = 0;                                         // bit k: hreg[k] is an element of the input map
+    const float *xf = X.p + (long long)f * X.sf;
+    const int chunks = c_in / CT_KC;
+    auto fetch = [&](int chunk) __attribute__((always_inline)) {
+        const ct_f32x4 *wsrc = reinterpret_cast<const ct_f32x4 *>(wp + (size_t)chunk * 9 * CT_KC * COLS);
+#pragma unroll
+        for (int k = 0; k < WN; ++k) {
+            const int i = tid + k * CT_THREADS;
+            if (i < W4) wreg[k] = wsrc[i];
+        }
+        if constexpr (SHORT) {
+            if (tid < D4) dreg = reinterpret_cast<const ct_f32x4 *>(wd + (size_t)chunk * CT_KC * COLS)[tid];
+        }
+        const float *src = xf + (long long)chunk * CT_KC * X.sc;
+        inside = 0;
+#pragma unroll
+        for (int k = 0; k < HN; ++k) {
+            const int idx = tid + k * CT_THREADS;
+            const int chl = idx / HALO, p = idx - chl * HALO, hy = p / HW, hx = p - hy * HW;
+            const int gy = iy0 + hy, gx = ix0 + hx;
+            float v = 0.0f;                                      // zero padding of the (normalised, rectified) input map
+            if (idx < HE && gy >= 0 && gy < X.h && gx >= 0 && gx < X.w) {
+                v = src[chl * X.sc + gy * X.sy + gx * X.sx];
+                inside |= 1u << k;
+            }
+            hreg[k] = v;
+        }
+    };
+    auto stage = [&](int chunk) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < WN; ++k) {
+            const int i = tid + k * CT_THREADS;
+            const int row = i / (COLS / 4), c4 = i - row * (COLS / 4);
+            if (i < W4) *reinterpret_cast<ct_f32x4 *>(w_l + row * WLD + c4 * 4) = wreg[k];
+        }
+        if constexpr (SHORT) {
+            const int row = tid / (COLS / 4), c4 = tid - row * (COLS / 4);
+            if (tid < D4) *reinterpret_cast<ct_f32x4 *>(wd_l + row * WLD + c4 * 4) = dreg;
+        }
+#pragma unroll
+        for (int k = 0; k < HN; ++k) {
+            const int idx = tid + k * CT_THREADS;
+            const int chl = idx / HALO, p = idx - chl * HALO, hy = p / HW, hx = p - hy * HW;
+            float v = hreg[k];
+            if constexpr (NORM) {
+                if ((inside >> k) & 1u) {
+                    const int c = chunk * CT_KC + chl;
+                    v = __fmul_rn(__fsub_rn(v, mean_l[c]), rstd_l[c]);
+                    v = v > 0.0f ? v : 0.0f;
+                }
+            }
+            const int col = S == 1 ? hx : ((hx & 1) ? G::EVEN + (hx >> 1) : (hx >> 1));
+            if (idx < HE) in_l[chl * PL + hy * HW + col] = v;
+        }
+    };
+    auto stage_direct = [&](int chunk) __attribute__((always_inline)) {      // the same elements to the same places, not through registers
+        const float4 *wsrc = reinterpret_cast<const float4 *>(wp + (size_t)chunk * 9 * CT_KC * COLS);
+#pragma unroll 3
+        for (int i = tid; i < W4; i += CT_THREADS) {
+            const int row = i / (COLS / 4), c4 = i - row * (COLS / 4);
+            *reinterpret_cast<float4 *>(w_l + row * WLD + c4 * 4) = wsrc[i];
+        }
+        if constexpr (SHORT) {
+            const int row = tid / (COLS / 4), c4 = tid - row * (COLS / 4);
+            if (tid < D4) *reinterpret_cast<float4 *>(wd_l + row * WLD + c4 * 4) = reinterpret_cast<const float4 *>(wd + (size_t)chunk * CT_KC * COLS)[tid];
+        }
+        const float *src = xf + (long long)chunk * CT_KC * X.sc;
+        // six loads at a time, every one unconditional (the address clamped into the map, the value dropped outside): a load
+        // behind a branch that is used in its own trip waits for memory every trip
+        constexpr int HB = 6;
+#pragma unroll 1
+        for (int k0 = 0; k0 < HN; k0 += HB) {
+            float v[HB];
+#pragma unroll
+            for (int j = 0; j < HB; ++j) {
+                const int idx = tid + (k0 + j) * CT_THREADS, ic = idx < HE ? idx : HE - 1;
+                const int chl = ic / HALO, p = ic - chl * HALO, hy = p / HW, hx = p - hy * HW;
+                const int gy = iy0 + hy, gx = ix0 + hx;
+                const bool in = gy >= 0 && gy < X.h && gx >= 0 && gx < X.w;
+                const int cy = gy < 0 ? 0 : (gy < X.h ? gy : X.h - 1), cx = gx < 0 ? 0 : (gx < X.w ? gx : X.w - 1);
+                float t = src[chl * X.sc + cy * X.sy + cx * X.sx];
+                if constexpr (NORM) {
+                    const int c = chunk * CT_KC + chl;
+                    t = __fmul_rn(__fsub_rn(t, mean_l[c]), rstd_l[c]);
+                    t = t > 0.0f ? t : 0.0f;
+                }
+                v[j] = in ? t : 0.0f;                            // zero padding of the (normalised, rectified) input map
+            }
+#pragma unroll
+            for (int j = 0; j < HB; ++j) {
+                const int idx = tid + (k0 + j) * CT_THREADS;
+                const int chl = idx / HALO, p = idx - chl * HALO, hy = p / HW, hx = p - hy * HW;
+                const int col = S == 1 ? hx : ((hx & 1) ? G::EVEN + (hx >> 1) : (hx >> 1));
+                if (idx < HE) in_l[chl * PL + hy * HW + col] = v[j];
+            }
+        }
+    };
+    // stride 2 stages directly: 18 halo registers on top of its three accumulator sets spill (kernel-resource-usage), and it
+    // is a twelfth of the trunk's products
+    constexpr bool AHEAD = S == 1;
+    if constexpr (AHEAD) fetch(0);
+    for (int chunk = 0; chunk < chunks; ++chunk) {
+        __syncthreads();                                         // the previous chunk's reads are done (and the statistics are written)
+        if constexpr (AHEAD) stage(chunk);
+        else stage_direct(chunk);
+        __syncthreads();
+        if constexpr (AHEAD) {
+            if (chunk + 1 < chunks) fetch(chunk + 1);            // in flight while this chunk is multiplied
+        }
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - 3 * ky;
+            const int coff = S == 1 ? kx : (kx == 1 ? G::EVEN : (kx >> 1));
+#pragma unroll
+            for (int s = 0; s < CT_KC / 4; ++s) {
+                const float *ap = in_l + (4 * s + q) * PL + (S * 2 * wave + ky) * HW + l16 + coff;
+                const float a0 = ap[0], a1 = ap[S * HW];
+                const float *wr = w_l + (tap * CT_KC + 4 * s + q) * WLD + l16;
+#pragma unroll
+                for (int ct = 0; ct < NT; ++ct) {
+                    const float b = wr[ct * 16];
+                    acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][ct], 0, 0, 0);
+                    acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][ct], 0, 0, 0);
+                }
+                if constexpr (SHORT) if (tap == 4) {                         // the centre tap's pixel is the shortcut's
+                    const float *dr = wd_l + (4 * s + q) * WLD + l16;
+#pragma unroll
+                    for (int ct = 0; ct < NT; ++ct) {
+                        const float b = dr[ct * 16];
+                        accd[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, accd[0][ct], 0, 0, 0);
+                        accd[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, accd[1][ct], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        if (chunk % CT_FLUSH == CT_FLUSH - 1) tile_flush<NT>(tot, acc);      // a block is complete: one rounded add into the total
+    }
+    __syncthreads();                                             // the last chunk's weights are read: their LDS takes the statistics
+    double *red = reinterpret_cast<double *>(w_l);
+    const long long tile = (long long)f * gridDim.x + blockIdx.x;
+    tile_store_stats<NT>(tot, bias, raw + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, part + tile * COLS * 2);
+    if constexpr (SHORT) tile_store_stats<NT>(accd, bd, rawd + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, partd + tile * COLS * 2);
+}
+
+// ------------------------------------------------------------------------------------------------------------- k_res_stats
+// part [maps][F][tiles][C][2]; mean, rstd [maps][F][C]; thread i is (map, frame, channel) i
+__global__ __launch_bounds__(64) void k_res_stats(const double *__restrict__ part, int tiles, int C, long long count, double n,
+                                                  float *__restrict__ mean, float *__restrict__ rstd) {
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const long long mf = i / C;
+    const int c = (int)(i - mf * C);
+    float m, r;
+    tile_order_stats(part + (mf * tiles * C + c) * 2, (long long)C * 2, tiles, n, m, r);
+    mean[i] = m;
+    rstd[i] = r;
+}
+
+// -------------------------------------------------------------------------------------------------------------- k_res_join
+// raw2, rawd [F][C][n]; the statistics [F][C]; X the block's input (DOWN: unused); out [F][C][n].  V pixels a thread.
+template <bool DOWN, int V>
+__global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2, const float *__restrict__ m2, const float *__restrict__ r2,
+                                                  const float *__restrict__ rawd, const float *__restrict__ md, const float *__restrict__ rd,
+                                                  const ResView X, int C, int wo, long long n, float *__restrict__ out) {
+    const int c = blockIdx.y, f = blockIdx.z;
+    const long long p = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (p >= n) return;
+    const long long fc = (long long)f * C + c, base = fc * n + p;
+    const float mean2 = m2[fc], rstd2 = r2[fc];
+    float y[V], s[V];
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(raw2 + base);
+        y[0] = t.x; y[1] = t.y; y[2] = t.z; y[3] = t.w;
+    } else {
+        y[0] = raw2[base];
+    }
+    if (DOWN) {
+        const float meand = md[fc], rstdd = rd[fc];
+        if constexpr (V == 4) {
+            const float4 t = *reinterpret_cast<const float4 *>(rawd + base);
+            s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
+        } else {
+            s[0] = rawd[base];
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) s[j] = __fmul_rn(__fsub_rn(s[j], meand), rstdd);
+    } else {
+        const int py = (int)(p / wo), px = (int)(p - (long long)py * wo);
+        const float *xs = X.p + f * X.sf + c * X.sc + py * X.sy + px * X.sx;
+        if constexpr (V == 4) {                                            // V == 4 only with unit x stride, wo % 4 == 0 and 16-byte rows
+            const float4 t = *reinterpret_cast<const float4 *>(xs);
+            s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
+        } else {
+            s[0] = xs[0];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        float z = __fmul_rn(__fsub_rn(y[j], mean2), rstd2);
+        z = z > 0.0f ? z : 0.0f;
+        z = __fadd_rn(s[j], z);
+        y[j] = z > 0.0f ? z : 0.0f;
+    }
+    if constexpr (V == 4) *reinterpret_cast<float4 *>(out + base) = float4{y[0], y[1], y[2], y[3]};
+    else out[base] = y[0];
+}
+
+constexpr long long kResI31 = 2147483647LL;
+
+static bool res_channels(long long c) { return c == 64 || c == 96 || c == 128; }
+
+static long long res_tiles(long long ho, long long wo) { return ((ho + CT_TH - 1) / CT_TH) * ((wo + CT_TW - 1) / CT_TW); }
+
+struct ResLayout {               // byte offsets into the workspace; maps = 2 (raw1, raw2) or 3 (raw1, rawd, raw2)
+    long long ho, wo, n, tiles, maps;
+    size_t part, stat, bytes;
+};
+
+// false when the sizes are refused
+static bool res_layout(long long F, long long c_out, long long h, long long w, long long stride, ResLayout *L) {
+    if (F < 1 || h < 1 || w < 1 || F > kResI31 || h > kResI31 || w > kResI31 || !res_channels(c_out) || (stride != 1 && stride != 2)) return false;
+    L->ho = (h - 1) / stride + 1; L->wo = (w - 1) / stride + 1; L->n = L->ho * L->wo; L->tiles = res_tiles(L->ho, L->wo);
+    L->maps = stride == 1 ? 2 : 3;
+    if ((__int128)L->maps * F * c_out * L->ho * L->wo > kResI31 || L->tiles > kResI31) return false;
+    L->part = ((size_t)L->maps * F * c_out * L->n * sizeof(float) + 15) & ~(size_t)15;
+    L->stat = L->part + (size_t)L->maps * F * L->tiles * c_out * 2 * sizeof(double);
+    L->bytes = L->stat + (size_t)L->maps * F * c_out * 2 * sizeof(float);
+    return true;
+}
+
+template <bool NORM, int S, bool SHORT>
+static bool res_conv_launch(hipStream_t st, long long tiles, long long F, long long c_out, const ResView &X, int c_in, const float *mean, const float *rstd,
+                            const float *wp, const float *bias, const float *wd, const float *bd, int ho, int wo, int tiles_x, float *raw, double *part,
+                            float *rawd, double *partd) {
+    const dim3 grid((unsigned)tiles, (unsigned)F), block(CT_THREADS);
+    if (c_out == 64)
+        hipLaunchKernelGGL((k_res_conv<NORM, S, SHORT, 4>), grid, block, 0, st, X, c_in, mean, rstd, wp, bias, wd, bd, ho, wo, tiles_x, raw, part, rawd, partd);
+    else if (c_out == 96)
+        hipLaunchKernelGGL((k_res_conv<NORM, S, SHORT, 6>), grid, block, 0, st, X, c_in, mean, rstd, wp, bias, wd, bd, ho, wo, tiles_x, raw, part, rawd, partd);
+    else
+        hipLaunchKernelGGL((k_res_conv<NORM, S, SHORT, 8>), grid, block, 0, st, X, c_in, mean, rstd, wp, bias, wd, bd, ho, wo, tiles_x, raw, part, rawd, partd);
+    return hipGetLastError() == hipSuccess;
+}
+
+}  // namespace bt
+
+extern "C" size_t bt_res_block_workspace_bytes(int64_t F, int64_t c_out, int64_t h_in, int64_t w_in, int64_t stride) {
+    bt::ResLayout L;
+    return bt::res_layout(F, c_out, h_in, w_in, stride, &L) ? L.bytes : 0;
+}
+
+extern "C" int bt_res_block(const bt_encoder_level *x, const struct bt_res_block *blk, int64_t F, void *workspace, float *out, void *stream) {
+    using namespace bt;
+    if (!x || !blk || !workspace || !out || !x->data || !blk->w1 || !blk->b1 || !blk->w2 || !blk->b2) return BT_EINVAL;
+    if (F < 1 || x->h < 1 || x->w < 1 || x->C < 1 || blk->c_in < 1 || blk->c_out < 1 || blk->stride < 1) return BT_EINVAL;
+    if (x->sf < 0 || x->sc < 0 || x->sy < 0 || x->sx < 0) return BT_EINVAL;
+    if (((uintptr_t)blk->w1 & 15) || ((uintptr_t)blk->w2 & 15) || ((uintptr_t)blk->wd & 15) || ((uintptr_t)workspace & 15)) return BT_EINVAL;
+    if (blk->stride == 1 && (blk->wd || blk->bd)) return BT_EINVAL;
+    if (blk->stride == 2 && (!blk->wd || !blk->bd)) return BT_EINVAL;
+    const long long c_in = blk->c_in, c_out = blk->c_out, stride = blk->stride;
+    if (!res_channels(c_in) || !res_channels(c_out) || x->C != c_in || stride > 2 || (stride == 1 && c_in != c_out) || F > 65535) return BT_EUNSUPPORTED;
+    if (x->h > kResI31 || x->w > kResI31 || x->sf > kResI31 || x->sc > kResI31 || x->sy > kResI31 || x->sx > kResI31) return BT_EUNSUPPORTED;
+    if ((__int128)F * c_in * x->h * x->w > kResI31
+        || (__int128)(F - 1) * x->sf + (__int128)(c_in - 1) * x->sc + (__int128)(x->h - 1) * x->sy + (__int128)(x->w - 1) * x->sx > kResI31)
+        return BT_EUNSUPPORTED;
+    ResLayout L;
+    if (!res_layout(F, c_out, x->h, x->w, stride, &L)) return BT_EUNSUPPORTED;
+
+    hipStream_t st = (hipStream_t)stream;
+    const long long slot_f = (long long)F * c_out * L.n, slot_p = (long long)F * L.tiles * c_out * 2, slot_s = (long long)F * c_out;
+    float *raw1 = (float *)workspace, *rawd = stride == 2 ? raw1 + slot_f : nullptr, *raw2 = raw1 + (L.maps - 1) * slot_f;
+    double *part1 = (double *)((char *)workspace + L.part), *partd = stride == 2 ? part1 + slot_p : nullptr, *part2 = part1 + (L.maps - 1) * slot_p;
+    float *mean1 = (float *)((char *)workspace + L.stat), *rstd1 = mean1 + L.maps * slot_s;
+    float *meand = mean1 + slot_s, *rstdd = rstd1 + slot_s, *mean2 = mean1 + (L.maps - 1) * slot_s, *rstd2 = rstd1 + (L.maps - 1) * slot_s;
+    const int ho = (int)L.ho, wo = (int)L.wo, tiles_x = (int)((L.wo + CT_TW - 1) / CT_TW);
+    const ResView X{x->data, x->sf, x->sc, x->sy, x->sx, (int)x->h, (int)x->w};
+    const ResView Y{raw1, c_out * L.n, L.n, L.wo, 1, ho, wo};
+
+    bool ok = stride == 1
+        ? res_conv_launch<false, 1, false>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, nullptr, nullptr, ho, wo, tiles_x, raw1, part1, nullptr, nullptr)
+        : res_conv_launch<false, 2, true>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, blk->wd, blk->bd, ho, wo, tiles_x, raw1, part1, rawd, partd);
+    if (!ok) return BT_EHIP;
+    const long long count1 = (L.maps - 1) * slot_s;              // raw1's statistics, and the shortcut's beside them
+    hipLaunchKernelGGL(k_res_stats, dim3((unsigned)((count1 + 63) / 64)), dim3(64), 0, st, (const double *)part1, (int)L.tiles, (int)c_out, count1,
+                       (double)L.n, mean1, rstd1);
+    if (hipGetLastError() != hipSuccess) return BT_EHIP;
+    if (!res_conv_launch<true, 1, false>(st, L.tiles, F, c_out, Y, (int)c_out, mean1, rstd1, blk->w2, blk->b2, nullptr, nullptr, ho, wo, tiles_x, raw2, part2,
+                                         nullptr, nullptr))
+        return BT_EHIP;
+    hipLaunchKernelGGL(k_res_stats, dim3((unsigned)((slot_s + 63) / 64)), dim3(64), 0, st, (const double *)part2, (int)L.tiles, (int)c_out, slot_s,
+                       (double)L.n, mean2, rstd2);
+    if (hipGetLastError() != hipSuccess) return BT_EHIP;
+
+    const bool rows16 = L.n % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    if (stride == 2) {
+        if (rows16)
+            hipLaunchKernelGGL((k_res_join<true, 4>), dim3((unsigned)((L.n / 4 + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
+                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)rawd, (const float *)meand, (const float *)rstdd, X,
+                               (int)c_out, wo, L.n, out);
+        else
+            hipLaunchKernelGGL((k_res_join<true, 1>), dim3((unsigned)((L.n + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
+                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)rawd, (const float *)meand, (const float *)rstdd, X,
+                               (int)c_out, wo, L.n, out);
+    } else {
+        const bool xrows16 = rows16 && L.wo % 4 == 0 && x->sx == 1 && x->sy % 4 == 0 && x->sc % 4 == 0 && x->sf % 4 == 0 && ((uintptr_t)x->data & 15) == 0;
+        if (xrows16)
+            hipLaunchKernelGGL((k_res_join<false, 4>), dim3((unsigned)((L.n / 4 + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
+                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, X,
+                               (int)c_out, wo, L.n, out);
+        else
+            hipLaunchKernelGGL((k_res_join<false, 1>), dim3((unsigned)((L.n + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
+                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, X,
+                               (int)c_out, wo, L.n, out);
+    }
+    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+}

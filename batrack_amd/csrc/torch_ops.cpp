@@ -67,6 +67,9 @@
 //                             Tensor(a!) out) -> ()
 //       bt_encoder_head (include/batrack_encoder.h): the levels [F, 64 / 96 / 128 / 128, h_l, w_l], any strides; w2_packed
 //       [52, 9, 8, 256]; w3_packed [256, 128]; out [F, 128, h, w] contiguous, whose h and w are the output map's
+//   batrack_hip::res_block(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor? wd, Tensor? bd, int stride, Tensor(a!) out) -> ()
+//       bt_res_block (include/batrack_encoder.h): x [F, c_in, h, w], any strides; w1 [c_in / 8, 9, 8, c_out]; w2 [c_out / 8, 9, 8,
+//       c_out]; wd [c_in, c_out] and bd exactly when stride is 2; out [F, c_out, ho, wo] contiguous
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -549,6 +552,38 @@ void encoder_head(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c,
     TORCH_CHECK(rc == BT_OK, op, "bt_encoder_head failed with status ", rc);
 }
 
+void res_block(const at::Tensor &x, const at::Tensor &w1, const at::Tensor &b1, const at::Tensor &w2, const at::Tensor &b2,
+               const c10::optional<at::Tensor> &wd, const c10::optional<at::Tensor> &bd, int64_t stride, at::Tensor out) {
+    const char *op = "batrack_hip::res_block: ";
+    const bool down = wd.has_value() && wd->defined();
+    TORCH_CHECK(down == (bd.has_value() && bd->defined()), op, "wd and bd come together");
+    std::vector<const at::Tensor *> all = {&x, &w1, &b1, &w2, &b2, &out};
+    if (down) { all.push_back(&*wd); all.push_back(&*bd); }
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->device() == x.device(), op, "tensors must be on one device");
+    }
+    TORCH_CHECK(stride == 1 || stride == 2, op, "stride must be 1 or 2");
+    TORCH_CHECK(down == (stride == 2), op, "wd and bd are given exactly when stride is 2");
+    TORCH_CHECK(x.dim() == 4 && x.numel() > 0 && out.dim() == 4 && out.is_contiguous(), op, "x must be [F, c_in, h, w] and not empty, out contiguous");
+    const int64_t F = x.size(0), c_in = x.size(1), h = x.size(2), w = x.size(3), c_out = out.size(1);
+    TORCH_CHECK(out.size(0) == F && out.size(2) == (h - 1) / stride + 1 && out.size(3) == (w - 1) / stride + 1, op,
+                "out must be [F, c_out, (h - 1) / stride + 1, (w - 1) / stride + 1]");
+    TORCH_CHECK(w1.is_contiguous() && w1.numel() == 9 * c_in * c_out && b1.is_contiguous() && b1.numel() == c_out && w2.is_contiguous()
+                && w2.numel() == 9 * c_out * c_out && b2.is_contiguous() && b2.numel() == c_out, op,
+                "w1 [c_in / 8, 9, 8, c_out], b1 [c_out], w2 [c_out / 8, 9, 8, c_out], b2 [c_out], all contiguous");
+    if (down) TORCH_CHECK(wd->is_contiguous() && wd->numel() == c_in * c_out && bd->is_contiguous() && bd->numel() == c_out, op,
+                          "wd [c_in, c_out] and bd [c_out], contiguous");
+    const size_t bytes = bt_res_block_workspace_bytes(F, c_out, h, w, stride);
+    TORCH_CHECK(bytes > 0, op, "channels must be 64, 96 or 128 and the element counts must not pass 2^31 - 1");
+    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options().dtype(at::kDouble));      // needs no initialisation
+    const bt_encoder_level lx{x.data_ptr<float>(), c_in, h, w, x.stride(0), x.stride(1), x.stride(2), x.stride(3)};
+    const struct bt_res_block blk{w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(),
+                           down ? wd->data_ptr<float>() : nullptr, down ? bd->data_ptr<float>() : nullptr, c_in, c_out, stride};
+    const int rc = bt_res_block(&lx, &blk, F, ws.data_ptr(), out.data_ptr<float>(), c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_res_block failed with status ", rc);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -584,4 +619,5 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("feat_sample(Tensor fmaps, Tensor frames, Tensor xy) -> Tensor", &feat_sample);
     m.def("encoder_head(Tensor a, Tensor b, Tensor c, Tensor d, Tensor w2_packed, Tensor bias2, Tensor w3_packed, Tensor bias3, "
           "Tensor(a!) out) -> ()", &encoder_head);
+    m.def("res_block(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor? wd, Tensor? bd, int stride, Tensor(a!) out) -> ()", &res_block);
 }

@@ -13,7 +13,11 @@
   batrack_amd.frontend.tracker.sample_features        each new track's features from its own frame
   batrack_amd.frontend.tracker.install                make the reference's MDTracker use `forward`
   batrack_amd.frontend.encoder.encoder_head           the encoder's head: pyramid resize, 416 -> 256 conv, instance norm, 1 x 1, two launches
-  batrack_amd.frontend.encoder.forward                `BasicEncoder.forward` around it (the residual layers called as they are)
+  batrack_amd.frontend.encoder.residual_block         one residual block of layer1..4: no normalised map in memory, five launches
+  batrack_amd.frontend.encoder.encoder_trunk          layer1..4, the eight blocks: (a, b, c, d)
+  batrack_amd.frontend.encoder.pack_block_weights     a block's weights in the layouts the kernels stage
+  batrack_amd.frontend.encoder.packed_block           the same, cached per block
+  batrack_amd.frontend.encoder.forward                `BasicEncoder.forward` around them (the stem called as it is; encoder.DEVICE_LAYERS)
   batrack_amd.frontend.encoder.install                make the reference's BasicEncoder use `forward`
   batrack_amd.frontend.observe.window_observations tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning

@@ -1,6 +1,7 @@
-"""The feature encoder's head (the reference's main/frontend/core/cotracker/blocks.py:241-273, the last third of
-`BasicEncoder.forward` with norm_fn="instance"), HIP underneath (batrack_amd/csrc/encoder_head.hip through
-include/batrack_encoder.h, which holds the specification).
+"""The feature encoder's trunk and head (the reference's main/frontend/core/cotracker/blocks.py: the eight `ResidualBlock`s
+of layer1..4, lines 16-75, and lines 241-273, the last third of `BasicEncoder.forward`, with norm_fn="instance"), HIP
+underneath (batrack_amd/csrc/encoder_trunk.hip and encoder_head.hip through include/batrack_encoder.h, which holds the
+specification).
 
     pack_head_weights(conv2_weight [256,416,3,3], conv3_weight [128,256,1,1]) -> ([52,9,8,256], [256,128])
                                                                                  the layouts the kernels stage (permutations)
@@ -9,9 +10,17 @@ include/batrack_encoder.h, which holds the specification).
                                                                                  align_corners), concatenated, conv2, instance
                                                                                  norm, ReLU, conv3: neither the resized copies
                                                                                  nor the concatenation is in memory; two launches
+    pack_block_weights(conv1_w, conv2_w, down_w=None) -> (w1, w2, wd or None)    [c/8, 9, 8, c_out] twice and [c_in, c_out]
+    packed_block(block) -> (w1, b1, w2, b2, wd, bd)                              cached per block; wd, bd None at stride 1
+    residual_block(x, block, out=None) -> [F, c_out, ho, wo]                     one residual block: conv, norm, ReLU, conv, norm,
+                                                                                 ReLU, (shortcut conv, norm,) add, ReLU; no
+                                                                                 normalised map is in memory; five launches
+    encoder_trunk(x, layer1, layer2, layer3, layer4) -> (a, b, c, d)             the eight blocks, always on the kernels
     forward(self, x)                                                             `BasicEncoder.forward` in our own words: conv1,
-                                                                                 norm1, relu1 and layer1..4 are called as they
-                                                                                 are, then `encoder_head`
+                                                                                 norm1, relu1 are called as they are; a layer in
+                                                                                 DEVICE_LAYERS that is a Sequential of residual
+                                                                                 blocks runs on the kernels, any other layer is
+                                                                                 called as it is; then `encoder_head`
 
 Inference only (no autograd through the kernels), float32, GPU tensors only; no CPU fallback.
 
@@ -27,6 +36,10 @@ from .. import _lib
 LEVELS = (64, 96, 128, 128)  # BT_ENC_CA .. BT_ENC_CD
 CIN, CMID, COUT = 416, 256, 128
 KCHUNK = 8                   # BT_WINDOW_KCHUNK
+BLOCK_CHANNELS = (64, 96, 128)
+# The layers `forward` sends to the kernels: those whose measured device time is not above torch's at 12 and at 6 frames of
+# 64 x 192 x 256 (profiles/r26_encoder_trunk.txt; DESIGN.md f-13 has both numbers of every layer).
+DEVICE_LAYERS = ("layer1", "layer2")
 
 
 def _gpu(name, t, what):
@@ -118,6 +131,148 @@ def _plain_instance_norm(m):
         and getattr(m, "weight", None) is None and getattr(m, "running_mean", None) is None
 
 
+# ------------------------------------------------------------------------------------------------------ the residual blocks
+def pack_block_weights(conv1_w, conv2_w, down_w=None):
+    """[c_out, c_in, 3, 3] -> [c_in / 8, 9, 8, c_out]: w1[c // 8, 3 ky + kx, c % 8, m] = conv1_w[m, c, ky, kx]; conv2_w
+    [c_out, c_out, 3, 3] likewise; down_w [c_out, c_in, 1, 1] -> [c_in, c_out]: wd[c, m] = down_w[m, c, 0, 0] (None stays None).
+    Permutations of the weights (any device)."""
+    c_out, c_in = (int(v) for v in conv1_w.shape[:2]) if conv1_w.dim() == 4 else (-1, -1)
+    if tuple(conv1_w.shape[2:]) != (3, 3) or c_in not in BLOCK_CHANNELS or c_out not in BLOCK_CHANNELS:
+        raise RuntimeError(f"residual_block: conv1 must be 3 x 3 between 64, 96 or 128 channels, not {tuple(conv1_w.shape)}")
+    if tuple(conv2_w.shape) != (c_out, c_out, 3, 3):
+        raise RuntimeError(f"residual_block: conv2 must be 3 x 3 from {c_out} to {c_out} channels, not {tuple(conv2_w.shape)}")
+    if down_w is not None and tuple(down_w.shape) != (c_out, c_in, 1, 1):
+        raise RuntimeError(f"residual_block: downsample[0] must be 1 x 1 from {c_in} to {c_out} channels, not {tuple(down_w.shape)}")
+
+    def pack(w):
+        return w.detach().float().permute(1, 2, 3, 0).reshape(w.shape[1] // KCHUNK, KCHUNK, 9, w.shape[0]).permute(0, 2, 1, 3).contiguous()
+    wd = None if down_w is None else down_w.detach().float().reshape(c_out, c_in).t().contiguous()
+    return pack(conv1_w), pack(conv2_w), wd
+
+
+def _conv_is(conv, kernel, padding, strides):
+    return isinstance(conv, torch.nn.Conv2d) and tuple(conv.kernel_size) == (kernel, kernel) and tuple(conv.padding) == (padding, padding) \
+        and tuple(conv.stride) in strides and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.bias is not None \
+        and (not padding or getattr(conv, "padding_mode", "zeros") == "zeros")
+
+
+def is_residual_shaped(block):
+    """The attributes of a `ResidualBlock`, whatever its class: conv1 and conv2 3 x 3 convolutions, norm1, norm2 and a
+    `downsample` attribute.  What `check_block` then refuses is an error, not a reason to leave the layer to torch."""
+    return all(isinstance(getattr(block, n, None), torch.nn.Conv2d) and tuple(getattr(block, n).kernel_size) == (3, 3) for n in ("conv1", "conv2")) \
+        and hasattr(block, "norm1") and hasattr(block, "norm2") and hasattr(block, "downsample")
+
+
+def _check_norm(m, name):
+    if not isinstance(m, torch.nn.InstanceNorm2d):
+        raise RuntimeError(f"residual_block: {name} must be an InstanceNorm2d (norm_fn \"instance\"), not {type(m).__name__}")
+    if not _plain_instance_norm(m):
+        raise RuntimeError(f"residual_block: {name} must be an InstanceNorm2d without affine parameters or running statistics")
+    if abs(float(m.eps) - 1e-5) > 1e-12:
+        raise RuntimeError(f"residual_block: {name}'s eps must be 1e-5, not {m.eps}")
+
+
+def check_block(block):
+    """Raises, naming what it refuses, unless `block` has the reference's residual shape; returns its stride."""
+    if not is_residual_shaped(block):
+        raise RuntimeError("residual_block: the block must have conv1, conv2 (3 x 3 convolutions), norm1, norm2 and downsample")
+    conv1, conv2 = block.conv1, block.conv2
+    if not _conv_is(conv1, 3, 1, ((1, 1), (2, 2))):
+        raise RuntimeError("residual_block: conv1 must be 3 x 3 with padding 1 (zeros), stride 1 or 2, a bias, no dilation and one group")
+    if not _conv_is(conv2, 3, 1, ((1, 1),)):
+        raise RuntimeError("residual_block: conv2 must be 3 x 3 with padding 1 (zeros), stride 1, a bias, no dilation and one group")
+    stride, c_in, c_out = conv1.stride[0], conv1.in_channels, conv1.out_channels
+    if c_in not in BLOCK_CHANNELS or c_out not in BLOCK_CHANNELS or conv2.in_channels != c_out or conv2.out_channels != c_out:
+        raise RuntimeError(f"residual_block: channel counts must be 64, 96 or 128 and conv2 square, not {c_in} -> {c_out} -> {conv2.out_channels}")
+    _check_norm(block.norm1, "norm1")
+    _check_norm(block.norm2, "norm2")
+    down = block.downsample
+    if stride == 1:
+        if down is not None:
+            raise RuntimeError("residual_block: a stride-1 block must have downsample None")
+        if c_in != c_out:
+            raise RuntimeError(f"residual_block: a stride-1 block must keep its channel count, not {c_in} -> {c_out}")
+    else:
+        if down is None or not isinstance(down, torch.nn.Sequential) or len(down) != 2:
+            raise RuntimeError("residual_block: a stride-2 block's downsample must be a Sequential of a convolution and a norm")
+        if not _conv_is(down[0], 1, 0, ((2, 2),)) or down[0].in_channels != c_in or down[0].out_channels != c_out:
+            raise RuntimeError(f"residual_block: downsample[0] must be 1 x 1 with stride 2, no padding and a bias, from {c_in} to {c_out} channels")
+        _check_norm(down[1], "downsample[1]")
+    return stride
+
+
+_packed_blocks = weakref.WeakKeyDictionary()  # block -> (key, the six tensors)
+
+
+def packed_block(block):
+    """(w1, b1, w2, b2, wd, bd) of a residual block (wd, bd None at stride 1), redone when any tensor is replaced or written to."""
+    stride = check_block(block)
+    convs = [block.conv1, block.conv2] + ([block.downsample[0]] if stride == 2 else [])
+    ts = [t for c in convs for t in (c.weight, c.bias)]
+    key = tuple(v for t in ts for v in (t.data_ptr(), t._version)) + (str(block.conv1.weight.device),)
+    hit = _packed_blocks.get(block)
+    if hit is None or hit[0] != key:
+        w1, w2, wd = pack_block_weights(block.conv1.weight, block.conv2.weight, block.downsample[0].weight if stride == 2 else None)
+        bias = lambda c: c.bias.detach().float().contiguous()
+        hit = (key, (w1, bias(block.conv1), w2, bias(block.conv2), wd, bias(block.downsample[0]) if stride == 2 else None))
+        _packed_blocks[block] = hit
+    return hit[1]
+
+
+def residual_block(x, block, out=None):
+    """x [F, c_in, h, w] (any strides, any size >= 1 x 1) through one residual block; `out`, when given, is a contiguous
+    [F, c_out, ho, wo] (a slice of a larger buffer), ho = (h - 1) // stride + 1."""
+    x = _gpu("x", x, "residual_block")
+    w1, b1, w2, b2, wd, bd = packed_block(block)
+    stride, c_in, c_out = (2 if wd is not None else 1), w1.shape[0] * KCHUNK, w1.shape[3]
+    if x.dim() != 4 or x.shape[1] != c_in or min(x.shape) < 1:
+        raise RuntimeError(f"residual_block: `x` must be [F, {c_in}, h, w] and not empty, not {tuple(x.shape)}")
+    if not w1.is_cuda or w1.device != x.device:
+        raise RuntimeError("residual_block: the block must be on the GPU of `x` (there is no CPU fallback in batrack_amd)")
+    F, ho, wo = x.shape[0], (x.shape[2] - 1) // stride + 1, (x.shape[3] - 1) // stride + 1
+    if out is None:
+        out = torch.empty(F, c_out, ho, wo, dtype=torch.float32, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == (F, c_out, ho, wo) and out.device == x.device):
+        raise RuntimeError(f"residual_block: `out` must be a contiguous float32 [F, {c_out}, {ho}, {wo}] on the GPU of `x`")
+    ops = _lib.torch_ops()
+    if ops is not None:
+        ops.res_block(x, w1, b1, w2, b2, wd, bd, stride, out)
+        return out
+    L = _lib.lib()
+    nbytes = L.bt_res_block_workspace_bytes(F, c_out, x.shape[2], x.shape[3], stride)
+    if nbytes == 0:
+        raise RuntimeError("residual_block: " + _lib.ERRORS[_lib.BT_EUNSUPPORTED])
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)           # needs no initialisation
+    blk = _lib.ResBlock(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), wd.data_ptr() if stride == 2 else None,
+                        bd.data_ptr() if stride == 2 else None, c_in, c_out, stride)
+    lx = _level(x)
+    _lib.check(L.bt_res_block(ctypes.byref(lx), ctypes.byref(blk), F, ws.data_ptr(), out.data_ptr(),
+                              torch.cuda.current_stream(x.device).cuda_stream), "bt_res_block")
+    return out
+
+
+def is_residual_layer(layer):
+    return isinstance(layer, torch.nn.Sequential) and len(layer) > 0 and all(is_residual_shaped(b) for b in layer)
+
+
+def _run_layer(x, layer):
+    for block in layer:
+        x = residual_block(x, block)
+    return x
+
+
+def encoder_trunk(x, layer1, layer2, layer3, layer4):
+    """x [F, 64, h, w], the stem's output, through the four layers (each a Sequential of residual blocks): (a, b, c, d)."""
+    outs = []
+    for name, layer in zip(("layer1", "layer2", "layer3", "layer4"), (layer1, layer2, layer3, layer4)):
+        if not is_residual_layer(layer):
+            raise RuntimeError(f"encoder_trunk: {name} must be a Sequential of residual blocks")
+        x = _run_layer(x, layer)
+        outs.append(x)
+    return tuple(outs)
+
+
 def forward(self, x):
     if getattr(self, "shallow", False):
         raise RuntimeError("encoder.forward: the shallow encoder (three levels, a 1 x 1 conv2) is not supported")
@@ -134,11 +289,12 @@ def forward(self, x):
     stride = int(self.stride)
     with torch.no_grad():
         x = self.relu1(self.norm1(self.conv1(x)))
-        a = self.layer1(x)
-        b = self.layer2(a)
-        c = self.layer3(b)
-        d = self.layer4(c)
-        return encoder_head(a, b, c, d, self.conv2, self.conv3, (H // stride, W // stride))
+        maps = []
+        for name in ("layer1", "layer2", "layer3", "layer4"):
+            layer = getattr(self, name)
+            x = _run_layer(x, layer) if name in DEVICE_LAYERS and is_residual_layer(layer) else layer(x)
+            maps.append(x)
+        return encoder_head(*maps, self.conv2, self.conv3, (H // stride, W // stride))
 
 
 def install(module=None):

@@ -1,8 +1,11 @@
-/* batrack_encoder.h — C ABI of the feature encoder's head (the reference's main/frontend/core/cotracker/blocks.py:241-273,
+/* batrack_encoder.h — C ABI of the feature encoder: its head (bt_encoder_head, below) and one residual block of its trunk
+ * layer1..4 (bt_res_block, specified before its declaration).  The stem (conv1 7 x 7, norm1, relu1) is not here.
+ *
+ * The head (the reference's main/frontend/core/cotracker/blocks.py:241-273,
  * the last third of `BasicEncoder.forward` with norm_fn = "instance" and shallow = False): the four pyramid levels resized
  * to the output map, their concatenation convolved 3 x 3 from 416 to 256 channels, the instance normalisation, the ReLU and
  * the 1 x 1 convolution to 128 channels.  Neither the resized copies nor the concatenation is ever in memory: the
- * convolution samples the four small maps while it stages its input.  conv1, norm1 and layer1..4 are not here.
+ * convolution samples the four small maps while it stages its input.
  *
  * Inference only, float32.  The levels a, b, c, d have BT_ENC_CA .. BT_ENC_CD = 64, 96, 128, 128 channels; the virtual
  * concatenation has BT_ENC_CIN = 416 in that order, conv2 gives BT_ENC_CMID = 256 and conv3 BT_ENC_COUT = 128.
@@ -83,6 +86,52 @@ size_t bt_encoder_head_workspace_bytes(int64_t F, int64_t h, int64_t w);
 int bt_encoder_head(const bt_encoder_level *a, const bt_encoder_level *b, const bt_encoder_level *c, const bt_encoder_level *d,
                     const float *w2_packed, const float *bias2, int64_t c_mid, const float *w3_packed, const float *bias3,
                     int64_t c_out, int64_t F, int64_t h, int64_t w, void *workspace, float *out, void *stream);
+
+/* bt_res_block — one `ResidualBlock` (blocks.py:16-75, norm_fn = "instance") of layer1..4.  Inference only, float32.
+ * c_in, c_out in {64, 96, 128}; stride 1 (c_in == c_out, no shortcut convolution) or 2.  x is a strided view [F, c_in, h, w]
+ * read in place; ho = (h - 1) / stride + 1, wo likewise; out is a contiguous [F, c_out, ho, wo].
+ *
+ *   raw1 = conv1(x) + b1:   3 x 3, zero padding 1, stride `stride`: output (y, x) has its centre tap at input
+ *     (stride * y, stride * x).  Summed on v_mfma_f32_16x16x4_f32 in k_head_conv's order: chunks of 8 input channels ascending,
+ *     then tap 3 ky + kx, then group of four channels; the fma chain is added into the total and starts again every two
+ *     chunks (144 products); the bias is added last.
+ *   rawd = downsample[0](x) + bd (stride 2 only):   1 x 1, stride 2, no padding: ONE fma chain over the c_in products in
+ *     channel order, the bias last.
+ *   statistics of raw1 (and rawd), per (frame, channel) over the n = ho * wo pixels: as the head's (float64 sum and sum of
+ *     squares of the stored float32 values, one partial per 16 x 8 tile, added in tile order; no floating-point atomics);
+ *     mean = sum / n; var = max(sumsq / n - mean^2, 0); rstd = 1 / sqrt(var + 1e-5) in float64, stored as floats m, r.
+ *   raw2 = conv2(z1) + b2, z1 = max(fl(fl(raw1 - m1) * r1), 0):   3 x 3, stride 1, zero padding of z1 (NOT of raw1): a tap
+ *     outside the map contributes 0.  z1 is never in memory.  The same order of sums; then raw2's statistics m2, r2.
+ *   out = max(fl(s + max(fl(fl(raw2 - m2) * r2), 0)), 0),   s = x (stride 1) or fl(fl(rawd - md) * rd) (stride 2: norm3, no ReLU).
+ *   A constant channel has an exact mean, so its normalised values are exactly 0.
+ *
+ * Packed weights, all 16-byte aligned: w1[c / 8][3 ky + kx][c % 8][m] = conv1.weight[m][c][ky][kx], [c_in / 8][9][8][c_out];
+ * w2 likewise from conv2, [c_out / 8][9][8][c_out]; wd[c][m] = downsample[0].weight[m][c][0][0], [c_in][c_out]; wd and bd are
+ * NULL exactly when stride is 1.
+ *
+ * Five launches (convolution, statistics, convolution, statistics, join), no host read.  The order of every sum is fixed:
+ * a call repeats bit for bit, and frame f of F frames has the bits of that frame alone.
+ *
+ * workspace: bt_res_block_workspace_bytes(F, c_out, h, w, stride) bytes (0 when refused), 16-byte aligned: raw1, rawd, raw2,
+ * the tiles' partials and the statistics.  Every byte that is read is written first: it needs NO initialisation.
+ * `x` and `blk` are read on the HOST during the call; every pointer inside them is a DEVICE pointer.
+ * Returns
+ *   BT_EINVAL        a null pointer (x, x->data, blk, w1, b1, w2, b2, workspace, out); F, h, w, a channel count or `stride`
+ *                    below 1; a negative stride of the view; w1, w2, wd or the workspace not 16-byte aligned; wd or bd present
+ *                    when stride is 1, or absent when it is 2;
+ *   BT_EUNSUPPORTED  c_in or c_out outside {64, 96, 128}; x->C != c_in; a stride above 2; stride 1 with c_in != c_out;
+ *                    F above 65535; a size, a stride or an element offset of the view, or an element count (of x, or
+ *                    maps * F * c_out * ho * wo with 2 maps at stride 1 and 3 at stride 2) above 2^31 - 1;
+ *   BT_OK            otherwise;   BT_EHIP if a launch fails.
+ * Every refusal happens before any HIP call. */
+struct bt_res_block {            /* a tag only: the name without `struct` is the function's */
+    const float *w1, *b1, *w2, *b2, *wd, *bd;
+    int64_t c_in, c_out, stride;
+};
+
+size_t bt_res_block_workspace_bytes(int64_t F, int64_t c_out, int64_t h_in, int64_t w_in, int64_t stride);
+
+int bt_res_block(const bt_encoder_level *x, const struct bt_res_block *blk, int64_t F, void *workspace, float *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,18 @@ output, the largest difference between the two results and each one's error agai
 time of k_head_conv alone and its TFLOP/s (2 x 416 x 9 x 256 FLOP a pixel) against the 155 TFLOP/s float32 MFMA rate.
 
     python tools/gpu_encoder_bench.py [--reps 30] [--out profiles/r22_encoder_head.txt]
+
+--trunk measures the encoder's trunk instead (bt_res_block through encoder.residual_block / encoder_trunk)
+-> profiles/r26_encoder_trunk.txt: layer1..4 from a 64 x 192 x 256 input, 12 frames and 6, each layer and the whole trunk
+beside the same nn.Sequential layers run by torch on the same GPU (what `forward` executes for a layer that is not in
+encoder.DEVICE_LAYERS), alternating, device time between two events; the peak memory a call adds; frame 0 of every level
+against the statements in float64; `encoder.forward` on a 384 x 512 image with DEVICE_LAYERS as committed and empty (every
+layer called as it is); and the list DEVICE_LAYERS must be by the rule "not above torch's time at both shapes".  The kernel
+rows come from one rocprofv3 run of its own:
+
+    python tools/gpu_encoder_bench.py --trunk [--reps 20] [--out profiles/r26_encoder_trunk.txt]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/gpu_encoder_bench.py --trunk-trace        (a run of its own)
+    python tools/gpu_encoder_bench.py --trunk-trace-db DIR/.../*_results.db [--out ...]                  (appends the kernel rows)
 """
 import argparse
 import os
@@ -81,14 +93,163 @@ def kernel_times(fn, reps):
         print(f"(profiler unavailable: {e})")
         return {}
 
+# ------------------------------------------------------------------------------------------------------------- the trunk
+TRUNK_SIZE, TRUNK_IMAGE = (192, 256), (384, 512)
+TRACE_CALLS, TRACE_SKIP = 8, 3
+LAUNCHES = ("conv1", "stats1", "conv2", "stats2", "join")       # bt_res_block's five launches, in order
+
+
+def trunk_setup(F):
+    import encoder_trunk_util as T
+    t = {k: torch.as_tensor(v, dtype=torch.float32, device=DEV) for k, v in T.make_inputs(200 + F, 1, (2, 2)).items() if "." in k and not k.startswith("in.")}
+    layers = T.make_layers(t)
+    x = torch.rand(F, 64, *TRUNK_SIZE, generator=torch.Generator(device=DEV).manual_seed(300 + F), device=DEV) * 2.0
+    return T, t, layers, x
+
+
+def block_flops(F):
+    """Per block: (conv1, shortcut, conv2) FLOP of F frames from the 192 x 256 input."""
+    import encoder_trunk_util as T
+    sizes, out = T.level_sizes(TRUNK_SIZE), []
+    for layer, i, c_in, c_out, stride in T.BLOCKS:
+        ho, wo = sizes[T.LAYERS.index(layer)]
+        n = F * ho * wo
+        out.append((2 * 9 * c_in * c_out * n, 2 * c_in * c_out * n if stride == 2 else 0, 2 * 9 * c_out * c_out * n))
+    return out
+
+
+def trunk_trace():
+    for __, F in SHAPES:
+        T, t, layers, x = trunk_setup(F)
+        for r in range(TRACE_CALLS):
+            encoder.encoder_trunk(x, *layers)
+        torch.cuda.synchronize()
+
+
+def trunk_trace_db(args):
+    import sqlite3
+    import encoder_trunk_util as T
+    cur = sqlite3.connect(args.trunk_trace_db).cursor()
+    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_res_%' order by start").fetchall()
+    per_call = len(T.BLOCKS) * len(LAUNCHES)
+    with open(args.out, "a") as fh:
+        fh.write(f"kernel time, rocprofv3 --kernel-trace --stats in a run of its own ({TRACE_CALLS} trunks per shape, the first {TRACE_SKIP} left out): "
+                 f"median us; convolutions with their TFLOP/s (the shortcut's products counted with conv1) and share of the {MFMA_F32_TFLOPS:.0f} TFLOP/s "
+                 "float32 MFMA rate; LDS as the trace reports it (registers: -Rpass-analysis=kernel-resource-usage, DESIGN.md f-13)\n")
+        if len(rows) != len(SHAPES) * TRACE_CALLS * per_call:
+            fh.write(f"  ({len(rows)} k_res_* launches in the trace, {len(SHAPES) * TRACE_CALLS * per_call} expected: rows NOT attributed)\n")
+            return
+        for k, (name, F) in enumerate(SHAPES):
+            part = rows[k * TRACE_CALLS * per_call:(k + 1) * TRACE_CALLS * per_call]
+            flops, total, mfma = block_flops(F), 0.0, 0.0
+            fh.write(f"  {name}:\n")
+            for b, (layer, i, c_in, c_out, stride) in enumerate(T.BLOCKS):
+                cells = []
+                for j, launch in enumerate(LAUNCHES):
+                    sel = [part[c * per_call + b * len(LAUNCHES) + j] for c in range(TRACE_SKIP, TRACE_CALLS)]
+                    us = float(np.median([r[1] for r in sel])) / 1e3
+                    total += us
+                    cell = f"{launch} {us:.0f}"
+                    if launch in ("conv1", "conv2"):
+                        fl = flops[b][0] + flops[b][1] if launch == "conv1" else flops[b][2]
+                        tf = fl / (us * 1e-6) / 1e12
+                        mfma += us
+                        cell += f" ({tf:.1f} TFLOP/s, {100 * tf / MFMA_F32_TFLOPS:.0f} %; {sel[0][4]} B LDS)"
+                    cells.append(cell)
+                fh.write(f"    {layer}[{i}] {c_in} -> {c_out} stride {stride}: " + ", ".join(cells) + "\n")
+            fl = sum(sum(v) for v in flops)
+            fh.write(f"    sum of the 40 launches {total:.0f} us, of the 16 convolutions {mfma:.0f} us = {fl / (mfma * 1e-6) / 1e12:.1f} TFLOP/s over {fl / 1e9:.1f} GFLOP\n")
+
+
+def trunk_main(args):
+    lines = []
+
+    def out(s):
+        print(s, flush=True)
+        lines.append(s)
+    q = lambda v: "{:.0f} [{:.0f} .. {:.0f}]".format(*np.quantile(v, [0.5, 0.1, 0.9]))
+    mb = lambda b: f"{b / 1e6:.1f} MB"
+    out(f"encoder trunk on {torch.cuda.get_device_name(0)}: layer1..4 on bt_res_block (new) against the same nn.Sequential layers run by torch (torch)")
+    out(f"64 x {TRUNK_SIZE[0]} x {TRUNK_SIZE[1]} input; the two alternating, {args.reps} calls each after warm-up; device time between two events, us median [10 % .. 90 %]")
+    keep = {}
+    for name, F in SHAPES:
+        T, t, layers, x = trunk_setup(F)
+        with torch.no_grad():
+            inputs = [x]
+            for layer in layers[:3]:
+                inputs.append(layer(inputs[-1]))
+            pairs = [(n, (lambda l=l, v=v: encoder._run_layer(v, l)), (lambda l=l, v=v: l(v))) for n, l, v in zip(T.LAYERS, layers, inputs)]
+
+            def torch_trunk():
+                v, outs = x, []
+                for l in layers:
+                    v = l(v)
+                    outs.append(v)
+                return outs
+            pairs.append(("trunk", lambda: encoder.encoder_trunk(x, *layers), torch_trunk))
+            got, want = encoder.encoder_trunk(x, *layers), torch_trunk()
+            want64 = T.trunk(x[:1].double(), {k: v.double() for k, v in t.items()})               # frame 0: frames are independent
+            errs = [(float((g[:1].double() - w64).abs().max()), float((w[:1].double() - w64).abs().max())) for g, w, w64 in zip(got, want, want64)]
+            del want64, got, want
+            out(f"{name}: frame 0 of a, b, c, d against the statements in float64, max |new - f64| / max |torch - f64|: "
+                + ", ".join(f"{a:.2e} / {b:.2e}" for a, b in errs))
+            for n, new, ref in pairs:
+                d = {"new": [], "torch": []}
+                for r in range(2):                                   # alternate the two formulations
+                    for f, fn in (("new", new), ("torch", ref)):
+                        d[f].append(timed(fn, args.reps // 2))
+                d = {f: np.concatenate(v) for f, v in d.items()}
+                mem = {f: added_memory(fn) for f, fn in (("new", new), ("torch", ref))}
+                keep[n, F] = (float(np.median(d["new"])), float(np.median(d["torch"])))
+                fl = sum(sum(v) for v, blk in zip(block_flops(F), T.BLOCKS) if n in ("trunk", blk[0]))
+                out(f"  {n}: new {q(d['new'])} us, torch {q(d['torch'])} us = {np.median(d['torch']) / np.median(d['new']):.2f}x; "
+                    f"{fl / 1e9:.1f} GFLOP over the call's device time: new {fl / np.median(d['new']) / 1e6:.1f}, torch {fl / np.median(d['torch']) / 1e6:.1f} TFLOP/s; "
+                    f"peak memory a call adds, its output included: new {mb(mem['new'])}, torch {mb(mem['torch'])}")
+            del pairs, inputs
+            m = T.TrunkEncoder().to(DEV)
+            img = torch.rand(F, 3, *TRUNK_IMAGE, generator=torch.Generator(device=DEV).manual_seed(400 + F), device=DEV) * 2 - 1
+            committed = encoder.DEVICE_LAYERS
+
+            def forward_with(which):
+                encoder.DEVICE_LAYERS = which
+                try:
+                    return encoder.forward(m, img)
+                finally:
+                    encoder.DEVICE_LAYERS = committed
+            d = {"committed": [], "none": []}
+            for r in range(2):
+                for f, which in (("committed", committed), ("none", ())):
+                    d[f].append(timed(lambda: forward_with(which), args.reps // 2))
+            d = {f: np.concatenate(v) for f, v in d.items()}
+            out(f"  encoder.forward on a {TRUNK_IMAGE[0]} x {TRUNK_IMAGE[1]} image: DEVICE_LAYERS = {committed} {q(d['committed'])} us; "
+                f"empty (every layer called as it is, the parent's forward) {q(d['none'])} us = {np.median(d['none']) / np.median(d['committed']):.2f}x")
+            del m, img
+        torch.cuda.empty_cache()
+    rule = tuple(n for n in ("layer1", "layer2", "layer3", "layer4") if all(keep[n, F][0] <= keep[n, F][1] for __, F in SHAPES))
+    out(f"DEVICE_LAYERS by the rule (a layer's device time not above torch's at both shapes): {rule}; committed: {encoder.DEVICE_LAYERS}")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r22_encoder_head.txt"))
+    ap.add_argument("--out")
+    ap.add_argument("--trunk", action="store_true", help="measure the trunk (layer1..4) instead of the head")
+    ap.add_argument("--trunk-trace", action="store_true", help=f"{TRACE_CALLS} trunks per shape, nothing written: for rocprofv3")
+    ap.add_argument("--trunk-trace-db", help="append the trunk kernels' rows from a rocprofv3 results database, then exit")
     args = ap.parse_args()
+    trunk = args.trunk or args.trunk_trace or args.trunk_trace_db
+    args.out = args.out or os.path.join(ROOT, "profiles", "r26_encoder_trunk.txt" if trunk else "r22_encoder_head.txt")
+    if args.trunk_trace_db:
+        return trunk_trace_db(args)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: nothing is measured without one")
+    if args.trunk_trace:
+        return trunk_trace()
+    if args.trunk:
+        return trunk_main(args)
     lines = []
 
     def out(s):
