@@ -1,21 +1,16 @@
 // encoder_trunk.hip — one residual block of the feature encoder's layer1..4 (include/batrack_encoder.h holds the
 // specification): k_res_conv, k_res_stats, k_res_join.
 //
-// k_res_conv<NORM, S, SHORT, NT> is a 3 x 3 convolution with zero padding 1 and stride S from c_in to 16 NT channels, an
-// implicit GEMM on v_mfma_f32_16x16x4_f32 with k_head_conv's tile (csrc/conv_tile.hpp): rows are output pixels, columns
-// output channels, K = 9 taps x c_in.
-//   tile     a workgroup (4 waves) owns a 16 x 8 tile of OUTPUT pixels of one frame and all 16 NT <= 128 columns.
-//   K-chunk  8 input channels at a time: their halo tile (18 x 10 input pixels at stride 1, 33 x 17 at stride 2) is staged in
-//            LDS beside their 9 x 8 x 16 NT weights.  NORM: a halo element inside the input map is
-//            max(fl(fl(v - mean) * rstd), 0) with the (frame, channel)'s statistics, one outside is 0: the padding is of the
-//            normalised, rectified map, which is never in memory.  Otherwise v, or 0 outside; the input is a strided view.
-//            At stride 1 the chunk's global loads go into registers while the chunk before it is multiplied and reach LDS
-//            (normalised) when that one is done; at stride 2, with three accumulator sets, they are staged directly, six
-//            unconditional loads at a time.
-//   stride 2 a halo row is kept as its 17 even columns, then its 16 odd ones: output x reads column 2x + kx, which is
-//            element x of the even part (kx = 0), x of the odd part (kx = 1) or x + 1 of the even part (kx = 2): the A operand
-//            is one ds_read_b32 at unit lane stride, as at stride 1.  (Read from the code, not measured against the
-//            interleaved row: the split costs the staging one select.)
+// k_res_conv<NORM, S, SHORT, NT> is a 3 x 3 convolution with zero padding 1 and stride S from c_in to 16 NT <= 128 channels, an
+// implicit GEMM on v_mfma_f32_16x16x4_f32 with the tile of csrc/conv_tile.hpp (all 16 NT columns), K = 9 taps x c_in.
+//   K-chunk  8 input channels at a time: their halo tile (18 x 10 input pixels at stride 1, 33 x 17 at stride 2, the even
+//            columns of a row first) is staged in LDS beside their 9 x 8 x 16 NT weights.  NORM: a halo element inside the
+//            input map is max(fl(fl(v - mean) * rstd), 0) with the (frame, channel)'s statistics, one outside is 0: the
+//            padding is of the normalised, rectified map, which is never in memory.  Otherwise v, or 0 outside; the input is
+//            a strided view.  At stride 1 the chunk's global loads go into registers while the chunk before it is multiplied
+//            and reach LDS (normalised) when that one is done; at stride 2, with three accumulator sets, they are staged
+//            directly, six unconditional loads at a time.  (The even/odd split is read from the code, not measured against
+//            the interleaved row: it costs the staging one select.)
 //   order    chunk ascending, tap, group of four channels; every CT_FLUSH = 2 chunks (144 products) the accumulators are
 //            added into a second set and start again from zero; the bias last.  k_head_conv's order.
 //   SHORT    the block's 1 x 1 stride-2 shortcut reads exactly the centre tap's staged pixel: a second GEMM from the same
@@ -44,13 +39,6 @@ struct ResView {                 // a strided [F, C, h, w] view, by value in the
     int h, w;
 };
 
-template <int S> struct ResGeom {
-    static constexpr int HW = S * (CT_TW - 1) + 3, HH = S * (CT_TH - 1) + 3, HALO = HW * HH;    // 18 x 10, 33 x 17
-    static constexpr int EVEN = (HW + 1) / 2;                                                  // stride 2: the even columns first
-    static constexpr int PL = ((HALO + 15) / 32) * 32 + 16;                                    // plane stride, 16 mod 32
-    static_assert(PL >= HALO && PL % 32 == 16, "LDS plane stride");
-};
-
 constexpr int RC_MAXC = 128;
 
 // -------------------------------------------------------------------------------------------------------------- k_res_conv
@@ -60,9 +48,8 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
                                                          const float *__restrict__ wd, const float *__restrict__ bd, int ho, int wo, int tiles_x,
                                                          float *__restrict__ raw, double *__restrict__ part, float *__restrict__ rawd,
                                                          double *__restrict__ partd) {
-    using G = ResGeom<S>;
-    constexpr int COLS = 16 * NT, WLD = COLS + 16, HW = G::HW, HALO = G::HALO, PL = G::PL;
-    static_assert(WLD % 32 == 16, "LDS weight row stride");
+    using G = ConvGeom<S>;
+    constexpr int COLS = 16 * NT, WLD = conv_wld(COLS), HW = G::HW, HALO = G::HALO, PL = G::PL;
     static_assert(9 * CT_KC * WLD * sizeof(float) >= (CT_THREADS / 64) * COLS * 2 * sizeof(double), "the statistics reuse the weights' LDS");
     static_assert(!SHORT || S == 2, "the shortcut belongs to the stride-2 block");
     __shared__ __attribute__((aligned(16))) float w_l[9 * CT_KC * WLD];          // [tap][channel of the chunk][WLD]
@@ -79,37 +66,30 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
         for (int c = tid; c < c_in; c += CT_THREADS) { mean_l[c] = mean[(long long)f * c_in + c]; rstd_l[c] = rstd[(long long)f * c_in + c]; }
     }
 
-    ct_f32x4 acc[2][NT], tot[2][NT], accd[SHORT ? 2 : 1][SHORT ? NT : 1];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int ct = 0; ct < NT; ++ct) acc[r][ct] = tot[r][ct] = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if constexpr (SHORT) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct) accd[r][ct] = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    f32x4 acc[2][NT], tot[2][NT], accd[2][SHORT ? NT : 1];
+    tile_zero<NT>(acc);
+    tile_zero<NT>(tot);
+    tile_zero<SHORT ? NT : 1>(accd);
 
     // Staging is split in two: the global loads of a chunk go into registers (`fetch`) while the chunk before it is
     // multiplied, and reach LDS (`stage`, which normalises) when that one is done.  The order of the sums does not change.
     constexpr int W4 = 9 * CT_KC * (COLS / 4), D4 = CT_KC * (COLS / 4), HE = CT_KC * HALO;
     constexpr int WN = (W4 + CT_THREADS - 1) / CT_THREADS, HN = (HE + CT_THREADS - 1) / CT_THREADS;
     static_assert(D4 <= CT_THREADS && HN <= 32, "one shortcut float4 a thread; the inside mask is 32 bits");
-    ct_f32x4 wreg[WN], dreg = ct_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 wreg[WN], dreg = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     float hreg[HN];
     unsigned inside = 0;                                         // bit k: hreg[k] is an element of the input map
     const float *xf = X.p + (long long)f * X.sf;
     const int chunks = c_in / CT_KC;
     auto fetch = [&](int chunk) __attribute__((always_inline)) {
-        const ct_f32x4 *wsrc = reinterpret_cast<const ct_f32x4 *>(wp + (size_t)chunk * 9 * CT_KC * COLS);
+        const f32x4 *wsrc = reinterpret_cast<const f32x4 *>(wp + (size_t)chunk * 9 * CT_KC * COLS);
 #pragma unroll
         for (int k = 0; k < WN; ++k) {
             const int i = tid + k * CT_THREADS;
             if (i < W4) wreg[k] = wsrc[i];
         }
         if constexpr (SHORT) {
-            if (tid < D4) dreg = reinterpret_cast<const ct_f32x4 *>(wd + (size_t)chunk * CT_KC * COLS)[tid];
+            if (tid < D4) dreg = reinterpret_cast<const f32x4 *>(wd + (size_t)chunk * CT_KC * COLS)[tid];
         }
         const float *src = xf + (long long)chunk * CT_KC * X.sc;
         inside = 0;
@@ -131,11 +111,11 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
         for (int k = 0; k < WN; ++k) {
             const int i = tid + k * CT_THREADS;
             const int row = i / (COLS / 4), c4 = i - row * (COLS / 4);
-            if (i < W4) *reinterpret_cast<ct_f32x4 *>(w_l + row * WLD + c4 * 4) = wreg[k];
+            if (i < W4) *reinterpret_cast<f32x4 *>(w_l + row * WLD + c4 * 4) = wreg[k];
         }
         if constexpr (SHORT) {
             const int row = tid / (COLS / 4), c4 = tid - row * (COLS / 4);
-            if (tid < D4) *reinterpret_cast<ct_f32x4 *>(wd_l + row * WLD + c4 * 4) = dreg;
+            if (tid < D4) *reinterpret_cast<f32x4 *>(wd_l + row * WLD + c4 * 4) = dreg;
         }
 #pragma unroll
         for (int k = 0; k < HN; ++k) {
@@ -154,16 +134,8 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
         }
     };
     auto stage_direct = [&](int chunk) __attribute__((always_inline)) {      // the same elements to the same places, not through registers
-        const float4 *wsrc = reinterpret_cast<const float4 *>(wp + (size_t)chunk * 9 * CT_KC * COLS);
-#pragma unroll 3
-        for (int i = tid; i < W4; i += CT_THREADS) {
-            const int row = i / (COLS / 4), c4 = i - row * (COLS / 4);
-            *reinterpret_cast<float4 *>(w_l + row * WLD + c4 * 4) = wsrc[i];
-        }
-        if constexpr (SHORT) {
-            const int row = tid / (COLS / 4), c4 = tid - row * (COLS / 4);
-            if (tid < D4) *reinterpret_cast<float4 *>(wd_l + row * WLD + c4 * 4) = reinterpret_cast<const float4 *>(wd + (size_t)chunk * CT_KC * COLS)[tid];
-        }
+        tile_stage_rows<9 * CT_KC, COLS, 3>(w_l, wp + (size_t)chunk * 9 * CT_KC * COLS, COLS);
+        if constexpr (SHORT) tile_stage_rows<CT_KC, COLS>(wd_l, wd + (size_t)chunk * CT_KC * COLS, COLS);
         const float *src = xf + (long long)chunk * CT_KC * X.sc;
         // six loads at a time, every one unconditional (the address clamped into the map, the value dropped outside): a load
         // behind a branch that is used in its own trip waits for memory every trip
@@ -207,39 +179,20 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
         if constexpr (AHEAD) {
             if (chunk + 1 < chunks) fetch(chunk + 1);            // in flight while this chunk is multiplied
         }
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            const int coff = S == 1 ? kx : (kx == 1 ? G::EVEN : (kx >> 1));
-#pragma unroll
-            for (int s = 0; s < CT_KC / 4; ++s) {
-                const float *ap = in_l + (4 * s + q) * PL + (S * 2 * wave + ky) * HW + l16 + coff;
-                const float a0 = ap[0], a1 = ap[S * HW];
-                const float *wr = w_l + (tap * CT_KC + 4 * s + q) * WLD + l16;
-#pragma unroll
-                for (int ct = 0; ct < NT; ++ct) {
-                    const float b = wr[ct * 16];
-                    acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][ct], 0, 0, 0);
-                    acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][ct], 0, 0, 0);
-                }
-                if constexpr (SHORT) if (tap == 4) {                         // the centre tap's pixel is the shortcut's
-                    const float *dr = wd_l + (4 * s + q) * WLD + l16;
-#pragma unroll
-                    for (int ct = 0; ct < NT; ++ct) {
-                        const float b = dr[ct * 16];
-                        accd[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, accd[0][ct], 0, 0, 0);
-                        accd[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, accd[1][ct], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        if constexpr (SHORT)                                     // the centre tap's pixel is the shortcut's
+            tile_taps<S, NT>(in_l, w_l, acc, [&](int s, float a0, float a1) __attribute__((always_inline)) { tile_group<NT>(a0, a1, wd_l + (4 * s + q) * WLD + l16, accd); });
+        else
+            tile_taps<S, NT>(in_l, w_l, acc);
         if (chunk % CT_FLUSH == CT_FLUSH - 1) tile_flush<NT>(tot, acc);      // a block is complete: one rounded add into the total
     }
     __syncthreads();                                             // the last chunk's weights are read: their LDS takes the statistics
     double *red = reinterpret_cast<double *>(w_l);
     const long long tile = (long long)f * gridDim.x + blockIdx.x;
-    tile_store_stats<NT>(tot, bias, raw + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, part + tile * COLS * 2);
-    if constexpr (SHORT) tile_store_stats<NT>(accd, bd, rawd + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, partd + tile * COLS * 2);
+    tile_store_stats<NT, true>(tot, bias, raw + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, part + tile * COLS * 2);
+    if constexpr (SHORT) {
+        __syncthreads();                                         // `red` is read
+        tile_store_stats<NT, true>(accd, bd, rawd + (long long)f * COLS * hwo, hwo, ho, wo, ty0, tx0, red, partd + tile * COLS * 2);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------- k_res_stats
@@ -305,11 +258,7 @@ __global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2
     else out[base] = y[0];
 }
 
-constexpr long long kResI31 = 2147483647LL;
-
 static bool res_channels(long long c) { return c == 64 || c == 96 || c == 128; }
-
-static long long res_tiles(long long ho, long long wo) { return ((ho + CT_TH - 1) / CT_TH) * ((wo + CT_TW - 1) / CT_TW); }
 
 struct ResLayout {               // byte offsets into the workspace; maps = 2 (raw1, raw2) or 3 (raw1, rawd, raw2)
     long long ho, wo, n, tiles, maps;
@@ -318,10 +267,10 @@ struct ResLayout {               // byte offsets into the workspace; maps = 2 (r
 
 // false when the sizes are refused
 static bool res_layout(long long F, long long c_out, long long h, long long w, long long stride, ResLayout *L) {
-    if (F < 1 || h < 1 || w < 1 || F > kResI31 || h > kResI31 || w > kResI31 || !res_channels(c_out) || (stride != 1 && stride != 2)) return false;
-    L->ho = (h - 1) / stride + 1; L->wo = (w - 1) / stride + 1; L->n = L->ho * L->wo; L->tiles = res_tiles(L->ho, L->wo);
+    if (F < 1 || h < 1 || w < 1 || F > kI31 || h > kI31 || w > kI31 || !res_channels(c_out) || (stride != 1 && stride != 2)) return false;
+    L->ho = (h - 1) / stride + 1; L->wo = (w - 1) / stride + 1; L->n = L->ho * L->wo; L->tiles = conv_tiles(L->ho, L->wo);
     L->maps = stride == 1 ? 2 : 3;
-    if ((__int128)L->maps * F * c_out * L->ho * L->wo > kResI31 || L->tiles > kResI31) return false;
+    if ((__int128)L->maps * F * c_out * L->ho * L->wo > kI31 || L->tiles > kI31) return false;
     L->part = ((size_t)L->maps * F * c_out * L->n * sizeof(float) + 15) & ~(size_t)15;
     L->stat = L->part + (size_t)L->maps * F * L->tiles * c_out * 2 * sizeof(double);
     L->bytes = L->stat + (size_t)L->maps * F * c_out * 2 * sizeof(float);
@@ -359,10 +308,7 @@ extern "C" int bt_res_block(const bt_encoder_level *x, const struct bt_res_block
     if (blk->stride == 2 && (!blk->wd || !blk->bd)) return BT_EINVAL;
     const long long c_in = blk->c_in, c_out = blk->c_out, stride = blk->stride;
     if (!res_channels(c_in) || !res_channels(c_out) || x->C != c_in || stride > 2 || (stride == 1 && c_in != c_out) || F > 65535) return BT_EUNSUPPORTED;
-    if (x->h > kResI31 || x->w > kResI31 || x->sf > kResI31 || x->sc > kResI31 || x->sy > kResI31 || x->sx > kResI31) return BT_EUNSUPPORTED;
-    if ((__int128)F * c_in * x->h * x->w > kResI31
-        || (__int128)(F - 1) * x->sf + (__int128)(c_in - 1) * x->sc + (__int128)(x->h - 1) * x->sy + (__int128)(x->w - 1) * x->sx > kResI31)
-        return BT_EUNSUPPORTED;
+    if (!view_fits_i31(F, c_in, x->h, x->w, x->sf, x->sc, x->sy, x->sx)) return BT_EUNSUPPORTED;
     ResLayout L;
     if (!res_layout(F, c_out, x->h, x->w, stride, &L)) return BT_EUNSUPPORTED;
 
@@ -372,7 +318,7 @@ extern "C" int bt_res_block(const bt_encoder_level *x, const struct bt_res_block
     double *part1 = (double *)((char *)workspace + L.part), *partd = stride == 2 ? part1 + slot_p : nullptr, *part2 = part1 + (L.maps - 1) * slot_p;
     float *mean1 = (float *)((char *)workspace + L.stat), *rstd1 = mean1 + L.maps * slot_s;
     float *meand = mean1 + slot_s, *rstdd = rstd1 + slot_s, *mean2 = mean1 + (L.maps - 1) * slot_s, *rstd2 = rstd1 + (L.maps - 1) * slot_s;
-    const int ho = (int)L.ho, wo = (int)L.wo, tiles_x = (int)((L.wo + CT_TW - 1) / CT_TW);
+    const int ho = (int)L.ho, wo = (int)L.wo, tiles_x = (int)conv_tiles_x(L.wo);
     const ResView X{x->data, x->sf, x->sc, x->sy, x->sx, (int)x->h, (int)x->w};
     const ResView Y{raw1, c_out * L.n, L.n, L.wo, 1, ho, wo};
 

@@ -6,19 +6,14 @@
 // pairs and puts the ticket back to zero.  One launch, no atomics on the values, and min / max do not depend on the order.
 // A NaN among the values they select makes both results NaN, as torch's min() and max() do.
 //
-// k_embed_conv is the 3 x 3 convolution 191 -> 128 as an implicit GEMM on v_mfma_f32_16x16x4_f32: rows are output pixels,
-// columns the 128 output channels, K = 9 taps x 192 input channels (191 and a zero weight).
-//   tile     a workgroup (4 waves) owns a 16 x 8 tile of output pixels of one frame and all 128 channels; wave v owns tile
-//            rows 2v and 2v + 1, each a 16-pixel MFMA row block: 2 x 8 accumulators of 4 registers.
+// k_embed_conv is the 3 x 3 convolution 191 -> 128 as an implicit GEMM on v_mfma_f32_16x16x4_f32 with the tile of
+// csrc/conv_tile.hpp (stride 1, all 128 columns): K = 9 taps x 192 input channels (191 and a zero weight).
 //   K-chunk  8 input channels at a time: their 18 x 10 halo tile (zero outside the map) and their 9 x 8 x 128 weights are
-//            staged in LDS, 50288 bytes with the pixels' coordinates — two workgroups share a CU (184 VGPRs allow two waves a SIMD), and while one
+//            staged in LDS, 50288 bytes with the pixels' coordinates — two workgroups share a CU (180 VGPRs allow two waves a SIMD), and while one
 //            stages the other multiplies.  Chunks 0 .. 15 are the encoder's channels, read from memory; chunks 16 .. 23 are the embedding,
 //            COMPUTED into the same halo tile from the pixel's normalised (x, y, z), which is kept in LDS per halo pixel.
-//   operands A: lane l holds pixel l % 16 of the row block and channel l / 16 of the group of four — one ds_read_b32 from the
-//            halo tile at the tap's offset.  B: lane l holds channel l / 16 and output column 16 ct + l % 16.  The halo
-//            plane stride (208) and the weight row stride (144) are 16 mod 32, so that the two channel rows a 32-lane half
-//            reads fall on different banks.  A B fragment feeds both row blocks: 10 LDS reads per 16 MFMAs.
-//   order    chunk, tap, group of four channels: fixed, the same for every pixel of every frame, whatever frame0 and F are.
+//   order    chunk, tap, group of four channels, ONE fma chain, the bias last: fixed, the same for every pixel of every
+//            frame, whatever frame0 and F are.
 // What it leaves on the table is in DESIGN.md.
 #include <hip/hip_runtime.h>
 
@@ -27,20 +22,17 @@
 
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_window.h"
+#include "conv_tile.hpp"
 #include "sample_taps.hpp"
 
 namespace bt {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WD_THREADS = 256, WD_MAX_BLOCKS = 1024, WD_PER_THREAD = 8;
 constexpr size_t WD_WORKSPACE = (size_t)2 * WD_MAX_BLOCKS * sizeof(float) + sizeof(unsigned);
 
-constexpr int EC_THREADS = 256, EC_TW = 16, EC_TH = 8, EC_HW = EC_TW + 2, EC_HH = EC_TH + 2, EC_HALO = EC_HW * EC_HH;
-constexpr int EC_KC = BT_WINDOW_KCHUNK, EC_PL = 208, EC_WLD = 144, EC_CHUNKS = (BT_WINDOW_C + BT_WINDOW_EMB + 1) / EC_KC;
-constexpr int EC_NT = BT_WINDOW_C / 16;
-static_assert(EC_PL >= EC_HALO && EC_PL % 32 == 16 && EC_WLD >= BT_WINDOW_C && EC_WLD % 32 == 16, "LDS strides");
-static_assert(EC_CHUNKS * EC_KC == 192 && EC_TH == 2 * (EC_THREADS / 64), "tiling");
+constexpr int EC_HW = ConvGeom<1>::HW, EC_HALO = ConvGeom<1>::HALO, EC_PL = ConvGeom<1>::PL;
+constexpr int EC_CHUNKS = (BT_WINDOW_C + BT_WINDOW_EMB + 1) / CT_KC, EC_NT = BT_WINDOW_C / 16;
+static_assert(CT_KC == BT_WINDOW_KCHUNK && EC_CHUNKS * CT_KC == 192, "the packed weights' chunks");
 
 constexpr int FS_THREADS = BT_WINDOW_C;
 
@@ -129,22 +121,22 @@ __device__ __forceinline__ float normalise(float v, float lo, float hi) {
     return __fmul_rn(2.0f, __fsub_rn(__fdiv_rn(__fsub_rn(v, lo), __fsub_rn(hi, lo)), 0.5f));
 }
 
-__global__ __launch_bounds__(EC_THREADS) void k_embed_conv(const float *__restrict__ fnet, long long sf, long long sc, long long sy,
+__global__ __launch_bounds__(CT_THREADS) void k_embed_conv(const float *__restrict__ fnet, long long sf, long long sc, long long sy,
                                                           long long sx, const float *__restrict__ dmaps,
                                                           const float *__restrict__ zrange, const float *__restrict__ wp,
                                                           const float *__restrict__ bias, const float *__restrict__ freqs,
                                                           int frame0, int h, int w, int tiles_x, float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float w_l[9 * EC_KC * EC_WLD];       // [tap][channel of the chunk][EC_WLD]
-    __shared__ float in_l[EC_KC * EC_PL];                                         // [channel of the chunk][halo pixel]
+    __shared__ __attribute__((aligned(16))) float w_l[9 * CT_KC * conv_wld(BT_WINDOW_C)];   // [tap][channel of the chunk][144]
+    __shared__ float in_l[CT_KC * EC_PL];                                         // [channel of the chunk][halo pixel]
     __shared__ float p_l[3 * EC_HALO];                                            // normalised x, y, z of the halo pixels
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
-    const int f = blockIdx.y, ty0 = (blockIdx.x / tiles_x) * EC_TH, tx0 = (blockIdx.x % tiles_x) * EC_TW;
+    const int tid = threadIdx.x;
+    const int f = blockIdx.y, ty0 = (blockIdx.x / tiles_x) * CT_TH, tx0 = (blockIdx.x % tiles_x) * CT_TW;
     const long long hw = (long long)h * w;
 
     {
         const float zlo = zrange[0], zhi = zrange[1];
         const float *dm = dmaps + (long long)(frame0 + f) * hw;
-        for (int p = tid; p < EC_HALO; p += EC_THREADS) {
+        for (int p = tid; p < EC_HALO; p += CT_THREADS) {
             const int gy = ty0 + p / EC_HW - 1, gx = tx0 + p % EC_HW - 1;
             const bool inside = gy >= 0 && gy < h && gx >= 0 && gx < w;
             p_l[p] = normalise((float)gx, 0.0f, (float)(w - 1));
@@ -154,25 +146,18 @@ __global__ __launch_bounds__(EC_THREADS) void k_embed_conv(const float *__restri
     }
 
     f32x4 acc[2][EC_NT];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int ct = 0; ct < EC_NT; ++ct) acc[r][ct] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    tile_zero<EC_NT>(acc);
 
     const float *fbase = fnet + (long long)f * sf;
     for (int chunk = 0; chunk < EC_CHUNKS; ++chunk) {
         __syncthreads();                                         // the previous chunk's reads are done (and p_l is written)
-        const float4 *wsrc = reinterpret_cast<const float4 *>(wp + (size_t)chunk * 9 * EC_KC * BT_WINDOW_C);
-        for (int i = tid; i < 9 * EC_KC * (BT_WINDOW_C / 4); i += EC_THREADS) {
-            const int row = i >> 5, c4 = i & 31;
-            *reinterpret_cast<float4 *>(w_l + row * EC_WLD + c4 * 4) = wsrc[i];
-        }
-        for (int idx = tid; idx < EC_KC * EC_HALO; idx += EC_THREADS) {
+        tile_stage_rows<9 * CT_KC, BT_WINDOW_C>(w_l, wp + (size_t)chunk * 9 * CT_KC * BT_WINDOW_C, BT_WINDOW_C);
+        for (int idx = tid; idx < CT_KC * EC_HALO; idx += CT_THREADS) {
             const int chl = idx / EC_HALO, p = idx - chl * EC_HALO;
             const int gy = ty0 + p / EC_HW - 1, gx = tx0 + p % EC_HW - 1;
             float v = 0.0f;                                      // zero padding, for the embedding as for the maps
             if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
-                const int c = chunk * EC_KC + chl;
+                const int c = chunk * CT_KC + chl;
                 if (c < BT_WINDOW_C) v = fbase[c * sc + gy * sy + gx * sx];
                 else {
                     const int e = c - BT_WINDOW_C;               // Embedder_Fourier's order: the input, then per frequency sin(xyz), cos(xyz)
@@ -187,41 +172,9 @@ __global__ __launch_bounds__(EC_THREADS) void k_embed_conv(const float *__restri
             in_l[chl * EC_PL + p] = v;
         }
         __syncthreads();
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-            for (int s = 0; s < EC_KC / 4; ++s) {
-                const float *ap = in_l + (4 * s + q) * EC_PL + (2 * wave + ky) * EC_HW + l16 + kx;
-                const float a0 = ap[0], a1 = ap[EC_HW];
-                const float *wr = w_l + (tap * EC_KC + 4 * s + q) * EC_WLD + l16;
-#pragma unroll
-                for (int ct = 0; ct < EC_NT; ++ct) {
-                    const float b = wr[ct * 16];
-                    acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][ct], 0, 0, 0);
-                    acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][ct], 0, 0, 0);
-                }
-            }
-        }
+        tile_taps<1, EC_NT>(in_l, w_l, acc);
     }
-    // register j of lane l is pixel 4 (l / 16) + j of the row block, column 16 ct + l % 16
-    float *ob = out + (long long)f * BT_WINDOW_C * hw;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int y = ty0 + 2 * wave + r;
-        if (y >= h) continue;
-#pragma unroll
-        for (int ct = 0; ct < EC_NT; ++ct) {
-            const int col = ct * 16 + l16;
-            const float b = bias[col];
-            float *orow = ob + (long long)col * hw + (long long)y * w;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x = tx0 + 4 * q + j;
-                if (x < w) orow[x] = __fadd_rn(acc[r][ct][j], b);
-            }
-        }
-    }
+    tile_store_stats<EC_NT, false>(acc, bias, out + (long long)f * BT_WINDOW_C * hw, hw, h, w, ty0, tx0, nullptr, nullptr);
 }
 
 // --------------------------------------------------------------------------------------------------------- k_feat_sample
@@ -237,8 +190,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_feat_sample(const float *__restr
         out[k * BT_WINDOW_C + threadIdx.x] = bilinear_blend(fmaps + ((long long)fr * BT_WINDOW_C + threadIdx.x) * hw, t);
     }
 }
-
-constexpr long long kI31 = 2147483647LL;
 
 static unsigned wd_blocks(long long total) {
     const long long nb = (total + (long long)WD_THREADS * WD_PER_THREAD - 1) / ((long long)WD_THREADS * WD_PER_THREAD);
@@ -294,11 +245,10 @@ extern "C" int bt_embed_conv(const float *fnet, int64_t sf, int64_t sc, int64_t 
         return BT_EINVAL;
     if (C != BT_WINDOW_C || S > bt::kI31 || h > bt::kI31 || w > bt::kI31 || (__int128)S * C * h * w > bt::kI31) return BT_EUNSUPPORTED;
     if (F == 0) return BT_OK;
-    if (sf > bt::kI31 || sc > bt::kI31 || sy > bt::kI31 || sx > bt::kI31
-        || (__int128)(F - 1) * sf + (__int128)(C - 1) * sc + (__int128)(h - 1) * sy + (__int128)(w - 1) * sx > bt::kI31) return BT_EUNSUPPORTED;
-    const long long tiles_x = (w + bt::EC_TW - 1) / bt::EC_TW, tiles_y = (h + bt::EC_TH - 1) / bt::EC_TH;
+    if (!bt::view_fits_i31(F, C, h, w, sf, sc, sy, sx)) return BT_EUNSUPPORTED;
+    const long long tiles_x = bt::conv_tiles_x(w);
     if (F > 65535) return BT_EUNSUPPORTED;                       // the grid's second dimension
-    hipLaunchKernelGGL(bt::k_embed_conv, dim3((unsigned)(tiles_x * tiles_y), (unsigned)F), dim3(bt::EC_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(bt::k_embed_conv, dim3((unsigned)bt::conv_tiles(h, w), (unsigned)F), dim3(bt::CT_THREADS), 0, (hipStream_t)stream,
                        fnet, (long long)sf, (long long)sc, (long long)sy, (long long)sx, dmaps, zrange, wpacked, bias, freqs, (int)frame0,
                        (int)h, (int)w, (int)tiles_x, out);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
