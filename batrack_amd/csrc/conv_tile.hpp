@@ -29,7 +29,8 @@
 //                    as part_tile[column][2].  No atomics, and every (frame, tile, column) pair is written by its workgroup:
 //                    the partials need no initialisation.  With STATS it contains a barrier: every thread of the workgroup
 //                    calls it, `red` (LDS, 4 * 16 NT * 2 doubles) must not be in use by a thread that has not passed a
-//                    barrier before the call, and is read until the next barrier after it.
+//                    barrier before the call, and is read until the next barrier after it.  VEC4 with `rows16` (w % 4 == 0 and
+//                    16-byte aligned planes): a lane's four pixels of a row are stored as one float4; the same values and sums.
 // tile_order_stats   the partials of one (frame, column) added in tile order; mean = sum / n, var = max(sumsq / n - mean^2, 0),
 //                    rstd = 1 / sqrt(var + 1e-5), all float64, returned as floats.  A constant channel has an exact mean.
 // Host side: kI31, view_fits_i31 (a strided [F, C, h, w] view within 32-bit-safe offsets), conv_tiles_x, conv_tiles.
@@ -121,9 +122,10 @@ __device__ __forceinline__ void tile_stage_rows(float *w_l, const float *__restr
     }
 }
 
-template <int NT, bool STATS>
+template <int NT, bool STATS, bool VEC4 = false>
 __device__ __forceinline__ void tile_store_stats(const f32x4 (&tot)[2][NT], const float *__restrict__ bias, float *__restrict__ planes,
-                                                 long long hw, int h, int w, int ty0, int tx0, double *red, double *__restrict__ part_tile) {
+                                                 long long hw, int h, int w, int ty0, int tx0, double *red, double *__restrict__ part_tile,
+                                                 bool rows16 = false) {
     constexpr int COLS = 16 * NT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, q = lane >> 4;
 #pragma unroll
@@ -135,6 +137,24 @@ __device__ __forceinline__ void tile_store_stats(const f32x4 (&tot)[2][NT], cons
         for (int r = 0; r < 2; ++r) {
             const int y = ty0 + 2 * wave + r;
             float *yrow = planes + (long long)col * hw + (long long)y * w;
+            if constexpr (VEC4) {
+                if (rows16) {                                    // w % 4 == 0 and 16-byte planes: a lane's four pixels are one float4, all inside or all outside
+                    const int x = tx0 + 4 * q;
+                    if (y < h && x < w) {
+                        float4 v4;
+                        v4.x = __fadd_rn(tot[r][ct][0], b); v4.y = __fadd_rn(tot[r][ct][1], b);
+                        v4.z = __fadd_rn(tot[r][ct][2], b); v4.w = __fadd_rn(tot[r][ct][3], b);
+                        *reinterpret_cast<float4 *>(yrow + x) = v4;
+                        if constexpr (STATS) {                   // the same adds in the same order as below
+                            s1 += (double)v4.x; s2 += (double)v4.x * (double)v4.x;
+                            s1 += (double)v4.y; s2 += (double)v4.y * (double)v4.y;
+                            s1 += (double)v4.z; s2 += (double)v4.z * (double)v4.z;
+                            s1 += (double)v4.w; s2 += (double)v4.w * (double)v4.w;
+                        }
+                    }
+                    continue;
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int x = tx0 + 4 * q + j;

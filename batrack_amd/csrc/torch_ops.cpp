@@ -70,6 +70,8 @@
 //   batrack_hip::res_block(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor? wd, Tensor? bd, int stride, Tensor(a!) out) -> ()
 //       bt_res_block (include/batrack_encoder.h): x [F, c_in, h, w], any strides; w1 [c_in / 8, 9, 8, c_out]; w2 [c_out / 8, 9, 8,
 //       c_out]; wd [c_in, c_out] and bd exactly when stride is 2; out [F, c_out, ho, wo] contiguous
+//   batrack_hip::encoder_stem(Tensor x, Tensor w, Tensor b, Tensor(a!) out) -> ()
+//       bt_encoder_stem (include/batrack_encoder.h): x [F, 3, h, w], any strides; w [7, 3, 8, 64]; out [F, 64, ho, wo] contiguous
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -584,6 +586,29 @@ void res_block(const at::Tensor &x, const at::Tensor &w1, const at::Tensor &b1, 
     TORCH_CHECK(rc == BT_OK, op, "bt_res_block failed with status ", rc);
 }
 
+void encoder_stem(const at::Tensor &x, const at::Tensor &w, const at::Tensor &b, at::Tensor out) {
+    const char *op = "batrack_hip::encoder_stem: ";
+    const at::Tensor *all[] = {&x, &w, &b, &out};
+    for (const at::Tensor *t : all) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK(t->device() == x.device(), op, "tensors must be on one device");
+    }
+    TORCH_CHECK(x.dim() == 4 && x.size(1) == BT_ENC_CIMG && x.numel() > 0 && out.dim() == 4 && out.is_contiguous(), op,
+                "x must be [F, 3, h, w] and not empty, out contiguous");
+    const int64_t F = x.size(0), h = x.size(2), wd = x.size(3);
+    TORCH_CHECK(out.size(0) == F && out.size(1) == BT_ENC_CSTEM && out.size(2) == (h - 1) / 2 + 1 && out.size(3) == (wd - 1) / 2 + 1, op,
+                "out must be [F, 64, (h - 1) / 2 + 1, (w - 1) / 2 + 1]");
+    TORCH_CHECK(w.is_contiguous() && w.numel() == (int64_t)7 * BT_ENC_CIMG * 8 * BT_ENC_CSTEM && b.is_contiguous() && b.numel() == BT_ENC_CSTEM, op,
+                "w [7, 3, 8, 64] and b [64], contiguous");
+    const size_t bytes = bt_encoder_stem_workspace_bytes(F, h, wd);
+    TORCH_CHECK(bytes > 0, op, "F * 64 * ho * wo must not pass 2^31 - 1");
+    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options().dtype(at::kDouble));      // needs no initialisation
+    const bt_encoder_level lx{x.data_ptr<float>(), BT_ENC_CIMG, h, wd, x.stride(0), x.stride(1), x.stride(2), x.stride(3)};
+    const int rc = bt_encoder_stem(&lx, w.data_ptr<float>(), b.data_ptr<float>(), BT_ENC_CSTEM, F, ws.data_ptr(), out.data_ptr<float>(),
+                                   c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_encoder_stem failed with status ", rc);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -620,4 +645,5 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("encoder_head(Tensor a, Tensor b, Tensor c, Tensor d, Tensor w2_packed, Tensor bias2, Tensor w3_packed, Tensor bias3, "
           "Tensor(a!) out) -> ()", &encoder_head);
     m.def("res_block(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor? wd, Tensor? bd, int stride, Tensor(a!) out) -> ()", &res_block);
+    m.def("encoder_stem(Tensor x, Tensor w, Tensor b, Tensor(a!) out) -> ()", &encoder_stem);
 }

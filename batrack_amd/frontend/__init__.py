@@ -17,7 +17,11 @@
   batrack_amd.frontend.encoder.encoder_trunk          layer1..4, the eight blocks: (a, b, c, d)
   batrack_amd.frontend.encoder.pack_block_weights     a block's weights in the layouts the kernels stage
   batrack_amd.frontend.encoder.packed_block           the same, cached per block
-  batrack_amd.frontend.encoder.forward                `BasicEncoder.forward` around them (the stem called as it is; encoder.DEVICE_LAYERS)
+  batrack_amd.frontend.encoder.encoder_stem           the encoder's stem: 7 x 7 stride-2 conv1, instance norm, ReLU, normalised in place, three launches
+  batrack_amd.frontend.encoder.pack_stem_weights      conv1's weights in the layout the kernel stages
+  batrack_amd.frontend.encoder.packed_stem            the same with the bias, cached per module
+  batrack_amd.frontend.encoder.stem_refusal           None, or what keeps a module's stem from being the reference's
+  batrack_amd.frontend.encoder.forward                `BasicEncoder.forward` around them (encoder.DEVICE_STEM, encoder.DEVICE_LAYERS)
   batrack_amd.frontend.encoder.install                make the reference's BasicEncoder use `forward`
   batrack_amd.frontend.observe.window_observations tracker output -> the BA's targets and weights
   batrack_amd.frontend.keyframe.prune_keyframe       keyframe removal and edge pruning

@@ -1,7 +1,7 @@
-"""The feature encoder's trunk and head (the reference's main/frontend/core/cotracker/blocks.py: the eight `ResidualBlock`s
-of layer1..4, lines 16-75, and lines 241-273, the last third of `BasicEncoder.forward`, with norm_fn="instance"), HIP
-underneath (batrack_amd/csrc/encoder_trunk.hip and encoder_head.hip through include/batrack_encoder.h, which holds the
-specification).
+"""The feature encoder's stem, trunk and head (the reference's main/frontend/core/cotracker/blocks.py: conv1, norm1, relu1,
+the eight `ResidualBlock`s of layer1..4, lines 16-75, and lines 241-273, the last third of `BasicEncoder.forward`, with
+norm_fn="instance"), HIP underneath (batrack_amd/csrc/encoder_stem.hip, encoder_trunk.hip and encoder_head.hip through
+include/batrack_encoder.h, which holds the specification).
 
     pack_head_weights(conv2_weight [256,416,3,3], conv3_weight [128,256,1,1]) -> ([52,9,8,256], [256,128])
                                                                                  the layouts the kernels stage (permutations)
@@ -16,8 +16,16 @@ specification).
                                                                                  ReLU, (shortcut conv, norm,) add, ReLU; no
                                                                                  normalised map is in memory; five launches
     encoder_trunk(x, layer1, layer2, layer3, layer4) -> (a, b, c, d)             the eight blocks, always on the kernels
-    forward(self, x)                                                             `BasicEncoder.forward` in our own words: conv1,
-                                                                                 norm1, relu1 are called as they are; a layer in
+    pack_stem_weights(conv1_weight [64,3,7,7]) -> [7,3,8,64]                     w[ky, c, kx, m], the eighth kx a zero
+    packed_stem(conv1) -> (w, bias)                                              cached per module
+    stem_refusal(enc) -> None or str                                             the first thing that is not the reference's stem
+    encoder_stem(x, conv1, out=None) -> [F, 64, ho, wo]                          conv1 7 x 7 stride 2, instance norm, ReLU: the raw
+                                                                                 map is written once and normalised in place;
+                                                                                 three launches
+    forward(self, x)                                                             `BasicEncoder.forward` in our own words: the stem
+                                                                                 runs on the kernels when DEVICE_STEM and it is the
+                                                                                 reference's (`stem_refusal`), else conv1, norm1,
+                                                                                 relu1 are called as they are; a layer in
                                                                                  DEVICE_LAYERS that is a Sequential of residual
                                                                                  blocks runs on the kernels, any other layer is
                                                                                  called as it is; then `encoder_head`
@@ -40,6 +48,10 @@ BLOCK_CHANNELS = (64, 96, 128)
 # The layers `forward` sends to the kernels: those whose measured device time is not above torch's at 12 and at 6 frames of
 # 64 x 192 x 256 (profiles/r26_encoder_trunk.txt; DESIGN.md f-13 has both numbers of every layer).
 DEVICE_LAYERS = ("layer1", "layer2")
+CIMG, CSTEM = 3, 64          # BT_ENC_CIMG, BT_ENC_CSTEM
+# Whether `forward` sends the stem to the kernels: only if its measured device time is not above torch's at 12 and at 6 frames
+# of 3 x 384 x 512 (profiles/r28_encoder_stem.txt).
+DEVICE_STEM = True
 
 
 def _gpu(name, t, what):
@@ -252,6 +264,93 @@ def residual_block(x, block, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- the stem
+def pack_stem_weights(conv1_weight):
+    """[64, 3, 7, 7] -> [7, 3, 8, 64]: w[ky, c, kx, m] = conv1_weight[m, c, ky, kx] for kx < 7 and w[ky, c, 7, m] = 0.  A
+    permutation of the 9408 weights plus 1344 zeros (any device)."""
+    if tuple(conv1_weight.shape) != (CSTEM, CIMG, 7, 7):
+        raise RuntimeError(f"encoder_stem: conv1 must be 7 x 7 from {CIMG} to {CSTEM} channels, not {tuple(conv1_weight.shape)}")
+    w = conv1_weight.detach().float()
+    packed = torch.zeros(7, CIMG, 8, CSTEM, dtype=torch.float32, device=w.device)
+    packed[:, :, :7, :] = w.permute(2, 1, 3, 0)
+    return packed
+
+
+def _stem_conv_refusal(conv1):
+    if not isinstance(conv1, torch.nn.Conv2d):
+        return f"conv1 must be a Conv2d, not {type(conv1).__name__}"
+    if not _conv_is(conv1, 7, 3, ((2, 2),)):
+        return "conv1 must be 7 x 7 with stride 2, padding 3 (zeros), a bias, no dilation and one group"
+    if conv1.in_channels != CIMG or conv1.out_channels != CSTEM:
+        return f"conv1 must go from {CIMG} to {CSTEM} channels, not {conv1.in_channels} -> {conv1.out_channels}"
+    return None
+
+
+def stem_refusal(enc):
+    """None when `enc.conv1`, `enc.norm1`, `enc.relu1` are the reference's stem (what `encoder_stem` computes); otherwise the
+    first thing that is not, in words."""
+    why = _stem_conv_refusal(getattr(enc, "conv1", None))
+    if why is not None:
+        return why
+    norm1, relu1 = getattr(enc, "norm1", None), getattr(enc, "relu1", None)
+    if not isinstance(norm1, torch.nn.InstanceNorm2d):
+        return f"norm1 must be an InstanceNorm2d (norm_fn \"instance\"), not {type(norm1).__name__}"
+    if not _plain_instance_norm(norm1):
+        return "norm1 must be an InstanceNorm2d without affine parameters or running statistics"
+    if abs(float(norm1.eps) - 1e-5) > 1e-12:
+        return f"norm1's eps must be 1e-5, not {norm1.eps}"
+    if not isinstance(relu1, torch.nn.ReLU):
+        return f"relu1 must be an nn.ReLU, not {type(relu1).__name__}"
+    return None
+
+
+_packed_stems = weakref.WeakKeyDictionary()   # conv1 -> (key, the two tensors)
+
+
+def packed_stem(conv1):
+    """(w, bias) of the stem's convolution, redone when either tensor is replaced or written to."""
+    why = _stem_conv_refusal(conv1)
+    if why is not None:
+        raise RuntimeError("encoder_stem: " + why)
+    ts = (conv1.weight, conv1.bias)
+    key = tuple(v for t in ts for v in (t.data_ptr(), t._version)) + (str(conv1.weight.device),)
+    hit = _packed_stems.get(conv1)
+    if hit is None or hit[0] != key:
+        hit = (key, (pack_stem_weights(conv1.weight), conv1.bias.detach().float().contiguous()))
+        _packed_stems[conv1] = hit
+    return hit[1]
+
+
+def encoder_stem(x, conv1, out=None):
+    """x [F, 3, h, w] (any strides, any size >= 1 x 1) through conv1, an instance normalisation (eps 1e-5) and a ReLU; `out`,
+    when given, is a contiguous [F, 64, ho, wo] (a slice of a larger buffer) that does not overlap x, ho = (h - 1) // 2 + 1."""
+    x = _gpu("x", x, "encoder_stem")
+    w, b = packed_stem(conv1)
+    if x.dim() != 4 or x.shape[1] != CIMG or min(x.shape) < 1:
+        raise RuntimeError(f"encoder_stem: `x` must be [F, {CIMG}, h, w] and not empty, not {tuple(x.shape)}")
+    if not w.is_cuda or w.device != x.device:
+        raise RuntimeError("encoder_stem: conv1 must be on the GPU of `x` (there is no CPU fallback in batrack_amd)")
+    F, ho, wo = x.shape[0], (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1
+    if out is None:
+        out = torch.empty(F, CSTEM, ho, wo, dtype=torch.float32, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == (F, CSTEM, ho, wo) and out.device == x.device):
+        raise RuntimeError(f"encoder_stem: `out` must be a contiguous float32 [F, {CSTEM}, {ho}, {wo}] on the GPU of `x`")
+    ops = _lib.torch_ops()
+    if ops is not None:
+        ops.encoder_stem(x, w, b, out)
+        return out
+    L = _lib.lib()
+    nbytes = L.bt_encoder_stem_workspace_bytes(F, x.shape[2], x.shape[3])
+    if nbytes == 0:
+        raise RuntimeError("encoder_stem: " + _lib.ERRORS[_lib.BT_EUNSUPPORTED])
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)           # needs no initialisation
+    lx = _level(x)
+    _lib.check(L.bt_encoder_stem(ctypes.byref(lx), w.data_ptr(), b.data_ptr(), CSTEM, F, ws.data_ptr(), out.data_ptr(),
+                                 torch.cuda.current_stream(x.device).cuda_stream), "bt_encoder_stem")
+    return out
+
+
 def is_residual_layer(layer):
     return isinstance(layer, torch.nn.Sequential) and len(layer) > 0 and all(is_residual_shaped(b) for b in layer)
 
@@ -288,7 +387,7 @@ def forward(self, x):
     __, __, H, W = x.shape
     stride = int(self.stride)
     with torch.no_grad():
-        x = self.relu1(self.norm1(self.conv1(x)))
+        x = encoder_stem(x, self.conv1) if DEVICE_STEM and stem_refusal(self) is None else self.relu1(self.norm1(self.conv1(x)))
         maps = []
         for name in ("layer1", "layer2", "layer3", "layer4"):
             layer = getattr(self, name)

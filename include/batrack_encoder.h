@@ -1,5 +1,6 @@
-/* batrack_encoder.h — C ABI of the feature encoder: its head (bt_encoder_head, below) and one residual block of its trunk
- * layer1..4 (bt_res_block, specified before its declaration).  The stem (conv1 7 x 7, norm1, relu1) is not here.
+/* batrack_encoder.h — C ABI of the feature encoder: its head (bt_encoder_head, below), one residual block of its trunk
+ * layer1..4 (bt_res_block, specified before its declaration) and its stem conv1 7 x 7, norm1, relu1 (bt_encoder_stem,
+ * specified before its declaration).
  *
  * The head (the reference's main/frontend/core/cotracker/blocks.py:241-273,
  * the last third of `BasicEncoder.forward` with norm_fn = "instance" and shallow = False): the four pyramid levels resized
@@ -132,6 +133,46 @@ struct bt_res_block {            /* a tag only: the name without `struct` is the
 size_t bt_res_block_workspace_bytes(int64_t F, int64_t c_out, int64_t h_in, int64_t w_in, int64_t stride);
 
 int bt_res_block(const bt_encoder_level *x, const struct bt_res_block *blk, int64_t F, void *workspace, float *out, void *stream);
+
+/* bt_encoder_stem — the stem (blocks.py: `relu1(norm1(conv1(x)))`, norm_fn = "instance").  Inference only, float32.
+ * x is a strided view [F, BT_ENC_CIMG = 3, h, w] read in place; ho = (h - 1) / 2 + 1, wo likewise; out is a contiguous
+ * [F, BT_ENC_CSTEM = 64, ho, wo] (possibly a slice of a larger buffer) that must NOT overlap x: the raw map is written into it
+ * while other tiles still read x.  Any h, w >= 1.
+ *
+ *   raw = conv1(x) + bias:   7 x 7, stride 2, zero padding 3 OF THE IMAGE: output (y, x) has its centre tap at input
+ *     (2 y, 2 x), a tap outside the h x w image contributing 0.  Summed on v_mfma_f32_16x16x4_f32 as float32 fma chains in
+ *     one order for every pixel of every frame: kernel row ky ascending; within a row channel c ascending; within a channel
+ *     kx ascending, 0..7, where kx = 7 is a zero weight times 0 or a finite image value (it leaves the chain's bits as they
+ *     are).  The chain of a kernel row (21 products) starts from zero and is added into the total when the row ends: seven
+ *     rounded adds, ky ascending; the bias is added last.
+ *   statistics per (frame, channel) over the n = ho * wo pixels: as the head's and the trunk's (float64 sum and sum of
+ *     squares of the stored float32 values, one partial per 16 x 8 tile, added in tile order; no floating-point atomics);
+ *     mean = sum / n; var = max(sumsq / n - mean^2, 0); rstd = 1 / sqrt(var + 1e-5) in float64, stored as floats m, r.
+ *   out = max(fl(fl(raw - m) * r), 0).  A constant channel has an exact mean, so it is exactly 0.
+ *
+ * `w_packed` is conv1.weight repacked as [7][3][8][64], 16-byte aligned: w_packed[ky][c][kx][m] = W[m][c][ky][kx] for
+ * kx < 7, and w_packed[ky][c][7][m] = 0: the eighth entry MUST be zero.
+ *
+ * Three launches (convolution into out, statistics, normalisation of out in place), no host read.  The order of every sum is
+ * fixed: a call repeats bit for bit, and frame f of F frames has the bits of that frame alone.
+ *
+ * workspace: bt_encoder_stem_workspace_bytes(F, h_in, w_in) bytes (0 when refused), 16-byte aligned: the tiles' partials and
+ * the statistics, no map.  Every byte that is read is written first: it needs NO initialisation.
+ * `x` is read on the HOST during the call; x->data and every other pointer is a DEVICE pointer.  The library allocates nothing.
+ * Returns
+ *   BT_EINVAL        a null pointer (x, x->data, w_packed, bias, workspace, out); F, h, w, x->C or c_out below 1; a negative
+ *                    stride of the view; w_packed or the workspace not 16-byte aligned;
+ *   BT_EUNSUPPORTED  x->C != 3 or c_out != 64; F above 65535; a size, a stride or an element offset of the view, the element
+ *                    count F * 64 * ho * wo or the tile count above 2^31 - 1;
+ *   BT_OK            otherwise;   BT_EHIP if a launch fails.
+ * Every refusal happens before any HIP call. */
+#define BT_ENC_CIMG 3
+#define BT_ENC_CSTEM 64
+
+size_t bt_encoder_stem_workspace_bytes(int64_t F, int64_t h_in, int64_t w_in);
+
+int bt_encoder_stem(const bt_encoder_level *x, const float *w_packed, const float *bias, int64_t c_out, int64_t F, void *workspace,
+                    float *out, void *stream);
 
 #ifdef __cplusplus
 }

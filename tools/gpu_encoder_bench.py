@@ -25,6 +25,16 @@ rows come from one rocprofv3 run of its own:
     python tools/gpu_encoder_bench.py --trunk [--reps 20] [--out profiles/r26_encoder_trunk.txt]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/gpu_encoder_bench.py --trunk-trace        (a run of its own)
     python tools/gpu_encoder_bench.py --trunk-trace-db DIR/.../*_results.db [--out ...]                  (appends the kernel rows)
+
+--stem measures the encoder's stem (bt_encoder_stem through encoder.encoder_stem) -> profiles/r28_encoder_stem.txt: 12 and 6
+frames of 3 x 384 x 512 beside `relu1(norm1(conv1(x)))` with the modules as the reference builds them (the ReLU in place),
+alternating, device time between two events; the peak memory a call adds; frame 0 of both against the statements in float64;
+`encoder.forward` on the same image with DEVICE_STEM on and off (off is the parent's forward); and the value DEVICE_STEM must
+have by the rule "not above torch's time at both shapes".  The kernel rows come from one rocprofv3 run of its own:
+
+    python tools/gpu_encoder_bench.py --stem [--reps 20] [--out profiles/r28_encoder_stem.txt]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/gpu_encoder_bench.py --stem-trace          (a run of its own)
+    python tools/gpu_encoder_bench.py --stem-trace-db DIR/.../*_results.db [--out ...]                    (appends the kernel rows)
 """
 import argparse
 import os
@@ -232,6 +242,126 @@ def trunk_main(args):
         fh.write("\n".join(lines) + "\n")
 
 
+# -------------------------------------------------------------------------------------------------------------- the stem
+STEM_LAUNCHES = ("k_stem_conv", "k_stem_stats", "k_stem_norm")  # bt_encoder_stem's three launches, in order
+STEM_K, STEM_K_PADDED = 147, 168
+
+
+def stem_setup(F):
+    import encoder_stem_util as S
+    m = S.StemEncoder(seed=500 + F).to(DEV)
+    x = torch.rand(F, 3, *TRUNK_IMAGE, generator=torch.Generator(device=DEV).manual_seed(600 + F), device=DEV) * 2 - 1
+    return S, m, x
+
+
+def stem_flop(F, k=STEM_K):
+    return 2 * k * 64 * (TRUNK_IMAGE[0] // 2) * (TRUNK_IMAGE[1] // 2) * F
+
+
+def stem_trace():
+    for __, F in SHAPES:
+        S, m, x = stem_setup(F)
+        for r in range(TRACE_CALLS):
+            encoder.encoder_stem(x, m.conv1)
+        torch.cuda.synchronize()
+
+
+def stem_trace_db(args):
+    import sqlite3
+    cur = sqlite3.connect(args.stem_trace_db).cursor()
+    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_stem_%' order by start").fetchall()
+    per_call = len(STEM_LAUNCHES)
+    with open(args.out) as fh:
+        lines = fh.read().splitlines()
+    last = lines.pop()                                           # the rule's outcome stays the last line
+    lines.append(f"kernel time, rocprofv3 --kernel-trace --stats in a run of its own ({TRACE_CALLS} stems per shape, the first {TRACE_SKIP} left out): "
+                 f"median us; the convolution with its TFLOP/s over the {STEM_K} products a pixel (and over the {STEM_K_PADDED} it multiplies) and share of "
+                 f"the {MFMA_F32_TFLOPS:.0f} TFLOP/s float32 MFMA rate; the elementwise pass with its GB/s")
+    if len(rows) != len(SHAPES) * TRACE_CALLS * per_call or any(STEM_LAUNCHES[i % per_call] not in r[0] for i, r in enumerate(rows)):
+        lines.append(f"  ({len(rows)} k_stem_* launches in the trace, {len(SHAPES) * TRACE_CALLS * per_call} expected: rows NOT attributed)")
+    else:
+        for k, (name, F) in enumerate(SHAPES):
+            part = rows[k * TRACE_CALLS * per_call:(k + 1) * TRACE_CALLS * per_call]
+            cells, total = [], 0.0
+            for j, launch in enumerate(STEM_LAUNCHES):
+                sel = [part[c * per_call + j] for c in range(TRACE_SKIP, TRACE_CALLS)]
+                us = float(np.median([r[1] for r in sel])) / 1e3
+                total += us
+                cell = f"{launch} {us:.0f}"
+                if launch == "k_stem_conv":
+                    tf, tfp = (stem_flop(F, kk) / (us * 1e-6) / 1e12 for kk in (STEM_K, STEM_K_PADDED))
+                    cell += f" ({tf:.1f} TFLOP/s, {100 * tf / MFMA_F32_TFLOPS:.0f} %; padded {tfp:.1f}, {100 * tfp / MFMA_F32_TFLOPS:.0f} %; {sel[0][4]} B LDS)"
+                if launch == "k_stem_norm":
+                    cell += f" ({2 * stem_flop(F, 1) * 2 / (us * 1e-6) / 1e9:.0f} GB/s read and written)"
+                cells.append(cell)
+            lines.append(f"  {name}: " + ", ".join(cells) + f"; sum of the three launches {total:.0f} us")
+    lines.append(last)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def stem_main(args):
+    import encoder_trunk_util as T
+    lines = []
+
+    def out(s):
+        print(s, flush=True)
+        lines.append(s)
+    q = lambda v: "{:.0f} [{:.0f} .. {:.0f}]".format(*np.quantile(v, [0.5, 0.1, 0.9]))
+    mb = lambda b: f"{b / 1e6:.1f} MB"
+    out(f"encoder stem on {torch.cuda.get_device_name(0)}: encoder_stem (new, three launches) against relu1(norm1(conv1(x))) with the modules as the "
+        "reference builds them, the ReLU in place (torch)")
+    out(f"3 x {TRUNK_IMAGE[0]} x {TRUNK_IMAGE[1]} images; the two alternating, {args.reps} calls each after warm-up; device time between two events, "
+        "us median [10 % .. 90 %]")
+    keep = {}
+    for name, F in SHAPES:
+        S, m, x = stem_setup(F)
+        with torch.no_grad():
+            new = lambda: encoder.encoder_stem(x, m.conv1)
+            ref = lambda: m.relu1(m.norm1(m.conv1(x)))
+            got, want = new(), ref()
+            want64 = S.stem(x[:1].double(), m.conv1.weight.double(), m.conv1.bias.double())     # frame 0: frames are independent
+            e_new, e_ref = (float((v[:1].double() - want64).abs().max()) for v in (got, want))
+            diff = float((got - want).abs().max())
+            del want64, got, want
+            d = {"new": [], "torch": []}
+            for r in range(2):                                   # alternate the two formulations
+                for f, fn in (("new", new), ("torch", ref)):
+                    d[f].append(timed(fn, args.reps // 2))
+            d = {f: np.concatenate(v) for f, v in d.items()}
+            mem = {f: added_memory(fn) for f, fn in (("new", new), ("torch", ref))}
+            keep[F] = (float(np.median(d["new"])), float(np.median(d["torch"])))
+            fl = stem_flop(F)
+            out(f"{name}: output {mb(F * 64 * (TRUNK_IMAGE[0] // 2) * (TRUNK_IMAGE[1] // 2) * 4)}; max |new - torch| {diff:.3e}; frame 0 against the "
+                f"statements in float64: new {e_new:.3e}, torch {e_ref:.3e}")
+            out(f"  device (events): new {q(d['new'])} us, torch {q(d['torch'])} us = {np.median(d['torch']) / np.median(d['new']):.2f}x; "
+                f"{fl / 1e9:.1f} GFLOP over the call's device time: new {fl / np.median(d['new']) / 1e6:.1f}, torch {fl / np.median(d['torch']) / 1e6:.1f} TFLOP/s")
+            out(f"  peak memory a call adds, its output included: new {mb(mem['new'])}, torch {mb(mem['torch'])}")
+            enc = T.TrunkEncoder().to(DEV)
+            committed = encoder.DEVICE_STEM
+
+            def forward_with(flag):
+                encoder.DEVICE_STEM = flag
+                try:
+                    return encoder.forward(enc, x)
+                finally:
+                    encoder.DEVICE_STEM = committed
+            d = {True: [], False: []}
+            for r in range(2):
+                for flag in (True, False):
+                    d[flag].append(timed(lambda: forward_with(flag), args.reps // 2))
+            d = {f: np.concatenate(v) for f, v in d.items()}
+            out(f"  encoder.forward on the same images: DEVICE_STEM on {q(d[True])} us; off (conv1, norm1, relu1 called as they are, the parent's "
+                f"forward) {q(d[False])} us = {np.median(d[False]) / np.median(d[True]):.2f}x")
+            del enc, m, x
+        torch.cuda.empty_cache()
+    rule = all(keep[F][0] <= keep[F][1] for __, F in SHAPES)
+    out(f"DEVICE_STEM by the rule (the stem's device time not above torch's at both shapes): {rule}; committed: {encoder.DEVICE_STEM}")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
@@ -239,13 +369,23 @@ def main():
     ap.add_argument("--trunk", action="store_true", help="measure the trunk (layer1..4) instead of the head")
     ap.add_argument("--trunk-trace", action="store_true", help=f"{TRACE_CALLS} trunks per shape, nothing written: for rocprofv3")
     ap.add_argument("--trunk-trace-db", help="append the trunk kernels' rows from a rocprofv3 results database, then exit")
+    ap.add_argument("--stem", action="store_true", help="measure the stem (conv1, norm1, relu1) instead of the head")
+    ap.add_argument("--stem-trace", action="store_true", help=f"{TRACE_CALLS} stems per shape, nothing written: for rocprofv3")
+    ap.add_argument("--stem-trace-db", help="append the stem kernels' rows from a rocprofv3 results database, then exit")
     args = ap.parse_args()
     trunk = args.trunk or args.trunk_trace or args.trunk_trace_db
-    args.out = args.out or os.path.join(ROOT, "profiles", "r26_encoder_trunk.txt" if trunk else "r22_encoder_head.txt")
+    stem = args.stem or args.stem_trace or args.stem_trace_db
+    args.out = args.out or os.path.join(ROOT, "profiles", "r28_encoder_stem.txt" if stem else "r26_encoder_trunk.txt" if trunk else "r22_encoder_head.txt")
     if args.trunk_trace_db:
         return trunk_trace_db(args)
+    if args.stem_trace_db:
+        return stem_trace_db(args)
     if not torch.cuda.is_available():
         raise SystemExit("needs a GPU: nothing is measured without one")
+    if args.stem_trace:
+        return stem_trace()
+    if args.stem:
+        return stem_main(args)
     if args.trunk_trace:
         return trunk_trace()
     if args.trunk:
