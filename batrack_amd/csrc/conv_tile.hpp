@@ -33,11 +33,24 @@
 //                    16-byte aligned planes): a lane's four pixels of a row are stored as one float4; the same values and sums.
 // tile_order_stats   the partials of one (frame, column) added in tile order; mean = sum / n, var = max(sumsq / n - mean^2, 0),
 //                    rstd = 1 / sqrt(var + 1e-5), all float64, returned as floats.  A constant channel has an exact mean.
-// Host side: kI31, view_fits_i31 (a strided [F, C, h, w] view within 32-bit-safe offsets), conv_tiles_x, conv_tiles.
+// norm_plain, norm_relu   fl(fl(v - mean) * rstd), and its maximum with 0: two rounded operations, never contracted.
+//
+// What surrounds the tile, once for the stem (encoder_stem.hip), the trunk (encoder_trunk.hip) and the head (encoder_head.hip):
+// ConvView, conv_view   a strided [F, C, h, w] view by value in a kernel's arguments, and the one of a bt_encoder_level.
+// conv_stats_launch     k_conv_stats (csrc/conv_stats.hip): one thread per (map, frame, channel) adds the tiles' partials in
+//                       tile order (tile_order_stats) and stores mean and rstd as floats.
+// pointwise_launch      a pointwise kernel over [F][C][n] planes, four pixels a thread or one: the argument list once.
+// conv_layout           the workspace of a call: raw maps, then the tiles' partials, then mean and rstd sets.
+// level_invalid, level_check   what every entry point refuses of a view, BT_EINVAL before BT_EUNSUPPORTED.
+// kI31, view_fits_i31 (a strided [F, C, h, w] view within 32-bit-safe offsets), conv_out, conv_tiles_x, conv_tiles.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
+
+#include "../../include/batrack_ba.h"
+#include "../../include/batrack_encoder.h"
 
 namespace bt {
 
@@ -199,6 +212,19 @@ __device__ __forceinline__ void tile_order_stats(const double *__restrict__ pp, 
     rstd_out = (float)(1.0 / sqrt(var + 1e-5));
 }
 
+__device__ __forceinline__ float norm_plain(float v, float mean, float rstd) { return __fmul_rn(__fsub_rn(v, mean), rstd); }
+
+__device__ __forceinline__ float norm_relu(float v, float mean, float rstd) {
+    const float z = norm_plain(v, mean, rstd);
+    return z > 0.0f ? z : 0.0f;
+}
+
+struct ConvView {                // a strided [F, C, h, w] view, by value in the kernel's arguments
+    const float *p;
+    long long sf, sc, sy, sx;
+    int h, w;
+};
+
 // ------------------------------------------------------------------------------------------------------------------ host
 constexpr long long kI31 = 2147483647LL;
 
@@ -212,5 +238,54 @@ inline bool view_fits_i31(long long F, long long C, long long h, long long w, lo
 
 inline long long conv_tiles_x(long long w) { return (w + CT_TW - 1) / CT_TW; }
 inline long long conv_tiles(long long h, long long w) { return ((h + CT_TH - 1) / CT_TH) * conv_tiles_x(w); }
+inline long long conv_out(long long n, long long stride) { return n < 1 ? 0 : (n - 1) / stride + 1; }      // 0: no such input size
+
+inline ConvView conv_view(const bt_encoder_level &l) { return ConvView{l.data, l.sf, l.sc, l.sy, l.sx, (int)l.h, (int)l.w}; }
+
+// a null view, a size below 1 or a negative stride: BT_EINVAL
+inline bool level_invalid(const bt_encoder_level *l) {
+    return !l || !l->data || l->h < 1 || l->w < 1 || l->sf < 0 || l->sc < 0 || l->sy < 0 || l->sx < 0;
+}
+
+// BT_OK when the level has C channels and its view of F frames can be read with 32-bit-safe offsets
+inline int level_check(const bt_encoder_level *l, long long C, long long F) {
+    if (level_invalid(l)) return BT_EINVAL;
+    if (l->C != C || !view_fits_i31(F, C, l->h, l->w, l->sf, l->sc, l->sy, l->sx)) return BT_EUNSUPPORTED;
+    return BT_OK;
+}
+
+// The workspace of a call on F frames of C channels of ho x wo output maps, as byte offsets: `raws` raw maps [F][C][n] float32
+// from 0 (slot r at raw_slot * r floats), rounded up to 16 bytes; from `part` `parts` sets of the tiles' partials
+// [F][tiles][C][2] float64; from `stat` `stats` means [F][C] float32, then as many rstds.  The head keeps 1 / 1 / 0, the stem
+// 0 / 1 / 1 (its raw map is `out`), a block 2 or 3 of each.
+struct ConvLayout {
+    long long n, tiles, raw_slot, part_slot, stat_slot;
+    size_t part, stat, bytes;
+};
+
+// false when the sizes are refused: one below 1 or above 2^31 - 1, or more than 2^31 - 1 elements in the raw maps (in one map
+// when the call keeps none) or tiles.  The tile count cannot be what refuses: tiles <= ho * wo <= (2^31 - 1) / C whenever the
+// element count passes.
+inline bool conv_layout(long long F, long long C, long long ho, long long wo, int raws, int parts, int stats, ConvLayout *L) {
+    if (F < 1 || ho < 1 || wo < 1 || F > kI31 || ho > kI31 || wo > kI31) return false;
+    L->tiles = conv_tiles(ho, wo);
+    if ((__int128)(raws ? raws : 1) * F * C * ho * wo > kI31 || L->tiles > kI31) return false;
+    L->n = ho * wo; L->raw_slot = F * C * L->n; L->part_slot = F * L->tiles * C * 2; L->stat_slot = F * C;
+    L->part = ((size_t)raws * L->raw_slot * sizeof(float) + 15) & ~(size_t)15;
+    L->stat = L->part + (size_t)parts * L->part_slot * sizeof(double);
+    L->bytes = L->stat + (size_t)stats * L->stat_slot * 2 * sizeof(float);
+    return true;
+}
+
+// part [count / C][tiles][C][2] -> mean, rstd [count]; false when the launch fails (csrc/conv_stats.hip)
+bool conv_stats_launch(hipStream_t st, const double *part, long long tiles, long long C, long long count, long long n, float *mean, float *rstd);
+
+// k4 (four pixels a thread: the caller has checked n % 4 == 0 and the alignment of every plane) or k1 over n pixels of C
+// channels of F frames, 256 threads a workgroup; false when the launch fails
+template <class... A, class... B>
+inline bool pointwise_launch(void (*k4)(A...), void (*k1)(A...), bool vec4, long long n, long long C, long long F, hipStream_t st, B... args) {
+    hipLaunchKernelGGL(vec4 ? k4 : k1, dim3((unsigned)(((vec4 ? n / 4 : n) + 255) / 256), (unsigned)C, (unsigned)F), dim3(256), 0, st, args...);
+    return hipGetLastError() == hipSuccess;
+}
 
 }  // namespace bt

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(CT_THREADS) void k_head_norm_conv(const float *__re
     const int f = blockIdx.y;
     const long long p0 = (long long)blockIdx.x * NC_PIX;
 
-    // the partials begin 16-byte aligned (bt_encoder_head refuses a workspace that is not, and enc_workspace rounds the
+    // the partials begin 16-byte aligned (bt_encoder_head refuses a workspace that is not, and conv_layout rounds the
     // bytes of y2 before them to 16), and a (tile, channel) pair is 16 bytes: tile_order_stats' double2 loads are legal
     tile_order_stats(part + ((long long)f * tiles * BT_ENC_CMID + tid) * 2, (long long)BT_ENC_CMID * 2, tiles, (double)hw, mean_l[tid], rstd_l[tid]);
 
@@ -155,10 +155,7 @@ __global__ __launch_bounds__(CT_THREADS) void k_head_norm_conv(const float *__re
         for (int idx = tid; idx < NC_KC * NC_PIX; idx += CT_THREADS) {
             const int chl = idx / NC_PIX, p = idx - chl * NC_PIX, c = chunk * NC_KC + chl;
             float z = 0.0f;
-            if (p0 + p < hw) {
-                z = __fmul_rn(__fsub_rn(yb[(long long)c * hw + p0 + p], mean_l[c]), rstd_l[c]);
-                z = z > 0.0f ? z : 0.0f;
-            }
+            if (p0 + p < hw) z = norm_relu(yb[(long long)c * hw + p0 + p], mean_l[c], rstd_l[c]);
             z_l[chl * NC_ZLD + p] = z;
         }
         __syncthreads();
@@ -185,24 +182,15 @@ __global__ __launch_bounds__(CT_THREADS) void k_head_norm_conv(const float *__re
     }
 }
 
-// bytes of y2 [F][256][h * w] float32, then of the partials [F][tiles][256][2] float64; 0 when the sizes are refused
-static size_t enc_workspace(long long F, long long h, long long w, size_t *part_offset) {
-    if (F < 1 || h < 1 || w < 1 || F > kI31 || h > kI31 || w > kI31 || (__int128)F * BT_ENC_CMID * h * w > kI31) return 0;
-    const size_t ybytes = ((size_t)F * BT_ENC_CMID * h * w * sizeof(float) + 15) & ~(size_t)15;
-    if (part_offset) *part_offset = ybytes;
-    return ybytes + (size_t)F * conv_tiles(h, w) * BT_ENC_CMID * 2 * sizeof(double);
-}
-
-// BT_OK when the level's view can be read with 32-bit-safe offsets
-static int enc_level_check(const bt_encoder_level *l, long long C, long long F) {
-    if (!l || !l->data || l->h < 1 || l->w < 1 || l->sf < 0 || l->sc < 0 || l->sy < 0 || l->sx < 0) return BT_EINVAL;
-    if (l->C != C || !view_fits_i31(F, C, l->h, l->w, l->sf, l->sc, l->sy, l->sx)) return BT_EUNSUPPORTED;
-    return BT_OK;
-}
+// y2 [F][256][h * w] float32, then the partials [F][tiles][256][2] float64; no statistics (k_head_norm_conv reduces in-kernel)
+static bool head_layout(long long F, long long h, long long w, ConvLayout *L) { return conv_layout(F, BT_ENC_CMID, h, w, 1, 1, 0, L); }
 
 }  // namespace bt
 
-extern "C" size_t bt_encoder_head_workspace_bytes(int64_t F, int64_t h, int64_t w) { return bt::enc_workspace(F, h, w, nullptr); }
+extern "C" size_t bt_encoder_head_workspace_bytes(int64_t F, int64_t h, int64_t w) {
+    bt::ConvLayout L;
+    return bt::head_layout(F, h, w, &L) ? L.bytes : 0;
+}
 
 extern "C" int bt_encoder_head(const bt_encoder_level *a, const bt_encoder_level *b, const bt_encoder_level *c, const bt_encoder_level *d,
                                const float *w2_packed, const float *bias2, int64_t c_mid, const float *w3_packed, const float *bias3,
@@ -213,30 +201,26 @@ extern "C" int bt_encoder_head(const bt_encoder_level *a, const bt_encoder_level
     const bt_encoder_level *lv[4] = {a, b, c, d};
     const long long ch[4] = {BT_ENC_CA, BT_ENC_CB, BT_ENC_CC, BT_ENC_CD};
     for (int i = 0; i < 4; ++i)                                  // invalid arguments first, whatever level they are in
-        if (bt::enc_level_check(lv[i], lv[i]->C, 1) == BT_EINVAL) return BT_EINVAL;
-    if (c_mid != BT_ENC_CMID || c_out != BT_ENC_COUT || F > bt::kI31 || h > bt::kI31 || w > bt::kI31) return BT_EUNSUPPORTED;
-    size_t part_offset = 0;
-    if (bt::enc_workspace(F, h, w, &part_offset) == 0) return BT_EUNSUPPORTED;
-    for (int i = 0; i < 4; ++i) {
-        const int rc = bt::enc_level_check(lv[i], ch[i], F);
-        if (rc != BT_OK) return rc;
-    }
-    const long long tiles_x = bt::conv_tiles_x(w), tiles = bt::conv_tiles(h, w), hw = (long long)h * w;
-    if (F > 65535 || tiles > bt::kI31) return BT_EUNSUPPORTED;
+        if (bt::level_invalid(lv[i])) return BT_EINVAL;
+    bt::ConvLayout W;
+    if (c_mid != BT_ENC_CMID || c_out != BT_ENC_COUT || F > 65535 || !bt::head_layout(F, h, w, &W)) return BT_EUNSUPPORTED;
+    for (int i = 0; i < 4; ++i)
+        if (bt::level_check(lv[i], ch[i], F) != BT_OK) return BT_EUNSUPPORTED;
     bt::HeadLevels L;
     for (int i = 0; i < 4; ++i) {
-        L.p[i] = lv[i]->data;
-        L.sf[i] = lv[i]->sf; L.sc[i] = lv[i]->sc; L.sy[i] = lv[i]->sy; L.sx[i] = lv[i]->sx;
-        L.hl[i] = (int)lv[i]->h; L.wl[i] = (int)lv[i]->w;
+        const bt::ConvView v = bt::conv_view(*lv[i]);
+        L.p[i] = v.p;
+        L.sf[i] = v.sf; L.sc[i] = v.sc; L.sy[i] = v.sy; L.sx[i] = v.sx;
+        L.hl[i] = v.h; L.wl[i] = v.w;
         L.scale_y[i] = h > 1 ? (float)(lv[i]->h - 1) / (float)(h - 1) : 0.0f;
         L.scale_x[i] = w > 1 ? (float)(lv[i]->w - 1) / (float)(w - 1) : 0.0f;
     }
     float *ybuf = (float *)workspace;
-    double *part = (double *)((char *)workspace + part_offset);
-    hipLaunchKernelGGL(bt::k_head_conv, dim3((unsigned)tiles, (unsigned)F, (unsigned)bt::HC_HALVES), dim3(bt::CT_THREADS), 0,
-                       (hipStream_t)stream, L, w2_packed, bias2, (int)h, (int)w, (int)tiles_x, ybuf, part);
+    double *part = (double *)((char *)workspace + W.part);
+    hipLaunchKernelGGL(bt::k_head_conv, dim3((unsigned)W.tiles, (unsigned)F, (unsigned)bt::HC_HALVES), dim3(bt::CT_THREADS), 0,
+                       (hipStream_t)stream, L, w2_packed, bias2, (int)h, (int)w, (int)bt::conv_tiles_x(w), ybuf, part);
     if (hipGetLastError() != hipSuccess) return BT_EHIP;
-    hipLaunchKernelGGL(bt::k_head_norm_conv, dim3((unsigned)((hw + bt::NC_PIX - 1) / bt::NC_PIX), (unsigned)F), dim3(bt::CT_THREADS), 0,
-                       (hipStream_t)stream, (const float *)ybuf, (const double *)part, (int)tiles, w3_packed, bias3, hw, out);
+    hipLaunchKernelGGL(bt::k_head_norm_conv, dim3((unsigned)((W.n + bt::NC_PIX - 1) / bt::NC_PIX), (unsigned)F), dim3(bt::CT_THREADS), 0,
+                       (hipStream_t)stream, (const float *)ybuf, (const double *)part, (int)W.tiles, w3_packed, bias3, W.n, out);
     return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
 }

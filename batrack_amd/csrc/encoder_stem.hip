@@ -1,5 +1,5 @@
 // encoder_stem.hip — the feature encoder's stem, conv1 7 x 7 stride 2 from 3 to 64 channels, norm1, relu1
-// (include/batrack_encoder.h holds the specification): k_stem_conv, k_stem_stats, k_stem_norm.
+// (include/batrack_encoder.h holds the specification): k_stem_conv, k_conv_stats (csrc/conv_stats.hip), k_stem_norm.
 //
 // k_stem_conv is an implicit GEMM on v_mfma_f32_16x16x4_f32 with the tile of csrc/conv_tile.hpp (16 x 8 output pixels, four
 // waves, all 64 columns: NT = 4).  K = (ky, c, kx) with kx padded from 7 to 8 by a zero weight: 168 rows, 42 groups of four.
@@ -15,7 +15,7 @@
 //            every ky (21 products and 3 zeros) the chain is added into the total and starts again; the bias last.
 //   output   raw = conv + bias straight into out's [F][64][ho * wo] planes, a lane's four pixels as one float4 where the rows
 //            allow, and per (frame, tile, column) the float64 sum and sum of squares of the stored values (tile_store_stats).
-// k_stem_stats: one thread per (frame, channel) adds the tiles' partials in tile order (tile_order_stats).
+// k_conv_stats: one thread per (frame, channel) adds the tiles' partials in tile order (tile_order_stats).
 // k_stem_norm: out = max(fl(fl(out - mean) * rstd), 0) in place.
 // What they leave on the table is in DESIGN.md.
 #include <hip/hip_runtime.h>
@@ -29,12 +29,6 @@
 
 namespace bt {
 
-struct StemView {                // a strided [F, 3, h, w] view, by value in the kernel's arguments
-    const float *p;
-    long long sf, sc, sy, sx;
-    int h, w;
-};
-
 constexpr int ST_NT = BT_ENC_CSTEM / 16, ST_WLD = conv_wld(BT_ENC_CSTEM);
 constexpr int ST_KY = 7, ST_KX = 8, ST_ROWS = ST_KY * BT_ENC_CIMG * ST_KX;                       // 168 rows of the packed weight
 constexpr int ST_HW = 2 * (CT_TW - 1) + ST_KX, ST_HH = 2 * (CT_TH - 1) + ST_KY;                  // 38 x 21
@@ -47,7 +41,7 @@ static_assert(ST_ODD >= ST_PART && ST_ODD % 32 == 16, "the odd part's LDS offset
 // ------------------------------------------------------------------------------------------------------------- k_stem_conv
 // workgroup blockIdx.x takes tiles ST_TPW blockIdx.x .. of frame blockIdx.y, one after the other; part [F][tiles][64][2];
 // rows16: wo % 4 == 0 and out 16-byte aligned, so a lane's four pixels of a row are stored as one float4
-__global__ __launch_bounds__(CT_THREADS) void k_stem_conv(const StemView X, const float *__restrict__ wp, const float *__restrict__ bias, int ho, int wo,
+__global__ __launch_bounds__(CT_THREADS) void k_stem_conv(const ConvView X, const float *__restrict__ wp, const float *__restrict__ bias, int ho, int wo,
                                                           int tiles_x, int tiles, int rows16, float *__restrict__ out, double *__restrict__ part) {
     __shared__ __attribute__((aligned(16))) float w_l[ST_ROWS * ST_WLD];          // [ky][c][kx][ST_WLD]
     __shared__ __attribute__((aligned(16))) float in_l[ST_ODD + ST_PART];         // even columns [c][row][19], then the odd ones
@@ -113,20 +107,6 @@ __global__ __launch_bounds__(CT_THREADS) void k_stem_conv(const StemView X, cons
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------ k_stem_stats
-// part [F][tiles][64][2]; mean, rstd [F][64]; thread i is (frame, channel) i
-__global__ __launch_bounds__(64) void k_stem_stats(const double *__restrict__ part, int tiles, long long count, double n, float *__restrict__ mean,
-                                                   float *__restrict__ rstd) {
-    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (i >= count) return;
-    const long long f = i / BT_ENC_CSTEM;
-    const int c = (int)(i - f * BT_ENC_CSTEM);
-    float m, r;
-    tile_order_stats(part + (f * tiles * BT_ENC_CSTEM + c) * 2, (long long)BT_ENC_CSTEM * 2, tiles, n, m, r);
-    mean[i] = m;
-    rstd[i] = r;
-}
-
 // ------------------------------------------------------------------------------------------------------------- k_stem_norm
 // out [F][64][n] holds raw and is normalised in place; the statistics [F][64].  V pixels a thread.
 template <int V>
@@ -143,64 +123,41 @@ __global__ __launch_bounds__(256) void k_stem_norm(const float *__restrict__ mea
         y[0] = out[base];
     }
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-        const float z = __fmul_rn(__fsub_rn(y[j], m), r);
-        y[j] = z > 0.0f ? z : 0.0f;
-    }
+    for (int j = 0; j < V; ++j) y[j] = norm_relu(y[j], m, r);
     if constexpr (V == 4) *reinterpret_cast<float4 *>(out + base) = float4{y[0], y[1], y[2], y[3]};
     else out[base] = y[0];
 }
 
-struct StemLayout {              // byte offsets into the workspace: the tiles' partials, then mean and rstd
-    long long ho, wo, n, tiles;
-    size_t stat, bytes;
-};
-
-// false when the sizes are refused
-static bool stem_layout(long long F, long long h, long long w, StemLayout *L) {
-    if (F < 1 || h < 1 || w < 1 || F > kI31 || h > kI31 || w > kI31) return false;
-    L->ho = (h - 1) / 2 + 1; L->wo = (w - 1) / 2 + 1; L->n = L->ho * L->wo; L->tiles = conv_tiles(L->ho, L->wo);
-    if ((__int128)F * BT_ENC_CSTEM * L->ho * L->wo > kI31 || L->tiles > kI31) return false;
-    L->stat = (size_t)F * L->tiles * BT_ENC_CSTEM * 2 * sizeof(double);
-    L->bytes = L->stat + (size_t)F * BT_ENC_CSTEM * 2 * sizeof(float);
-    return true;
+// the tiles' partials, then mean and rstd; no raw map (it is `out`); false when the sizes are refused
+static bool stem_layout(long long F, long long h, long long w, ConvLayout *L) {
+    return conv_layout(F, BT_ENC_CSTEM, conv_out(h, 2), conv_out(w, 2), 0, 1, 1, L);
 }
 
 }  // namespace bt
 
 extern "C" size_t bt_encoder_stem_workspace_bytes(int64_t F, int64_t h_in, int64_t w_in) {
-    bt::StemLayout L;
+    bt::ConvLayout L;
     return bt::stem_layout(F, h_in, w_in, &L) ? L.bytes : 0;
 }
 
 extern "C" int bt_encoder_stem(const bt_encoder_level *x, const float *w_packed, const float *bias, int64_t c_out, int64_t F, void *workspace,
                                float *out, void *stream) {
     using namespace bt;
-    if (!x || !x->data || !w_packed || !bias || !workspace || !out) return BT_EINVAL;
-    if (F < 1 || x->h < 1 || x->w < 1 || x->C < 1 || c_out < 1) return BT_EINVAL;
-    if (x->sf < 0 || x->sc < 0 || x->sy < 0 || x->sx < 0) return BT_EINVAL;
+    if (!w_packed || !bias || !workspace || !out || level_invalid(x)) return BT_EINVAL;
+    if (F < 1 || x->C < 1 || c_out < 1) return BT_EINVAL;
     if (((uintptr_t)w_packed & 15) || ((uintptr_t)workspace & 15)) return BT_EINVAL;
-    if (x->C != BT_ENC_CIMG || c_out != BT_ENC_CSTEM || F > 65535) return BT_EUNSUPPORTED;
-    if (!view_fits_i31(F, BT_ENC_CIMG, x->h, x->w, x->sf, x->sc, x->sy, x->sx)) return BT_EUNSUPPORTED;
-    StemLayout L;
+    if (c_out != BT_ENC_CSTEM || F > 65535 || level_check(x, BT_ENC_CIMG, F) != BT_OK) return BT_EUNSUPPORTED;
+    ConvLayout L;
     if (!stem_layout(F, x->h, x->w, &L)) return BT_EUNSUPPORTED;
 
     hipStream_t st = (hipStream_t)stream;
     double *part = (double *)workspace;
-    float *mean = (float *)((char *)workspace + L.stat), *rstd = mean + F * BT_ENC_CSTEM;
-    const StemView X{x->data, x->sf, x->sc, x->sy, x->sx, (int)x->h, (int)x->w};
-    hipLaunchKernelGGL(k_stem_conv, dim3((unsigned)((L.tiles + ST_TPW - 1) / ST_TPW), (unsigned)F), dim3(CT_THREADS), 0, st, X, w_packed, bias,
-                       (int)L.ho, (int)L.wo, (int)conv_tiles_x(L.wo), (int)L.tiles, (int)(L.wo % 4 == 0 && ((uintptr_t)out & 15) == 0), out, part);
+    float *mean = (float *)((char *)workspace + L.stat), *rstd = mean + L.stat_slot;
+    const long long wo = conv_out(x->w, 2);
+    const bool out16 = ((uintptr_t)out & 15) == 0;
+    hipLaunchKernelGGL(k_stem_conv, dim3((unsigned)((L.tiles + ST_TPW - 1) / ST_TPW), (unsigned)F), dim3(CT_THREADS), 0, st, conv_view(*x), w_packed, bias,
+                       (int)conv_out(x->h, 2), (int)wo, (int)conv_tiles_x(wo), (int)L.tiles, (int)(wo % 4 == 0 && out16), out, part);
     if (hipGetLastError() != hipSuccess) return BT_EHIP;
-    const long long count = (long long)F * BT_ENC_CSTEM;
-    hipLaunchKernelGGL(k_stem_stats, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, (const double *)part, (int)L.tiles, count, (double)L.n, mean,
-                       rstd);
-    if (hipGetLastError() != hipSuccess) return BT_EHIP;
-    if (L.n % 4 == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL((k_stem_norm<4>), dim3((unsigned)((L.n / 4 + 255) / 256), BT_ENC_CSTEM, (unsigned)F), dim3(256), 0, st, (const float *)mean,
-                           (const float *)rstd, L.n, out);
-    else
-        hipLaunchKernelGGL((k_stem_norm<1>), dim3((unsigned)((L.n + 255) / 256), BT_ENC_CSTEM, (unsigned)F), dim3(256), 0, st, (const float *)mean,
-                           (const float *)rstd, L.n, out);
-    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+    if (!conv_stats_launch(st, part, L.tiles, BT_ENC_CSTEM, L.stat_slot, L.n, mean, rstd)) return BT_EHIP;
+    return pointwise_launch(k_stem_norm<4>, k_stem_norm<1>, L.n % 4 == 0 && out16, L.n, BT_ENC_CSTEM, F, st, mean, rstd, L.n, out) ? BT_OK : BT_EHIP;
 }

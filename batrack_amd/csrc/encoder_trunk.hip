@@ -1,5 +1,5 @@
 // encoder_trunk.hip — one residual block of the feature encoder's layer1..4 (include/batrack_encoder.h holds the
-// specification): k_res_conv, k_res_stats, k_res_join.
+// specification): k_res_conv, k_conv_stats (csrc/conv_stats.hip), k_res_join.
 //
 // k_res_conv<NORM, S, SHORT, NT> is a 3 x 3 convolution with zero padding 1 and stride S from c_in to 16 NT <= 128 channels, an
 // implicit GEMM on v_mfma_f32_16x16x4_f32 with the tile of csrc/conv_tile.hpp (all 16 NT columns), K = 9 taps x c_in.
@@ -18,8 +18,7 @@
 //            second raw map with its own statistics.
 //   output   raw = conv + bias as [F][16 NT][ho * wo] planes, and per (frame, tile, column) the float64 sum and sum of
 //            squares of the stored values (tile_store_stats).
-// k_res_stats: one thread per (map, frame, channel) adds the tiles' partials in tile order and stores mean and rstd as floats.
-// A launch of its own: at 192 x 256 a frame has 384 tiles, and every workgroup re-reducing them would read more than it stages.
+// k_conv_stats: one thread per (map, frame, channel) adds the tiles' partials in tile order and stores mean and rstd as floats.
 // k_res_join: out = max(fl(s + max(fl(fl(raw2 - m2) * r2), 0)), 0); s = x (stride 1) or fl(fl(rawd - md) * rd) (stride 2).
 // What they leave on the table is in DESIGN.md.
 #include <hip/hip_runtime.h>
@@ -33,17 +32,11 @@
 
 namespace bt {
 
-struct ResView {                 // a strided [F, C, h, w] view, by value in the kernel's arguments
-    const float *p;
-    long long sf, sc, sy, sx;
-    int h, w;
-};
-
 constexpr int RC_MAXC = 128;
 
 // -------------------------------------------------------------------------------------------------------------- k_res_conv
 template <bool NORM, int S, bool SHORT, int NT>
-__global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHORT ? 1 : 2))) void k_res_conv(const ResView X, int c_in, const float *__restrict__ mean, const float *__restrict__ rstd,
+__global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHORT ? 1 : 2))) void k_res_conv(const ConvView X, int c_in, const float *__restrict__ mean, const float *__restrict__ rstd,
                                                          const float *__restrict__ wp, const float *__restrict__ bias,
                                                          const float *__restrict__ wd, const float *__restrict__ bd, int ho, int wo, int tiles_x,
                                                          float *__restrict__ raw, double *__restrict__ part, float *__restrict__ rawd,
@@ -125,8 +118,7 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
             if constexpr (NORM) {
                 if ((inside >> k) & 1u) {
                     const int c = chunk * CT_KC + chl;
-                    v = __fmul_rn(__fsub_rn(v, mean_l[c]), rstd_l[c]);
-                    v = v > 0.0f ? v : 0.0f;
+                    v = norm_relu(v, mean_l[c], rstd_l[c]);
                 }
             }
             const int col = S == 1 ? hx : ((hx & 1) ? G::EVEN + (hx >> 1) : (hx >> 1));
@@ -153,8 +145,7 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
                 float t = src[chl * X.sc + cy * X.sy + cx * X.sx];
                 if constexpr (NORM) {
                     const int c = chunk * CT_KC + chl;
-                    t = __fmul_rn(__fsub_rn(t, mean_l[c]), rstd_l[c]);
-                    t = t > 0.0f ? t : 0.0f;
+                    t = norm_relu(t, mean_l[c], rstd_l[c]);
                 }
                 v[j] = in ? t : 0.0f;                            // zero padding of the (normalised, rectified) input map
             }
@@ -195,26 +186,12 @@ __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(SHOR
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------- k_res_stats
-// part [maps][F][tiles][C][2]; mean, rstd [maps][F][C]; thread i is (map, frame, channel) i
-__global__ __launch_bounds__(64) void k_res_stats(const double *__restrict__ part, int tiles, int C, long long count, double n,
-                                                  float *__restrict__ mean, float *__restrict__ rstd) {
-    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (i >= count) return;
-    const long long mf = i / C;
-    const int c = (int)(i - mf * C);
-    float m, r;
-    tile_order_stats(part + (mf * tiles * C + c) * 2, (long long)C * 2, tiles, n, m, r);
-    mean[i] = m;
-    rstd[i] = r;
-}
-
 // -------------------------------------------------------------------------------------------------------------- k_res_join
 // raw2, rawd [F][C][n]; the statistics [F][C]; X the block's input (DOWN: unused); out [F][C][n].  V pixels a thread.
 template <bool DOWN, int V>
 __global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2, const float *__restrict__ m2, const float *__restrict__ r2,
                                                   const float *__restrict__ rawd, const float *__restrict__ md, const float *__restrict__ rd,
-                                                  const ResView X, int C, int wo, long long n, float *__restrict__ out) {
+                                                  const ConvView X, int C, int wo, long long n, float *__restrict__ out) {
     const int c = blockIdx.y, f = blockIdx.z;
     const long long p = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
     if (p >= n) return;
@@ -236,7 +213,7 @@ __global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2
             s[0] = rawd[base];
         }
 #pragma unroll
-        for (int j = 0; j < V; ++j) s[j] = __fmul_rn(__fsub_rn(s[j], meand), rstdd);
+        for (int j = 0; j < V; ++j) s[j] = norm_plain(s[j], meand, rstdd);
     } else {
         const int py = (int)(p / wo), px = (int)(p - (long long)py * wo);
         const float *xs = X.p + f * X.sf + c * X.sc + py * X.sy + px * X.sx;
@@ -249,9 +226,7 @@ __global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-        float z = __fmul_rn(__fsub_rn(y[j], mean2), rstd2);
-        z = z > 0.0f ? z : 0.0f;
-        z = __fadd_rn(s[j], z);
+        const float z = __fadd_rn(s[j], norm_relu(y[j], mean2, rstd2));
         y[j] = z > 0.0f ? z : 0.0f;
     }
     if constexpr (V == 4) *reinterpret_cast<float4 *>(out + base) = float4{y[0], y[1], y[2], y[3]};
@@ -260,25 +235,15 @@ __global__ __launch_bounds__(256) void k_res_join(const float *__restrict__ raw2
 
 static bool res_channels(long long c) { return c == 64 || c == 96 || c == 128; }
 
-struct ResLayout {               // byte offsets into the workspace; maps = 2 (raw1, raw2) or 3 (raw1, rawd, raw2)
-    long long ho, wo, n, tiles, maps;
-    size_t part, stat, bytes;
-};
-
-// false when the sizes are refused
-static bool res_layout(long long F, long long c_out, long long h, long long w, long long stride, ResLayout *L) {
-    if (F < 1 || h < 1 || w < 1 || F > kI31 || h > kI31 || w > kI31 || !res_channels(c_out) || (stride != 1 && stride != 2)) return false;
-    L->ho = (h - 1) / stride + 1; L->wo = (w - 1) / stride + 1; L->n = L->ho * L->wo; L->tiles = conv_tiles(L->ho, L->wo);
-    L->maps = stride == 1 ? 2 : 3;
-    if ((__int128)L->maps * F * c_out * L->ho * L->wo > kI31 || L->tiles > kI31) return false;
-    L->part = ((size_t)L->maps * F * c_out * L->n * sizeof(float) + 15) & ~(size_t)15;
-    L->stat = L->part + (size_t)L->maps * F * L->tiles * c_out * 2 * sizeof(double);
-    L->bytes = L->stat + (size_t)L->maps * F * c_out * 2 * sizeof(float);
-    return true;
+// maps = 2 (raw1, raw2) or 3 (raw1, rawd, raw2) raw maps, sets of partials and sets of statistics; false when the sizes are refused
+static bool res_layout(long long F, long long c_out, long long h, long long w, long long stride, ConvLayout *L) {
+    if (!res_channels(c_out) || (stride != 1 && stride != 2)) return false;
+    const int maps = stride == 1 ? 2 : 3;
+    return conv_layout(F, c_out, conv_out(h, stride), conv_out(w, stride), maps, maps, maps, L);
 }
 
 template <bool NORM, int S, bool SHORT>
-static bool res_conv_launch(hipStream_t st, long long tiles, long long F, long long c_out, const ResView &X, int c_in, const float *mean, const float *rstd,
+static bool res_conv_launch(hipStream_t st, long long tiles, long long F, long long c_out, const ConvView &X, int c_in, const float *mean, const float *rstd,
                             const float *wp, const float *bias, const float *wd, const float *bd, int ho, int wo, int tiles_x, float *raw, double *part,
                             float *rawd, double *partd) {
     const dim3 grid((unsigned)tiles, (unsigned)F), block(CT_THREADS);
@@ -294,69 +259,49 @@ static bool res_conv_launch(hipStream_t st, long long tiles, long long F, long l
 }  // namespace bt
 
 extern "C" size_t bt_res_block_workspace_bytes(int64_t F, int64_t c_out, int64_t h_in, int64_t w_in, int64_t stride) {
-    bt::ResLayout L;
+    bt::ConvLayout L;
     return bt::res_layout(F, c_out, h_in, w_in, stride, &L) ? L.bytes : 0;
 }
 
 extern "C" int bt_res_block(const bt_encoder_level *x, const struct bt_res_block *blk, int64_t F, void *workspace, float *out, void *stream) {
     using namespace bt;
-    if (!x || !blk || !workspace || !out || !x->data || !blk->w1 || !blk->b1 || !blk->w2 || !blk->b2) return BT_EINVAL;
-    if (F < 1 || x->h < 1 || x->w < 1 || x->C < 1 || blk->c_in < 1 || blk->c_out < 1 || blk->stride < 1) return BT_EINVAL;
-    if (x->sf < 0 || x->sc < 0 || x->sy < 0 || x->sx < 0) return BT_EINVAL;
+    if (level_invalid(x) || !blk || !workspace || !out || !blk->w1 || !blk->b1 || !blk->w2 || !blk->b2) return BT_EINVAL;
+    if (F < 1 || x->C < 1 || blk->c_in < 1 || blk->c_out < 1 || blk->stride < 1) return BT_EINVAL;
     if (((uintptr_t)blk->w1 & 15) || ((uintptr_t)blk->w2 & 15) || ((uintptr_t)blk->wd & 15) || ((uintptr_t)workspace & 15)) return BT_EINVAL;
     if (blk->stride == 1 && (blk->wd || blk->bd)) return BT_EINVAL;
     if (blk->stride == 2 && (!blk->wd || !blk->bd)) return BT_EINVAL;
     const long long c_in = blk->c_in, c_out = blk->c_out, stride = blk->stride;
-    if (!res_channels(c_in) || !res_channels(c_out) || x->C != c_in || stride > 2 || (stride == 1 && c_in != c_out) || F > 65535) return BT_EUNSUPPORTED;
-    if (!view_fits_i31(F, c_in, x->h, x->w, x->sf, x->sc, x->sy, x->sx)) return BT_EUNSUPPORTED;
-    ResLayout L;
+    if (!res_channels(c_in) || !res_channels(c_out) || stride > 2 || (stride == 1 && c_in != c_out) || F > 65535) return BT_EUNSUPPORTED;
+    if (level_check(x, c_in, F) != BT_OK) return BT_EUNSUPPORTED;
+    ConvLayout L;
     if (!res_layout(F, c_out, x->h, x->w, stride, &L)) return BT_EUNSUPPORTED;
 
+    // slot 0 is raw1's, the last raw2's, and at stride 2 the shortcut's lies between them: raw1's statistics and the
+    // shortcut's are one launch
     hipStream_t st = (hipStream_t)stream;
-    const long long slot_f = (long long)F * c_out * L.n, slot_p = (long long)F * L.tiles * c_out * 2, slot_s = (long long)F * c_out;
-    float *raw1 = (float *)workspace, *rawd = stride == 2 ? raw1 + slot_f : nullptr, *raw2 = raw1 + (L.maps - 1) * slot_f;
-    double *part1 = (double *)((char *)workspace + L.part), *partd = stride == 2 ? part1 + slot_p : nullptr, *part2 = part1 + (L.maps - 1) * slot_p;
-    float *mean1 = (float *)((char *)workspace + L.stat), *rstd1 = mean1 + L.maps * slot_s;
-    float *meand = mean1 + slot_s, *rstdd = rstd1 + slot_s, *mean2 = mean1 + (L.maps - 1) * slot_s, *rstd2 = rstd1 + (L.maps - 1) * slot_s;
-    const int ho = (int)L.ho, wo = (int)L.wo, tiles_x = (int)conv_tiles_x(L.wo);
-    const ResView X{x->data, x->sf, x->sc, x->sy, x->sx, (int)x->h, (int)x->w};
-    const ResView Y{raw1, c_out * L.n, L.n, L.wo, 1, ho, wo};
+    const bool down = stride == 2;
+    const long long last = down ? 2 : 1;
+    float *raw1 = (float *)workspace, *rawd = down ? raw1 + L.raw_slot : nullptr, *raw2 = raw1 + last * L.raw_slot;
+    double *part1 = (double *)((char *)workspace + L.part), *partd = down ? part1 + L.part_slot : nullptr, *part2 = part1 + last * L.part_slot;
+    float *mean1 = (float *)((char *)workspace + L.stat), *rstd1 = mean1 + (last + 1) * L.stat_slot;
+    float *meand = down ? mean1 + L.stat_slot : nullptr, *rstdd = down ? rstd1 + L.stat_slot : nullptr;
+    float *mean2 = mean1 + last * L.stat_slot, *rstd2 = rstd1 + last * L.stat_slot;
+    const int ho = (int)conv_out(x->h, stride), wo = (int)conv_out(x->w, stride), tiles_x = (int)conv_tiles_x(wo);
+    const ConvView X = conv_view(*x), Y{raw1, c_out * L.n, L.n, wo, 1, ho, wo};
 
-    bool ok = stride == 1
-        ? res_conv_launch<false, 1, false>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, nullptr, nullptr, ho, wo, tiles_x, raw1, part1, nullptr, nullptr)
-        : res_conv_launch<false, 2, true>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, blk->wd, blk->bd, ho, wo, tiles_x, raw1, part1, rawd, partd);
-    if (!ok) return BT_EHIP;
-    const long long count1 = (L.maps - 1) * slot_s;              // raw1's statistics, and the shortcut's beside them
-    hipLaunchKernelGGL(k_res_stats, dim3((unsigned)((count1 + 63) / 64)), dim3(64), 0, st, (const double *)part1, (int)L.tiles, (int)c_out, count1,
-                       (double)L.n, mean1, rstd1);
-    if (hipGetLastError() != hipSuccess) return BT_EHIP;
+    bool ok = down
+        ? res_conv_launch<false, 2, true>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, blk->wd, blk->bd, ho, wo, tiles_x, raw1, part1, rawd, partd)
+        : res_conv_launch<false, 1, false>(st, L.tiles, F, c_out, X, (int)c_in, nullptr, nullptr, blk->w1, blk->b1, nullptr, nullptr, ho, wo, tiles_x, raw1, part1, nullptr, nullptr);
+    if (!ok || !conv_stats_launch(st, part1, L.tiles, c_out, last * L.stat_slot, L.n, mean1, rstd1)) return BT_EHIP;
     if (!res_conv_launch<true, 1, false>(st, L.tiles, F, c_out, Y, (int)c_out, mean1, rstd1, blk->w2, blk->b2, nullptr, nullptr, ho, wo, tiles_x, raw2, part2,
-                                         nullptr, nullptr))
+                                         nullptr, nullptr)
+        || !conv_stats_launch(st, part2, L.tiles, c_out, L.stat_slot, L.n, mean2, rstd2))
         return BT_EHIP;
-    hipLaunchKernelGGL(k_res_stats, dim3((unsigned)((slot_s + 63) / 64)), dim3(64), 0, st, (const double *)part2, (int)L.tiles, (int)c_out, slot_s,
-                       (double)L.n, mean2, rstd2);
-    if (hipGetLastError() != hipSuccess) return BT_EHIP;
 
+    // four pixels a thread: 16-byte rows of out and of the raw maps, and at stride 1 of x too
     const bool rows16 = L.n % 4 == 0 && ((uintptr_t)out & 15) == 0;
-    if (stride == 2) {
-        if (rows16)
-            hipLaunchKernelGGL((k_res_join<true, 4>), dim3((unsigned)((L.n / 4 + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
-                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)rawd, (const float *)meand, (const float *)rstdd, X,
-                               (int)c_out, wo, L.n, out);
-        else
-            hipLaunchKernelGGL((k_res_join<true, 1>), dim3((unsigned)((L.n + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
-                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)rawd, (const float *)meand, (const float *)rstdd, X,
-                               (int)c_out, wo, L.n, out);
-    } else {
-        const bool xrows16 = rows16 && L.wo % 4 == 0 && x->sx == 1 && x->sy % 4 == 0 && x->sc % 4 == 0 && x->sf % 4 == 0 && ((uintptr_t)x->data & 15) == 0;
-        if (xrows16)
-            hipLaunchKernelGGL((k_res_join<false, 4>), dim3((unsigned)((L.n / 4 + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
-                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, X,
-                               (int)c_out, wo, L.n, out);
-        else
-            hipLaunchKernelGGL((k_res_join<false, 1>), dim3((unsigned)((L.n + 255) / 256), (unsigned)c_out, (unsigned)F), dim3(256), 0, st,
-                               (const float *)raw2, (const float *)mean2, (const float *)rstd2, (const float *)nullptr, (const float *)nullptr, (const float *)nullptr, X,
-                               (int)c_out, wo, L.n, out);
-    }
-    return hipGetLastError() == hipSuccess ? BT_OK : BT_EHIP;
+    const bool xrows16 = rows16 && wo % 4 == 0 && x->sx == 1 && x->sy % 4 == 0 && x->sc % 4 == 0 && x->sf % 4 == 0 && ((uintptr_t)x->data & 15) == 0;
+    ok = pointwise_launch(down ? k_res_join<true, 4> : k_res_join<false, 4>, down ? k_res_join<true, 1> : k_res_join<false, 1>, down ? rows16 : xrows16,
+                          L.n, c_out, F, st, raw2, mean2, rstd2, rawd, meand, rstdd, X, (int)c_out, wo, L.n, out);
+    return ok ? BT_OK : BT_EHIP;
 }

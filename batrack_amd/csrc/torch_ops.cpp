@@ -97,6 +97,23 @@ const float *f32(const at::Tensor &t, const char *what) {
     return t.data_ptr<float>();
 }
 
+// every tensor is float32 on the GPU of the first (and contiguous, where the operator reads none in place)
+void all_f32(const char *op, const std::vector<const at::Tensor *> &ts, bool contiguous = false) {
+    for (const at::Tensor *t : ts) {
+        (void)f32(*t, "an argument");
+        TORCH_CHECK((!contiguous || t->is_contiguous()) && t->device() == ts[0]->device(), op,
+                    contiguous ? "tensors must be contiguous and on one device" : "tensors must be on one device");
+    }
+}
+
+bt_encoder_level level_of(const at::Tensor &t) {                 // a 4-D float32 tensor as the strided view it is
+    return bt_encoder_level{t.data_ptr<float>(), t.size(1), t.size(2), t.size(3), t.stride(0), t.stride(1), t.stride(2), t.stride(3)};
+}
+
+at::Tensor scratch(size_t bytes, const at::Tensor &like) {       // on `like`'s device; needs no initialisation
+    return at::empty({(int64_t)((bytes + 7) / 8)}, like.options().dtype(at::kDouble));
+}
+
 int64_t plan_create(const at::Tensor &ii, const at::Tensor &jj, const at::Tensor &kk, int64_t n_buf, int64_t p_tot,
                     int64_t fixedp, int64_t own_lo, int64_t own_hi) {
     for (const at::Tensor *t : {&ii, &jj, &kk})
@@ -369,11 +386,7 @@ at::Tensor track_tokens(const at::Tensor &coords, const c10::optional<at::Tensor
     const int64_t S = coords.size(0), N = coords.size(1), LRR = fcorrs.size(2), C = ffeats.size(2);
     TORCH_CHECK(w_flow.dim() == 2 && w_flow.size(1) == BT_TRACK_EMB && b_flow.numel() == w_flow.size(0), op, "w_flow [F, 195], b_flow [F]");
     const int64_t F = w_flow.size(0), E = F + LRR + C + 2;
-    const at::Tensor *all[] = {&coords, &fcorrs, &ffeats, &track_mask, &vis, &pos, &time, &w_flow, &b_flow};
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->is_contiguous() && t->device() == coords.device(), op, "tensors must be contiguous and on one device");
-    }
+    all_f32(op, {&coords, &fcorrs, &ffeats, &track_mask, &vis, &pos, &time, &w_flow, &b_flow}, true);
     TORCH_CHECK(fcorrs.size(0) == S && fcorrs.size(1) == N && ffeats.size(0) == S && ffeats.size(1) == N && track_mask.numel() == S * N
                 && vis.numel() == S * N && pos.numel() == N * E && time.numel() == S * E, op, "shapes disagree");
     const float *sub = nullptr;
@@ -400,11 +413,7 @@ at::Tensor track_apply(const at::Tensor &delta, const at::Tensor &gamma, const a
     TORCH_CHECK(delta.dim() == 3 && state.dim() == 3 && state.size(2) == 3 && ffeats.dim() == 3, op,
                 "delta [N, S, 3 + C], state [S, N, 3], ffeats [S, N, C]");
     const int64_t N = delta.size(0), S = delta.size(1), C = ffeats.size(2);
-    const at::Tensor *all[] = {&delta, &gamma, &beta, &w_u, &b_u, &state, &ffeats};
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->is_contiguous() && t->device() == delta.device(), op, "tensors must be contiguous and on one device");
-    }
+    all_f32(op, {&delta, &gamma, &beta, &w_u, &b_u, &state, &ffeats}, true);
     TORCH_CHECK(delta.size(2) == 3 + C && state.size(0) == S && state.size(1) == N && ffeats.size(0) == S && ffeats.size(1) == N
                 && gamma.numel() == C && beta.numel() == C && w_u.numel() == C * C && b_u.numel() == C, op, "shapes disagree");
     TORCH_CHECK(total.has_value() == dyn_mask.has_value(), op, "total and dyn_mask come together (the static pass)");
@@ -477,11 +486,7 @@ std::tuple<at::Tensor, at::Tensor> window_depth(const at::Tensor &depth, int64_t
 void embed_conv(const at::Tensor &fnet_maps, const at::Tensor &dmaps, const at::Tensor &zrange, const at::Tensor &wpacked,
                 const at::Tensor &bias, const at::Tensor &freqs, int64_t frame0, at::Tensor out) {
     const char *op = "batrack_hip::embed_conv: ";
-    const at::Tensor *all[] = {&fnet_maps, &dmaps, &zrange, &wpacked, &bias, &freqs, &out};
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->device() == fnet_maps.device(), op, "tensors must be on one device");
-    }
+    all_f32(op, {&fnet_maps, &dmaps, &zrange, &wpacked, &bias, &freqs, &out});
     TORCH_CHECK(fnet_maps.dim() == 4 && dmaps.dim() == 3 && dmaps.is_contiguous(), op, "fnet_maps [F, C, h, w], dmaps [S, h, w] contiguous");
     const int64_t F = fnet_maps.size(0), C = fnet_maps.size(1), h = fnet_maps.size(2), w = fnet_maps.size(3), S = dmaps.size(0);
     TORCH_CHECK(C == BT_WINDOW_C, op, "the encoder's maps must have ", BT_WINDOW_C, " channels");
@@ -524,11 +529,7 @@ at::Tensor feat_sample(const at::Tensor &fmaps, const at::Tensor &frames, const 
 void encoder_head(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor &d, const at::Tensor &w2_packed,
                   const at::Tensor &bias2, const at::Tensor &w3_packed, const at::Tensor &bias3, at::Tensor out) {
     const char *op = "batrack_hip::encoder_head: ";
-    const at::Tensor *all[] = {&a, &b, &c, &d, &w2_packed, &bias2, &w3_packed, &bias3, &out};
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->device() == a.device(), op, "tensors must be on one device");
-    }
+    all_f32(op, {&a, &b, &c, &d, &w2_packed, &bias2, &w3_packed, &bias3, &out});
     TORCH_CHECK(out.dim() == 4 && out.is_contiguous() && out.size(1) == BT_ENC_COUT && out.numel() > 0, op,
                 "out must be a contiguous [F, 128, h, w] and not empty");
     const int64_t F = out.size(0), h = out.size(2), w = out.size(3);
@@ -539,7 +540,7 @@ void encoder_head(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c,
         const at::Tensor &t = *lv[i];
         TORCH_CHECK(t.dim() == 4 && t.size(0) == F && t.size(1) == ch[i] && t.size(2) >= 1 && t.size(3) >= 1, op,
                     "the levels must be [F, 64 / 96 / 128 / 128, h_l, w_l] with out's F");
-        L[i] = bt_encoder_level{t.data_ptr<float>(), t.size(1), t.size(2), t.size(3), t.stride(0), t.stride(1), t.stride(2), t.stride(3)};
+        L[i] = level_of(t);
     }
     TORCH_CHECK(w2_packed.is_contiguous() && w2_packed.numel() == (int64_t)9 * BT_ENC_CIN * BT_ENC_CMID && bias2.is_contiguous()
                 && bias2.numel() == BT_ENC_CMID && w3_packed.is_contiguous() && w3_packed.numel() == (int64_t)BT_ENC_CMID * BT_ENC_COUT
@@ -547,7 +548,7 @@ void encoder_head(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c,
                 "w2_packed [52, 9, 8, 256], bias2 [256], w3_packed [256, 128], bias3 [128], all contiguous");
     const size_t bytes = bt_encoder_head_workspace_bytes(F, h, w);
     TORCH_CHECK(bytes > 0, op, "F * 256 * h * w must not pass 2^31 - 1");
-    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, a.options().dtype(at::kDouble));      // needs no initialisation
+    at::Tensor ws = scratch(bytes, a);
     const int rc = bt_encoder_head(&L[0], &L[1], &L[2], &L[3], w2_packed.data_ptr<float>(), bias2.data_ptr<float>(), BT_ENC_CMID,
                                    w3_packed.data_ptr<float>(), bias3.data_ptr<float>(), BT_ENC_COUT, F, h, w, ws.data_ptr(),
                                    out.data_ptr<float>(), c10::hip::getCurrentHIPStream(a.device().index()).stream());
@@ -561,10 +562,7 @@ void res_block(const at::Tensor &x, const at::Tensor &w1, const at::Tensor &b1, 
     TORCH_CHECK(down == (bd.has_value() && bd->defined()), op, "wd and bd come together");
     std::vector<const at::Tensor *> all = {&x, &w1, &b1, &w2, &b2, &out};
     if (down) { all.push_back(&*wd); all.push_back(&*bd); }
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->device() == x.device(), op, "tensors must be on one device");
-    }
+    all_f32(op, all);
     TORCH_CHECK(stride == 1 || stride == 2, op, "stride must be 1 or 2");
     TORCH_CHECK(down == (stride == 2), op, "wd and bd are given exactly when stride is 2");
     TORCH_CHECK(x.dim() == 4 && x.numel() > 0 && out.dim() == 4 && out.is_contiguous(), op, "x must be [F, c_in, h, w] and not empty, out contiguous");
@@ -578,8 +576,8 @@ void res_block(const at::Tensor &x, const at::Tensor &w1, const at::Tensor &b1, 
                           "wd [c_in, c_out] and bd [c_out], contiguous");
     const size_t bytes = bt_res_block_workspace_bytes(F, c_out, h, w, stride);
     TORCH_CHECK(bytes > 0, op, "channels must be 64, 96 or 128 and the element counts must not pass 2^31 - 1");
-    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options().dtype(at::kDouble));      // needs no initialisation
-    const bt_encoder_level lx{x.data_ptr<float>(), c_in, h, w, x.stride(0), x.stride(1), x.stride(2), x.stride(3)};
+    at::Tensor ws = scratch(bytes, x);
+    const bt_encoder_level lx = level_of(x);
     const struct bt_res_block blk{w1.data_ptr<float>(), b1.data_ptr<float>(), w2.data_ptr<float>(), b2.data_ptr<float>(),
                            down ? wd->data_ptr<float>() : nullptr, down ? bd->data_ptr<float>() : nullptr, c_in, c_out, stride};
     const int rc = bt_res_block(&lx, &blk, F, ws.data_ptr(), out.data_ptr<float>(), c10::hip::getCurrentHIPStream(x.device().index()).stream());
@@ -588,11 +586,7 @@ void res_block(const at::Tensor &x, const at::Tensor &w1, const at::Tensor &b1, 
 
 void encoder_stem(const at::Tensor &x, const at::Tensor &w, const at::Tensor &b, at::Tensor out) {
     const char *op = "batrack_hip::encoder_stem: ";
-    const at::Tensor *all[] = {&x, &w, &b, &out};
-    for (const at::Tensor *t : all) {
-        (void)f32(*t, "an argument");
-        TORCH_CHECK(t->device() == x.device(), op, "tensors must be on one device");
-    }
+    all_f32(op, {&x, &w, &b, &out});
     TORCH_CHECK(x.dim() == 4 && x.size(1) == BT_ENC_CIMG && x.numel() > 0 && out.dim() == 4 && out.is_contiguous(), op,
                 "x must be [F, 3, h, w] and not empty, out contiguous");
     const int64_t F = x.size(0), h = x.size(2), wd = x.size(3);
@@ -602,8 +596,8 @@ void encoder_stem(const at::Tensor &x, const at::Tensor &w, const at::Tensor &b,
                 "w [7, 3, 8, 64] and b [64], contiguous");
     const size_t bytes = bt_encoder_stem_workspace_bytes(F, h, wd);
     TORCH_CHECK(bytes > 0, op, "F * 64 * ho * wo must not pass 2^31 - 1");
-    at::Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options().dtype(at::kDouble));      // needs no initialisation
-    const bt_encoder_level lx{x.data_ptr<float>(), BT_ENC_CIMG, h, wd, x.stride(0), x.stride(1), x.stride(2), x.stride(3)};
+    at::Tensor ws = scratch(bytes, x);
+    const bt_encoder_level lx = level_of(x);
     const int rc = bt_encoder_stem(&lx, w.data_ptr<float>(), b.data_ptr<float>(), BT_ENC_CSTEM, F, ws.data_ptr(), out.data_ptr<float>(),
                                    c10::hip::getCurrentHIPStream(x.device().index()).stream());
     TORCH_CHECK(rc == BT_OK, op, "bt_encoder_stem failed with status ", rc);

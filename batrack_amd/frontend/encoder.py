@@ -40,10 +40,10 @@ import weakref
 import torch
 
 from .. import _lib
+from ._conv import KCHUNK, _gpu, bias_of, cached, out_tensor, repack3x3, scratch
 
 LEVELS = (64, 96, 128, 128)  # BT_ENC_CA .. BT_ENC_CD
 CIN, CMID, COUT = 416, 256, 128
-KCHUNK = 8                   # BT_WINDOW_KCHUNK
 BLOCK_CHANNELS = (64, 96, 128)
 # The layers `forward` sends to the kernels: those whose measured device time is not above torch's at 12 and at 6 frames of
 # 64 x 192 x 256 (profiles/r26_encoder_trunk.txt; DESIGN.md f-13 has both numbers of every layer).
@@ -54,12 +54,28 @@ CIMG, CSTEM = 3, 64          # BT_ENC_CIMG, BT_ENC_CSTEM
 DEVICE_STEM = True
 
 
-def _gpu(name, t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what}: `{name}` must be a tensor on the GPU (there is no CPU fallback in batrack_amd)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what}: `{name}` must be float32")
-    return t.detach()
+def _conv_refusal(conv, kernel, padding, strides):
+    """None, or what keeps `conv` from being a kernel x kernel Conv2d with that (zero) padding, one of `strides`, a bias, no
+    dilation and one group, in words that follow the convolution's name."""
+    if not isinstance(conv, torch.nn.Conv2d):
+        return f"must be a Conv2d, not {type(conv).__name__}"
+    if conv.bias is None:
+        return "has no bias"
+    if tuple(conv.kernel_size) != (kernel, kernel) or tuple(conv.padding) != (padding, padding) or tuple(conv.stride) not in strides \
+            or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or (padding and getattr(conv, "padding_mode", "zeros") != "zeros"):
+        return f"must be {kernel} x {kernel} with padding {padding} (zeros), stride {' or '.join(str(s[0]) for s in strides)}, no dilation and one group"
+    return None
+
+
+def _norm_refusal(m):
+    """None, or what keeps `m` from being the reference's norm (norm_fn "instance"), in words that follow the norm's name."""
+    if not isinstance(m, torch.nn.InstanceNorm2d):
+        return f" must be an InstanceNorm2d (norm_fn \"instance\"), not {type(m).__name__}"
+    if m.affine or m.track_running_stats or getattr(m, "weight", None) is not None or getattr(m, "running_mean", None) is not None:
+        return " must be an InstanceNorm2d without affine parameters or running statistics"
+    if abs(float(m.eps) - 1e-5) > 1e-12:
+        return f"'s eps must be 1e-5, not {m.eps}"
+    return None
 
 
 def pack_head_weights(conv2_weight, conv3_weight):
@@ -69,34 +85,24 @@ def pack_head_weights(conv2_weight, conv3_weight):
         raise RuntimeError(f"encoder_head: conv2 must be 3 x 3 from {CIN} to {CMID} channels, not {tuple(conv2_weight.shape)}")
     if tuple(conv3_weight.shape) != (COUT, CMID, 1, 1):
         raise RuntimeError(f"encoder_head: conv3 must be 1 x 1 from {CMID} to {COUT} channels, not {tuple(conv3_weight.shape)}")
-    w2 = conv2_weight.detach().float().permute(1, 2, 3, 0).reshape(CIN // KCHUNK, KCHUNK, 9, CMID).permute(0, 2, 1, 3).contiguous()
-    w3 = conv3_weight.detach().float().reshape(COUT, CMID).t().contiguous()
-    return w2, w3
+    return repack3x3(conv2_weight), conv3_weight.detach().float().reshape(COUT, CMID).t().contiguous()
 
 
-_packed = weakref.WeakKeyDictionary()        # conv2 -> (key, conv3 weak reference, the four tensors)
-
-
-def _check_conv(conv, name, kernel, padding):
-    if conv.bias is None:
-        raise RuntimeError(f"encoder_head: {name} has no bias")
-    if tuple(conv.kernel_size) != (kernel, kernel) or tuple(conv.padding) != (padding, padding) or tuple(conv.stride) != (1, 1) \
-            or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or (padding and getattr(conv, "padding_mode", "zeros") != "zeros"):
-        raise RuntimeError(f"encoder_head: {name} must be {kernel} x {kernel} with padding {padding} (zeros), stride 1, no dilation and one group")
+_packed = weakref.WeakKeyDictionary()        # conv2 -> (key, the four tensors)
 
 
 def packed_head(conv2, conv3):
     """The two modules' repacked weights and their biases, redone when any of the four tensors is replaced or written to."""
-    _check_conv(conv2, "conv2", 3, 1)
-    _check_conv(conv3, "conv3", 1, 0)
-    ts = (conv2.weight, conv2.bias, conv3.weight, conv3.bias)
-    key = tuple(v for t in ts for v in (t.data_ptr(), t._version)) + (str(conv2.weight.device),)
-    hit = _packed.get(conv2)
-    if hit is None or hit[0] != key or hit[1]() is not conv3:
+    for name, conv, kernel, padding in (("conv2", conv2, 3, 1), ("conv3", conv3, 1, 0)):
+        why = _conv_refusal(conv, kernel, padding, ((1, 1),))
+        if why is not None:
+            raise RuntimeError(f"encoder_head: {name} {why}")
+
+    def build():
         w2, w3 = pack_head_weights(conv2.weight, conv3.weight)
-        hit = (key, weakref.ref(conv3), (w2, conv2.bias.detach().float().contiguous(), w3, conv3.bias.detach().float().contiguous()))
-        _packed[conv2] = hit
-    return hit[2]
+        return w2, bias_of(conv2), w3, bias_of(conv3)
+    # the partner in the key: a weak reference equals another one only while both name the same living module
+    return cached(_packed, conv2, (conv2.weight, conv2.bias, conv3.weight, conv3.bias), build, extra=(weakref.ref(conv3),))
 
 
 def _level(t):
@@ -117,30 +123,18 @@ def encoder_head(a, b, c, d, conv2, conv3, size, out=None):
     w2, b2, w3, b3 = packed_head(conv2, conv3)
     if not w2.is_cuda or w2.device != levels[0].device or w3.device != w2.device:
         raise RuntimeError("encoder_head: the convolutions must be on the GPU of the maps (there is no CPU fallback in batrack_amd)")
-    if out is None:
-        out = torch.empty(F, COUT, h, w, dtype=torch.float32, device=levels[0].device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-              and tuple(out.shape) == (F, COUT, h, w) and out.device == levels[0].device):
-        raise RuntimeError(f"encoder_head: `out` must be a contiguous float32 [F, {COUT}, h, w] on the GPU of the maps")
+    out = out_tensor(out, (F, COUT, h, w), levels[0].device, "encoder_head", f"a contiguous float32 [F, {COUT}, h, w] on the GPU of the maps")
     ops = _lib.torch_ops()
     if ops is not None:
         ops.encoder_head(*levels, w2, b2, w3, b3, out)
         return out
     L = _lib.lib()
-    nbytes = L.bt_encoder_head_workspace_bytes(F, h, w)
-    if nbytes == 0:
-        raise RuntimeError("encoder_head: " + _lib.ERRORS[_lib.BT_EUNSUPPORTED])
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=out.device)         # needs no initialisation
+    ws = scratch(L.bt_encoder_head_workspace_bytes(F, h, w), out.device, "encoder_head")
     lv = [_level(t) for t in levels]
     _lib.check(L.bt_encoder_head(*(ctypes.byref(v) for v in lv), w2.data_ptr(), b2.data_ptr(), CMID, w3.data_ptr(), b3.data_ptr(), COUT,
                                  F, h, w, ws.data_ptr(), out.data_ptr(), torch.cuda.current_stream(out.device).cuda_stream),
                "bt_encoder_head")
     return out
-
-
-def _plain_instance_norm(m):
-    return isinstance(m, torch.nn.InstanceNorm2d) and not m.affine and not m.track_running_stats \
-        and getattr(m, "weight", None) is None and getattr(m, "running_mean", None) is None
 
 
 # ------------------------------------------------------------------------------------------------------ the residual blocks
@@ -155,17 +149,8 @@ def pack_block_weights(conv1_w, conv2_w, down_w=None):
         raise RuntimeError(f"residual_block: conv2 must be 3 x 3 from {c_out} to {c_out} channels, not {tuple(conv2_w.shape)}")
     if down_w is not None and tuple(down_w.shape) != (c_out, c_in, 1, 1):
         raise RuntimeError(f"residual_block: downsample[0] must be 1 x 1 from {c_in} to {c_out} channels, not {tuple(down_w.shape)}")
-
-    def pack(w):
-        return w.detach().float().permute(1, 2, 3, 0).reshape(w.shape[1] // KCHUNK, KCHUNK, 9, w.shape[0]).permute(0, 2, 1, 3).contiguous()
     wd = None if down_w is None else down_w.detach().float().reshape(c_out, c_in).t().contiguous()
-    return pack(conv1_w), pack(conv2_w), wd
-
-
-def _conv_is(conv, kernel, padding, strides):
-    return isinstance(conv, torch.nn.Conv2d) and tuple(conv.kernel_size) == (kernel, kernel) and tuple(conv.padding) == (padding, padding) \
-        and tuple(conv.stride) in strides and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.bias is not None \
-        and (not padding or getattr(conv, "padding_mode", "zeros") == "zeros")
+    return repack3x3(conv1_w), repack3x3(conv2_w), wd
 
 
 def is_residual_shaped(block):
@@ -176,12 +161,9 @@ def is_residual_shaped(block):
 
 
 def _check_norm(m, name):
-    if not isinstance(m, torch.nn.InstanceNorm2d):
-        raise RuntimeError(f"residual_block: {name} must be an InstanceNorm2d (norm_fn \"instance\"), not {type(m).__name__}")
-    if not _plain_instance_norm(m):
-        raise RuntimeError(f"residual_block: {name} must be an InstanceNorm2d without affine parameters or running statistics")
-    if abs(float(m.eps) - 1e-5) > 1e-12:
-        raise RuntimeError(f"residual_block: {name}'s eps must be 1e-5, not {m.eps}")
+    why = _norm_refusal(m)
+    if why is not None:
+        raise RuntimeError(f"residual_block: {name}{why}")
 
 
 def check_block(block):
@@ -189,9 +171,9 @@ def check_block(block):
     if not is_residual_shaped(block):
         raise RuntimeError("residual_block: the block must have conv1, conv2 (3 x 3 convolutions), norm1, norm2 and downsample")
     conv1, conv2 = block.conv1, block.conv2
-    if not _conv_is(conv1, 3, 1, ((1, 1), (2, 2))):
+    if _conv_refusal(conv1, 3, 1, ((1, 1), (2, 2))):
         raise RuntimeError("residual_block: conv1 must be 3 x 3 with padding 1 (zeros), stride 1 or 2, a bias, no dilation and one group")
-    if not _conv_is(conv2, 3, 1, ((1, 1),)):
+    if _conv_refusal(conv2, 3, 1, ((1, 1),)):
         raise RuntimeError("residual_block: conv2 must be 3 x 3 with padding 1 (zeros), stride 1, a bias, no dilation and one group")
     stride, c_in, c_out = conv1.stride[0], conv1.in_channels, conv1.out_channels
     if c_in not in BLOCK_CHANNELS or c_out not in BLOCK_CHANNELS or conv2.in_channels != c_out or conv2.out_channels != c_out:
@@ -207,7 +189,7 @@ def check_block(block):
     else:
         if down is None or not isinstance(down, torch.nn.Sequential) or len(down) != 2:
             raise RuntimeError("residual_block: a stride-2 block's downsample must be a Sequential of a convolution and a norm")
-        if not _conv_is(down[0], 1, 0, ((2, 2),)) or down[0].in_channels != c_in or down[0].out_channels != c_out:
+        if _conv_refusal(down[0], 1, 0, ((2, 2),)) or down[0].in_channels != c_in or down[0].out_channels != c_out:
             raise RuntimeError(f"residual_block: downsample[0] must be 1 x 1 with stride 2, no padding and a bias, from {c_in} to {c_out} channels")
         _check_norm(down[1], "downsample[1]")
     return stride
@@ -219,16 +201,13 @@ _packed_blocks = weakref.WeakKeyDictionary()  # block -> (key, the six tensors)
 def packed_block(block):
     """(w1, b1, w2, b2, wd, bd) of a residual block (wd, bd None at stride 1), redone when any tensor is replaced or written to."""
     stride = check_block(block)
-    convs = [block.conv1, block.conv2] + ([block.downsample[0]] if stride == 2 else [])
-    ts = [t for c in convs for t in (c.weight, c.bias)]
-    key = tuple(v for t in ts for v in (t.data_ptr(), t._version)) + (str(block.conv1.weight.device),)
-    hit = _packed_blocks.get(block)
-    if hit is None or hit[0] != key:
-        w1, w2, wd = pack_block_weights(block.conv1.weight, block.conv2.weight, block.downsample[0].weight if stride == 2 else None)
-        bias = lambda c: c.bias.detach().float().contiguous()
-        hit = (key, (w1, bias(block.conv1), w2, bias(block.conv2), wd, bias(block.downsample[0]) if stride == 2 else None))
-        _packed_blocks[block] = hit
-    return hit[1]
+    down = block.downsample[0] if stride == 2 else None
+    convs = [block.conv1, block.conv2] + ([down] if down is not None else [])
+
+    def build():
+        w1, w2, wd = pack_block_weights(block.conv1.weight, block.conv2.weight, None if down is None else down.weight)
+        return w1, bias_of(block.conv1), w2, bias_of(block.conv2), wd, None if down is None else bias_of(down)
+    return cached(_packed_blocks, block, [t for c in convs for t in (c.weight, c.bias)], build)
 
 
 def residual_block(x, block, out=None):
@@ -242,20 +221,13 @@ def residual_block(x, block, out=None):
     if not w1.is_cuda or w1.device != x.device:
         raise RuntimeError("residual_block: the block must be on the GPU of `x` (there is no CPU fallback in batrack_amd)")
     F, ho, wo = x.shape[0], (x.shape[2] - 1) // stride + 1, (x.shape[3] - 1) // stride + 1
-    if out is None:
-        out = torch.empty(F, c_out, ho, wo, dtype=torch.float32, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-              and tuple(out.shape) == (F, c_out, ho, wo) and out.device == x.device):
-        raise RuntimeError(f"residual_block: `out` must be a contiguous float32 [F, {c_out}, {ho}, {wo}] on the GPU of `x`")
+    out = out_tensor(out, (F, c_out, ho, wo), x.device, "residual_block", f"a contiguous float32 [F, {c_out}, {ho}, {wo}] on the GPU of `x`")
     ops = _lib.torch_ops()
     if ops is not None:
         ops.res_block(x, w1, b1, w2, b2, wd, bd, stride, out)
         return out
     L = _lib.lib()
-    nbytes = L.bt_res_block_workspace_bytes(F, c_out, x.shape[2], x.shape[3], stride)
-    if nbytes == 0:
-        raise RuntimeError("residual_block: " + _lib.ERRORS[_lib.BT_EUNSUPPORTED])
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)           # needs no initialisation
+    ws = scratch(L.bt_res_block_workspace_bytes(F, c_out, x.shape[2], x.shape[3], stride), x.device, "residual_block")
     blk = _lib.ResBlock(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), wd.data_ptr() if stride == 2 else None,
                         bd.data_ptr() if stride == 2 else None, c_in, c_out, stride)
     lx = _level(x)
@@ -277,10 +249,9 @@ def pack_stem_weights(conv1_weight):
 
 
 def _stem_conv_refusal(conv1):
-    if not isinstance(conv1, torch.nn.Conv2d):
-        return f"conv1 must be a Conv2d, not {type(conv1).__name__}"
-    if not _conv_is(conv1, 7, 3, ((2, 2),)):
-        return "conv1 must be 7 x 7 with stride 2, padding 3 (zeros), a bias, no dilation and one group"
+    why = _conv_refusal(conv1, 7, 3, ((2, 2),))
+    if why is not None:                  # a stand-in that is no convolution is named; anything else gets the stem's one sentence
+        return "conv1 " + (why if "Conv2d" in why else "must be 7 x 7 with stride 2, padding 3 (zeros), a bias, no dilation and one group")
     if conv1.in_channels != CIMG or conv1.out_channels != CSTEM:
         return f"conv1 must go from {CIMG} to {CSTEM} channels, not {conv1.in_channels} -> {conv1.out_channels}"
     return None
@@ -293,12 +264,9 @@ def stem_refusal(enc):
     if why is not None:
         return why
     norm1, relu1 = getattr(enc, "norm1", None), getattr(enc, "relu1", None)
-    if not isinstance(norm1, torch.nn.InstanceNorm2d):
-        return f"norm1 must be an InstanceNorm2d (norm_fn \"instance\"), not {type(norm1).__name__}"
-    if not _plain_instance_norm(norm1):
-        return "norm1 must be an InstanceNorm2d without affine parameters or running statistics"
-    if abs(float(norm1.eps) - 1e-5) > 1e-12:
-        return f"norm1's eps must be 1e-5, not {norm1.eps}"
+    why = _norm_refusal(norm1)
+    if why is not None:
+        return "norm1" + why
     if not isinstance(relu1, torch.nn.ReLU):
         return f"relu1 must be an nn.ReLU, not {type(relu1).__name__}"
     return None
@@ -312,13 +280,7 @@ def packed_stem(conv1):
     why = _stem_conv_refusal(conv1)
     if why is not None:
         raise RuntimeError("encoder_stem: " + why)
-    ts = (conv1.weight, conv1.bias)
-    key = tuple(v for t in ts for v in (t.data_ptr(), t._version)) + (str(conv1.weight.device),)
-    hit = _packed_stems.get(conv1)
-    if hit is None or hit[0] != key:
-        hit = (key, (pack_stem_weights(conv1.weight), conv1.bias.detach().float().contiguous()))
-        _packed_stems[conv1] = hit
-    return hit[1]
+    return cached(_packed_stems, conv1, (conv1.weight, conv1.bias), lambda: (pack_stem_weights(conv1.weight), bias_of(conv1)))
 
 
 def encoder_stem(x, conv1, out=None):
@@ -331,20 +293,13 @@ def encoder_stem(x, conv1, out=None):
     if not w.is_cuda or w.device != x.device:
         raise RuntimeError("encoder_stem: conv1 must be on the GPU of `x` (there is no CPU fallback in batrack_amd)")
     F, ho, wo = x.shape[0], (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1
-    if out is None:
-        out = torch.empty(F, CSTEM, ho, wo, dtype=torch.float32, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-              and tuple(out.shape) == (F, CSTEM, ho, wo) and out.device == x.device):
-        raise RuntimeError(f"encoder_stem: `out` must be a contiguous float32 [F, {CSTEM}, {ho}, {wo}] on the GPU of `x`")
+    out = out_tensor(out, (F, CSTEM, ho, wo), x.device, "encoder_stem", f"a contiguous float32 [F, {CSTEM}, {ho}, {wo}] on the GPU of `x`")
     ops = _lib.torch_ops()
     if ops is not None:
         ops.encoder_stem(x, w, b, out)
         return out
     L = _lib.lib()
-    nbytes = L.bt_encoder_stem_workspace_bytes(F, x.shape[2], x.shape[3])
-    if nbytes == 0:
-        raise RuntimeError("encoder_stem: " + _lib.ERRORS[_lib.BT_EUNSUPPORTED])
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)           # needs no initialisation
+    ws = scratch(L.bt_encoder_stem_workspace_bytes(F, x.shape[2], x.shape[3]), x.device, "encoder_stem")
     lx = _level(x)
     _lib.check(L.bt_encoder_stem(ctypes.byref(lx), w.data_ptr(), b.data_ptr(), CSTEM, F, ws.data_ptr(), out.data_ptr(),
                                  torch.cuda.current_stream(x.device).cuda_stream), "bt_encoder_stem")
@@ -377,10 +332,9 @@ def forward(self, x):
         raise RuntimeError("encoder.forward: the shallow encoder (three levels, a 1 x 1 conv2) is not supported")
     if getattr(self, "norm_fn", None) != "instance":
         raise RuntimeError(f"encoder.forward: norm_fn must be \"instance\", not {getattr(self, 'norm_fn', None)!r}")
-    if not _plain_instance_norm(self.norm2):
-        raise RuntimeError("encoder.forward: norm2 must be an InstanceNorm2d without affine parameters or running statistics")
-    if abs(float(self.norm2.eps) - 1e-5) > 1e-12:
-        raise RuntimeError(f"encoder.forward: norm2's eps must be 1e-5, not {self.norm2.eps}")
+    why = _norm_refusal(self.norm2)
+    if why is not None:
+        raise RuntimeError("encoder.forward: norm2" + why)
     if self.training and getattr(self, "dropout", None) is not None:
         raise RuntimeError("encoder.forward: inference only (a training encoder with dropout is not supported)")
     _gpu("x", x, "encoder.forward")

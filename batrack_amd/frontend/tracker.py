@@ -26,18 +26,10 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._conv import KCHUNK, _gpu, bias_of, cached, out_tensor, repack3x3  # noqa: F401  (KCHUNK stays a name of this module)
 
 C = 128                      # BT_WINDOW_C (`latent_dim`)
 EMB = 63                     # BT_WINDOW_EMB: Embedder_Fourier(3, N_freqs=10, include_input=True)
-KCHUNK = 8                   # BT_WINDOW_KCHUNK
-
-
-def _gpu(name, t, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what}: `{name}` must be a tensor on the GPU (there is no CPU fallback in batrack_amd)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what}: `{name}` must be float32")
-    return t.detach()
 
 
 def _stream(t):
@@ -89,9 +81,8 @@ def pack_weights(weight):
     channel 191.  A permutation of the weights (any device)."""
     if tuple(weight.shape) != (C, C + EMB, 3, 3):
         raise RuntimeError(f"embed_conv: the convolution must be 3 x 3 from {C + EMB} to {C} channels, not {tuple(weight.shape)}")
-    w = weight.detach().float().permute(1, 2, 3, 0).reshape(C + EMB, 9, C)
-    w = torch.cat([w, w.new_zeros(1, 9, C)], 0)
-    return w.reshape((C + EMB + 1) // KCHUNK, KCHUNK, 9, C).permute(0, 2, 1, 3).contiguous()
+    w = weight.detach().float()
+    return repack3x3(torch.cat([w, w.new_zeros(C, 1, 3, 3)], 1))
 
 
 _packed = weakref.WeakKeyDictionary()        # conv -> (key, packed weight, bias)
@@ -106,12 +97,7 @@ def packed_conv(conv):
     if tuple(conv.padding) != (1, 1) or tuple(conv.stride) != (1, 1) or tuple(conv.dilation) != (1, 1) or conv.groups != 1 \
             or getattr(conv, "padding_mode", "zeros") != "zeros":
         raise RuntimeError("embed_conv: the convolution must have padding 1 (zeros), stride 1, no dilation and one group")
-    key = (w.data_ptr(), w._version, b.data_ptr(), b._version, str(w.device))
-    hit = _packed.get(conv)
-    if hit is None or hit[0] != key:
-        hit = (key, pack_weights(w), b.detach().float().contiguous())
-        _packed[conv] = hit
-    return hit[1], hit[2]
+    return cached(_packed, conv, (w, b), lambda: (pack_weights(w), bias_of(conv)))
 
 
 def freq_table(freqs, device):
@@ -143,11 +129,8 @@ def embed_conv(fnet_maps, dmaps, zrange, frame0, conv, freqs, out=None):
     if not wp.is_cuda or wp.device != fnet_maps.device:
         raise RuntimeError("embed_conv: the convolution must be on the GPU of the maps (there is no CPU fallback in batrack_amd)")
     ft = freq_table(freqs, fnet_maps.device)
-    if out is None:
-        out = torch.empty(F, C, h, w, dtype=torch.float32, device=fnet_maps.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-              and tuple(out.shape) == (F, C, h, w)):
-        raise RuntimeError(f"embed_conv: `out` must be a contiguous float32 [F, {C}, h, w] on the GPU")
+    # as lenient as it was: an `out` on another GPU than the maps is not refused here
+    out = out_tensor(out, (F, C, h, w), fnet_maps.device, "embed_conv", f"a contiguous float32 [F, {C}, h, w] on the GPU", same_device=False)
     zrange = zrange.contiguous()
     ops = _lib.torch_ops()
     if ops is not None:

@@ -217,7 +217,8 @@ def test_symbols_are_exported_and_sources_listed():
         assert f"encoder.{name}" in batrack_amd.frontend.__doc__, name
     ops = _lib.torch_ops(strict=True)
     assert str(ops.encoder_stem.default._schema) == "batrack_hip::encoder_stem(Tensor x, Tensor w, Tensor b, Tensor(a!) out) -> ()"
-    src = open(os.path.join(_lib.CSRC, "encoder_stem.hip")).read()
+    assert "conv_stats.hip" in _lib.SOURCES                        # the statistics kernel, shared with the trunk
+    src = open(os.path.join(_lib.CSRC, "encoder_stem.hip")).read() + open(os.path.join(_lib.CSRC, "conv_stats.hip")).read()
     assert "atomic" not in src                                     # no atomics of any kind
     assert "tile_store_stats<ST_NT, true" in src and "tile_order_stats(" in src and "tile_flush<ST_NT>" in src      # the shared tile, not a copy
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """sha256 digests of everything the implicit-GEMM convolution kernels of csrc/conv_tile.hpp write (bt_embed_conv,
-bt_encoder_head, bt_res_block), for comparing two builds of the library bit for bit -> profiles/r27_conv_tile.txt.
+bt_encoder_head, bt_res_block, bt_encoder_stem), for comparing two builds of the library bit for bit -> profiles/r27_conv_tile.txt.
 
 The library is the one batrack_amd._lib loads: BT_LIB_PATH names a measurement build (the parent's, built from a git worktree
 into _var/parent/), nothing the tree's own.  Every call goes through ctypes to the C ABI on seeded inputs; the packed weights
-are seeded values in the packed shapes.  For the head and the block the workspace is filled with zero bytes first and its
+are seeded values in the packed shapes.  For the head, the block and the stem the workspace is filled with zero bytes first and its
 defined parts are digested too — the raw maps, the per-tile partials, the mean / rstd arrays — so that a sum whose order
 changed is seen even where the output happens not to move.
 
@@ -18,6 +18,8 @@ Cases, the smallest that reach every path and one workload shape each:
               more at the first); 96 x 128 from 192 x 256, 96 x 128, 48 x 64, 24 x 32
   block       the six (c_in, c_out, stride) shapes of the trunk at 2 x c_in x 11 x 19; 64 -> 64 stride 1 at 9 x 17, 64 -> 96 stride 2
               at 17 x 33, both on a 1 x 1 map; 64 -> 64 stride 1 at 1 x 64 x 192 x 256 and 128 -> 128 stride 1 at 2 x 128 x 24 x 32
+  stem        2 frames of 3 x 1 x 1; 3 x 16 x 64 (two tiles, fewer than the three a workgroup takes, float4 rows); 3 x 31 x 67 (six
+              tiles); 3 x 33 x 65 (nine tiles, 33 columns: scalar stores and k_stem_norm<1>); one frame of 3 x 384 x 512
 """
 import argparse
 import ctypes
@@ -36,6 +38,8 @@ HEAD_CASES = ((2, (1, 1), None), (2, (9, 17), None), (2, (11, 12), None), (2, (9
 SHAPES = ((64, 64, 1), (64, 96, 2), (96, 96, 1), (96, 128, 2), (128, 128, 1), (128, 128, 2))
 BLOCK_CASES = tuple((2, ci, co, s, 11, 19) for ci, co, s in SHAPES) + (
     (2, 64, 64, 1, 9, 17), (2, 64, 96, 2, 17, 33), (2, 64, 64, 1, 1, 1), (2, 64, 96, 2, 1, 1), (1, 64, 64, 1, 192, 256), (2, 128, 128, 1, 24, 32))
+CIMG, CSTEM = 3, 64
+STEM_CASES = ((2, 1, 1), (2, 16, 64), (2, 31, 67), (2, 33, 65), (1, 384, 512))
 
 
 def compare(a, b):
@@ -129,6 +133,20 @@ def main():
         sha(f"{key} out", out)
         parts(key, ws, (("raw maps", torch.float32, maps * F * co * ho * wo), ("partials", torch.float64, maps * F * tiles(ho, wo) * co * 2),
                         ("mean, rstd", torch.float32, maps * F * co * 2)))
+
+    for k, (F, h, w) in enumerate(STEM_CASES):
+        x = rnd(600 + k, F, CIMG, h, w)
+        wp, bias = rnd(650 + k, 7, CIMG, 8, CSTEM, scale=0.1), rnd(700 + k, CSTEM, scale=0.3)
+        wp[:, :, 7, :] = 0.0                                           # the eighth kx is a zero weight
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        ws = zeros_ws(L.bt_encoder_stem_workspace_bytes(F, h, w))
+        out = torch.zeros(F, CSTEM, ho, wo, device=DEV)
+        lx = _lib.EncoderLevel(x.data_ptr(), *x.shape[1:], *x.stride())
+        rc = L.bt_encoder_stem(ctypes.byref(lx), wp.data_ptr(), bias.data_ptr(), CSTEM, F, ws.data_ptr(), out.data_ptr(), st())
+        assert rc == _lib.BT_OK, rc
+        key = f"stem {F} x {CIMG} x {h} x {w}"
+        sha(f"{key} out", out)
+        parts(key, ws, (("partials", torch.float64, F * tiles(ho, wo) * CSTEM * 2), ("mean, rstd", torch.float32, F * CSTEM * 2)))
 
     with open(args.out, "w") as fh:
         json.dump({"library": _lib.LIB_PATH, "device": torch.cuda.get_device_name(0), "digests": dig}, fh, indent=1)

@@ -140,7 +140,7 @@ def trunk_trace_db(args):
     import sqlite3
     import encoder_trunk_util as T
     cur = sqlite3.connect(args.trunk_trace_db).cursor()
-    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_res_%' order by start").fetchall()
+    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_res_%' or name like '%k_conv_stats%' order by start").fetchall()
     per_call = len(T.BLOCKS) * len(LAUNCHES)
     with open(args.out, "a") as fh:
         fh.write(f"kernel time, rocprofv3 --kernel-trace --stats in a run of its own ({TRACE_CALLS} trunks per shape, the first {TRACE_SKIP} left out): "
@@ -243,7 +243,7 @@ def trunk_main(args):
 
 
 # -------------------------------------------------------------------------------------------------------------- the stem
-STEM_LAUNCHES = ("k_stem_conv", "k_stem_stats", "k_stem_norm")  # bt_encoder_stem's three launches, in order
+STEM_LAUNCHES = ("k_stem_conv", "k_conv_stats", "k_stem_norm")  # bt_encoder_stem's three launches, in order
 STEM_K, STEM_K_PADDED = 147, 168
 
 
@@ -269,7 +269,7 @@ def stem_trace():
 def stem_trace_db(args):
     import sqlite3
     cur = sqlite3.connect(args.stem_trace_db).cursor()
-    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_stem_%' order by start").fetchall()
+    rows = cur.execute("select name, end - start, vgpr_count, accum_vgpr_count, lds_size from kernels where name like '%k_stem_%' or name like '%k_conv_stats%' order by start").fetchall()
     per_call = len(STEM_LAUNCHES)
     with open(args.out) as fh:
         lines = fh.read().splitlines()
