@@ -8,15 +8,15 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "window_fmaps.hip", "conv_stats.hip", "encoder_head.hip", "encoder_trunk.hip", "encoder_stem.hip"]
-HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "plan_host.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", "ba_solve_update.hpp", "conv_tile.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "window_fmaps.hip", "conv_stats.hip", "encoder_head.hip", "encoder_trunk.hip", "encoder_stem.hip", "video_prep.hip"]
+HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "plan_host.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", "ba_solve_update.hpp", "conv_tile.hpp", "minmax_reduce.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
            os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h"),
            os.path.join("..", "..", "include", "batrack_patches.h"), os.path.join("..", "..", "include", "batrack_track.h"),
            os.path.join("..", "..", "include", "batrack_attn.h"), os.path.join("..", "..", "include", "batrack_window.h"),
-           os.path.join("..", "..", "include", "batrack_encoder.h")]
+           os.path.join("..", "..", "include", "batrack_encoder.h"), os.path.join("..", "..", "include", "batrack_video.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 
@@ -39,7 +39,8 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
                            "offset or element count above 2^31 - 1; residual block: channels outside 64 / 96 / 128, a stride other than 1 or 2, stride 1 "
                            "with c_in != c_out, more than 65535 frames, or a size, stride, offset or element count above 2^31 - 1; "
                            "encoder stem: channel counts other than 3 -> 64, more than 65535 frames, or a size, stride, offset, element or tile "
-                           "count above 2^31 - 1)"}
+                           "count above 2^31 - 1; "
+                           "frame preparation: a size, a stride, an input's element count or offset, or F * 4 * oh * ow above 2^31 - 1)"}
 LOSS = {"trivial": 0, "huber": 1, "cauchy": 2}
 
 
@@ -388,6 +389,10 @@ def lib():
     L.bt_encoder_stem_workspace_bytes.argtypes = [i64, i64, i64]
     L.bt_encoder_stem.restype = i32
     L.bt_encoder_stem.argtypes = [ctypes.POINTER(EncoderLevel), vp, vp, i64, i64, vp, vp, vp]
+    L.bt_frame_prep_workspace_bytes.restype = ctypes.c_size_t
+    L.bt_frame_prep_workspace_bytes.argtypes = [i64, i64, i64]
+    L.bt_frame_prep.restype = i32
+    L.bt_frame_prep.argtypes = [vp, i32] + [i64] * 4 + [vp] + [i64] * 3 + [i64] * 5 + [i32, i32, vp, vp, vp, vp]
     L.bt_patchify.restype = i32
     L.bt_patchify.argtypes = [vp, i64, i64, i64, i64, vp, i64, i32, i32, vp, vp]
     _lib = L

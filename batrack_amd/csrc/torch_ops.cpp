@@ -72,6 +72,12 @@
 //       c_out]; wd [c_in, c_out] and bd exactly when stride is 2; out [F, c_out, ho, wo] contiguous
 //   batrack_hip::encoder_stem(Tensor x, Tensor w, Tensor b, Tensor(a!) out) -> ()
 //       bt_encoder_stem (include/batrack_encoder.h): x [F, 3, h, w], any strides; w [7, 3, 8, 64]; out [F, 64, ho, wo] contiguous
+//   batrack_hip::frame_prep(Tensor image, Tensor depth, bool normalise, bool use_log_depth, Tensor(a!) workspace, Tensor(b!) rgbd,
+//                           Tensor(c!) drange) -> ()
+//       bt_frame_prep (include/batrack_video.h): image [F, 3, H, W] uint8 or float32, any strides (a permuted HWC view is read in
+//       place); depth [F, H, W] float32, any strides; workspace int32, at least bt_frame_prep_workspace_bytes(F, oh, ow) bytes, its
+//       tickets zero (the kernel leaves them zero: one workspace serves every call of a stream); rgbd [F, 4, oh, ow] contiguous, whose
+//       oh and ow are the output size; drange [F, 2].  One launch, nothing allocated.
 // Built by batrack_amd/_lib.py:build() into batrack_amd/lib/libbatrack_torch.so (g++, host code only).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -87,6 +93,7 @@
 #include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
 #include "../../include/batrack_track.h"
+#include "../../include/batrack_video.h"
 #include "../../include/batrack_window.h"
 
 namespace {
@@ -603,6 +610,32 @@ void encoder_stem(const at::Tensor &x, const at::Tensor &w, const at::Tensor &b,
     TORCH_CHECK(rc == BT_OK, op, "bt_encoder_stem failed with status ", rc);
 }
 
+void frame_prep(const at::Tensor &image, const at::Tensor &depth, bool normalise, bool use_log_depth, at::Tensor workspace, at::Tensor rgbd,
+                at::Tensor drange) {
+    const char *op = "batrack_hip::frame_prep: ";
+    all_f32(op, {&depth, &rgbd, &drange});
+    TORCH_CHECK(image.is_cuda() && image.device() == depth.device() && (image.scalar_type() == at::kByte || image.scalar_type() == at::kFloat),
+                op, "image must be uint8 or float32 on the GPU of the depth (no CPU fallback)");
+    TORCH_CHECK(image.dim() == 4 && image.size(1) == 3 && depth.dim() == 3 && depth.size(0) == image.size(0) && depth.size(1) == image.size(2)
+                && depth.size(2) == image.size(3) && image.size(2) >= 1 && image.size(3) >= 1, op,
+                "image must be [F, 3, H, W] and depth [F, H, W], H and W at least 1");
+    const int64_t F = image.size(0), H = image.size(2), W = image.size(3);
+    TORCH_CHECK(rgbd.dim() == 4 && rgbd.is_contiguous() && rgbd.size(0) == F && rgbd.size(1) == 4 && rgbd.size(2) >= 1 && rgbd.size(3) >= 1
+                && drange.dim() == 2 && drange.is_contiguous() && drange.size(0) == F && drange.size(1) == 2, op,
+                "rgbd must be a contiguous [F, 4, oh, ow] and drange a contiguous [F, 2]");
+    if (F == 0) return;
+    const int64_t oh = rgbd.size(2), ow = rgbd.size(3);
+    const size_t bytes = bt_frame_prep_workspace_bytes(F, oh, ow);
+    TORCH_CHECK(bytes > 0, op, "F * 4 * oh * ow must not pass 2^31 - 1");
+    TORCH_CHECK(workspace.is_cuda() && workspace.device() == depth.device() && workspace.scalar_type() == at::kInt && workspace.is_contiguous()
+                && (size_t)workspace.numel() * 4 >= bytes, op, "workspace must be a contiguous int32 tensor of at least ", bytes, " bytes on the GPU of the frames");
+    const int rc = bt_frame_prep(image.data_ptr(), image.scalar_type() == at::kByte ? 1 : 0, image.stride(0), image.stride(1), image.stride(2),
+                                 image.stride(3), depth.data_ptr<float>(), depth.stride(0), depth.stride(1), depth.stride(2), F, H, W, oh, ow,
+                                 normalise ? 1 : 0, use_log_depth ? 1 : 0, workspace.data_ptr(), rgbd.data_ptr<float>(), drange.data_ptr<float>(),
+                                 c10::hip::getCurrentHIPStream(depth.device().index()).stream());
+    TORCH_CHECK(rc == BT_OK, op, "bt_frame_prep failed with status ", rc);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(batrack_hip, m) {
@@ -640,4 +673,6 @@ TORCH_LIBRARY(batrack_hip, m) {
           "Tensor(a!) out) -> ()", &encoder_head);
     m.def("res_block(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor? wd, Tensor? bd, int stride, Tensor(a!) out) -> ()", &res_block);
     m.def("encoder_stem(Tensor x, Tensor w, Tensor b, Tensor(a!) out) -> ()", &encoder_stem);
+    m.def("frame_prep(Tensor image, Tensor depth, bool normalise, bool use_log_depth, Tensor(a!) workspace, Tensor(b!) rgbd, "
+          "Tensor(c!) drange) -> ()", &frame_prep);
 }

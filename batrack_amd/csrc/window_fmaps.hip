@@ -1,10 +1,8 @@
 // window_fmaps.hip — the tracker's window preparation (include/batrack_window.h holds the specification): k_depth_range,
 // k_window_depth, k_embed_conv, k_feat_sample.
 //
-// k_depth_range and k_window_depth end in a minimum and a maximum over everything they read.  Each block reduces its own
-// share and leaves the pair in the workspace; a ticket tells the last block to finish that it is the last, and it reduces the
-// pairs and puts the ticket back to zero.  One launch, no atomics on the values, and min / max do not depend on the order.
-// A NaN among the values they select makes both results NaN, as torch's min() and max() do.
+// k_depth_range and k_window_depth end in a minimum and a maximum over everything they read: the two-stage reduction of
+// csrc/minmax_reduce.hpp (block pairs in the workspace, a ticket, the last block reduces them), shared with k_frame_prep.
 //
 // k_embed_conv is the 3 x 3 convolution 191 -> 128 as an implicit GEMM on v_mfma_f32_16x16x4_f32 with the tile of
 // csrc/conv_tile.hpp (stride 1, all 128 columns): K = 9 taps x 192 input channels (191 and a zero weight).
@@ -23,11 +21,12 @@
 #include "../../include/batrack_ba.h"
 #include "../../include/batrack_window.h"
 #include "conv_tile.hpp"
+#include "minmax_reduce.hpp"
 #include "sample_taps.hpp"
 
 namespace bt {
 
-constexpr int WD_THREADS = 256, WD_MAX_BLOCKS = 1024, WD_PER_THREAD = 8;
+constexpr int WD_MAX_BLOCKS = 1024, WD_PER_THREAD = 8;         // WD_THREADS: minmax_reduce.hpp
 constexpr size_t WD_WORKSPACE = (size_t)2 * WD_MAX_BLOCKS * sizeof(float) + sizeof(unsigned);
 
 constexpr int EC_HW = ConvGeom<1>::HW, EC_HALO = ConvGeom<1>::HALO, EC_PL = ConvGeom<1>::PL;
@@ -35,51 +34,6 @@ constexpr int EC_CHUNKS = (BT_WINDOW_C + BT_WINDOW_EMB + 1) / CT_KC, EC_NT = BT_
 static_assert(CT_KC == BT_WINDOW_KCHUNK && EC_CHUNKS * CT_KC == 192, "the packed weights' chunks");
 
 constexpr int FS_THREADS = BT_WINDOW_C;
-
-__device__ __forceinline__ float depth_process(float d, int use_log) {
-    if (!use_log) return d;
-    return logf(d < 1e-3f ? 1e-3f : d);                        // clamp(min=1e-3): a NaN stays NaN
-}
-
-// torch's min / max: a NaN on either side is the result
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
-__device__ __forceinline__ void nan_minmax(float v, float &mn, float &mx) { mn = nan_min(mn, v); mx = nan_max(mx, v); }
-
-// the block's (mn, mx) -> part[block]; the last block to arrive reduces part[0 .. gridDim.x) into out[0 .. 1]
-__device__ void minmax_finish(float mn, float mx, float *part, unsigned *ticket, float *out) {
-    __shared__ float s_mn[WD_THREADS / 64], s_mx[WD_THREADS / 64];
-    __shared__ unsigned s_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto block_reduce = [&](float &a, float &b) {
-        for (int o = 32; o; o >>= 1) { a = nan_min(a, __shfl_xor(a, o)); b = nan_max(b, __shfl_xor(b, o)); }
-        __syncthreads();
-        if (lane == 0) { s_mn[wave] = a; s_mx[wave] = b; }
-        __syncthreads();
-        a = s_mn[0]; b = s_mx[0];
-        for (int i = 1; i < WD_THREADS / 64; ++i) { a = nan_min(a, s_mn[i]); b = nan_max(b, s_mx[i]); }
-    };
-    block_reduce(mn, mx);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(part + 2 * blockIdx.x, mn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(part + 2 * blockIdx.x + 1, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        s_last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    mn = INFINITY; mx = -INFINITY;
-    for (unsigned i = threadIdx.x; i < gridDim.x; i += WD_THREADS) {
-        mn = nan_min(mn, __hip_atomic_load(part + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        mx = nan_max(mx, __hip_atomic_load(part + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-    block_reduce(mn, mx);
-    if (threadIdx.x == 0) {
-        out[0] = mn; out[1] = mx;
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 
 // --------------------------------------------------------------------------------------------------------- k_depth_range
 __global__ __launch_bounds__(WD_THREADS) void k_depth_range(const float *__restrict__ depth, int H, int W, long long st, long long sy,
@@ -90,11 +44,9 @@ __global__ __launch_bounds__(WD_THREADS) void k_depth_range(const float *__restr
         const long long row = i / W, t = row / H;
         const int x = (int)(i - row * W), y = (int)(row - t * H);
         const float d = depth[t * st + y * sy + x * sx];
-        if (use_log || d > 0.01f) {
-            nan_minmax(depth_process(d, use_log), mn, mx);       // (d > 0.01 is false for a NaN: only the log form can meet one)
-        }
+        depth_range_fold(d, use_log, mn, mx);                    // (d > 0.01 is false for a NaN: only the log form can meet one)
     }
-    minmax_finish(mn, mx, part, ticket, out);
+    minmax_finish(mn, mx, part, ticket, out, blockIdx.x, gridDim.x);
 }
 
 // -------------------------------------------------------------------------------------------------------- k_window_depth
@@ -112,7 +64,7 @@ __global__ __launch_bounds__(WD_THREADS) void k_window_depth(const float *__rest
         dmaps[i] = v;
         nan_minmax(v, mn, mx);
     }
-    minmax_finish(mn, mx, part, ticket, zrange);
+    minmax_finish(mn, mx, part, ticket, zrange, blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------- k_embed_conv

@@ -15,6 +15,8 @@ include/batrack_window.h, which holds the specification).
                                                                                  reference's signature and return tuple;
                                                                                  `self.fnet` and `self.forward_iteration` are
                                                                                  called as they are
+    forward_frames(self, frames, queries, iters=4)                               the single-window call on a `video.WindowFrames`:
+                                                                                 the same loop on frames prepared and encoded once
 
 Inference only (no autograd through the kernels), float32, GPU tensors only; no CPU fallback.  B = 1, 128 channels.
 
@@ -173,22 +175,74 @@ def _div_rn(a, b):
     return (a.double() / torch.full((), float(np.float32(b)), dtype=torch.float64, device=a.device)).float()
 
 
+def _checked(self, what):
+    """(S, stride, use_log_depth) of the tracker `self`, or a RuntimeError naming what `what` cannot run on."""
+    S, stride = int(self.S), int(self.stride)
+    if S % 2 or stride < 1 or stride & (stride - 1):
+        raise RuntimeError(f"{what}: the window length must be even and the stride a power of two")
+    if int(self.latent_dim) != C:
+        raise RuntimeError(f"{what}: latent_dim must be {C}")
+    return S, stride, bool(getattr(self, "use_log_depth", False))
+
+
 def forward(self, rgbds, queries, iters=4, feat_init=None, is_train=False):
     if is_train:
         raise RuntimeError("tracker.forward: inference only (is_train=True is not supported)")
     _gpu("rgbds", rgbds, "tracker.forward")
     _gpu("queries", queries, "tracker.forward")
     B, T, C_img, H, W = rgbds.shape
-    B, N, __ = queries.shape
-    device = rgbds.device
-    if B != 1:
+    if queries.shape[0] != 1:                                               # (the queries' batch, as before)
         raise RuntimeError("tracker.forward: B must be 1")
-    S, stride = int(self.S), int(self.stride)
-    if S % 2 or stride < 1 or stride & (stride - 1):
-        raise RuntimeError("tracker.forward: the window length must be even and the stride a power of two")
-    if int(self.latent_dim) != C:
-        raise RuntimeError(f"tracker.forward: latent_dim must be {C}")
-    use_log = bool(getattr(self, "use_log_depth", False))
+    S, stride, use_log = _checked(self, "tracker.forward")
+
+    # the caller's rgbds, in place; the division goes through double, in chunks of frames that keep that temporary to 64 MB
+    step = max(1, (1 << 23) // max(1, 3 * H * W))
+    for t in range(0, T, step):
+        rgbds[:, t: t + step, :3] = 2 * _div_rn(rgbds[:, t: t + step, :3], 255.0) - 1.0
+    d_near, d_far = depth_range(rgbds[0, :, 3], use_log).tolist()           # the other read-back
+
+    def fnet_of(ind, lo, hi):
+        rgbs_ = rgbds[0, ind: ind + S, :3]
+        if rgbs_.shape[0] < S:                                              # a short last window repeats its last frame
+            rgbs_ = torch.cat([rgbs_, rgbs_[-1:].repeat(S - rgbs_.shape[0], 1, 1, 1)], dim=0)
+        return self.fnet(rgbs_[lo:hi])
+
+    return _windows(self, queries, iters, feat_init, T, H, W, d_near, d_far, lambda ind, S_local: rgbds[0, ind: ind + S_local, 3], fnet_of,
+                    "tracker.forward", (S, stride, use_log))
+
+
+def forward_frames(self, frames, queries, iters=4):
+    """The tracker's single-window call on a `video.WindowFrames`: `forward`'s tuple for the window's frames, with what each
+    frame's preparation and encoding cost paid once per frame and not once per call.  A window shorter than S repeats its last
+    frame (the maps and the depth are copied, not recomputed).  One host read: the depth range.
+
+    Bit-equal to `forward(self, rgbds, queries, iters)` on the same S frames — prepared by `video.prepare_frames(normalise=False)`
+    and padded as `get_window_trajs` pads them — whenever `frames.fnet` is `self.fnet` and a frame's maps do not depend on the
+    frames encoded with it."""
+    _gpu("queries", queries, "tracker.forward_frames")
+    if queries.shape[0] != 1:
+        raise RuntimeError("tracker.forward_frames: B must be 1")
+    S, stride, use_log = _checked(self, "tracker.forward_frames")
+    if int(frames.S) != S or bool(frames.use_log_depth) != use_log:
+        raise RuntimeError("tracker.forward_frames: the frames' window length and use_log_depth must be the tracker's")
+    rgbd, maps, drange = frames.window()
+    n = rgbd.shape[0]
+    if maps.shape[1] != C or tuple(maps.shape[2:]) != (rgbd.shape[2] // stride, rgbd.shape[3] // stride):
+        raise RuntimeError(f"tracker.forward_frames: the frames' maps must be [n, {C}, H / stride, W / stride], not {tuple(maps.shape)}")
+    if n < S:
+        maps = torch.cat([maps, maps[-1:].expand(S - n, -1, -1, -1)], dim=0)
+    d_near, d_far = drange.tolist()
+    return _windows(self, queries, iters, None, S, rgbd.shape[2], rgbd.shape[3], d_near, d_far, lambda ind, S_local: rgbd[:, 3],
+                    lambda ind, lo, hi: maps[lo:hi], "tracker.forward_frames", (S, stride, use_log))
+
+
+def _windows(self, queries, iters, feat_init, T, H, W, d_near, d_far, depth_of, fnet_of, what, checked):
+    """The window loop `forward` and `forward_frames` share, from the depth range on.  depth_of(ind, S_local) is the depth
+    [<= S_local, H, W] of the window that starts at frame `ind` (fewer frames: the last is repeated); fnet_of(ind, lo, hi) the
+    encoder's maps of that window's frames lo .. hi, its padding frames included."""
+    B, N, __ = queries.shape
+    device = queries.device
+    S, stride, use_log = checked                                            # of `_checked(self, what)`, by the caller
     half = S // 2
 
     first_positive_inds = queries[:, :, 0].long()
@@ -197,13 +251,8 @@ def forward(self, rgbds, queries, iters=4, feat_init=None, is_train=False):
     first_positive_sorted_inds = first_positive_inds[0][sort_inds]
     first_sorted_host = first_positive_sorted_inds.cpu().numpy()            # one read-back: the windows' track counts
 
-    # the caller's rgbds, in place; the division goes through double, in chunks of frames that keep that temporary to 64 MB
-    step = max(1, (1 << 23) // max(1, 3 * H * W))
-    for t in range(0, T, step):
-        rgbds[:, t: t + step, :3] = 2 * _div_rn(rgbds[:, t: t + step, :3], 255.0) - 1.0
-    d_near, d_far = depth_range(rgbds[0, :, 3], use_log).tolist()           # the other read-back
     if not (np.isfinite(d_near) and np.isfinite(d_far)):
-        raise RuntimeError("tracker.forward: the video has no depth above 0.01, or a NaN depth (use_log_depth)")
+        raise RuntimeError(f"{what}: the video has no depth above 0.01, or a NaN depth (use_log_depth)")
     self.d_near, self.d_far = d_near, d_far
     self.Dz = Dz = W // stride
     d_range = d_far - d_near
@@ -233,25 +282,22 @@ def forward(self, rgbds, queries, iters=4, feat_init=None, is_train=False):
     fmaps_ = None
     h, w = H // stride, W // stride
     while ind < T - half:
-        rgbs_ = rgbds[0, ind: ind + S, :3]
-        S_local = rgbs_.shape[0]
-        if S_local < S:                                                     # a short last window repeats its last frame
-            rgbs_ = torch.cat([rgbs_, rgbs_[-1:].repeat(S - S_local, 1, 1, 1)], dim=0)
-        dmaps_, zrange = window_depth(rgbds[0, ind: ind + S_local, 3], S, stride, d_near, d_far, Dz, use_log)
+        S_local = min(S, T - ind)
+        dmaps_, zrange = window_depth(depth_of(ind, S_local), S, stride, d_near, d_far, Dz, use_log)
 
         if self.Embed3D:
             freqs = self.embed3d.freq_bands
             if fmaps_ is None:
-                fmaps_ = embed_conv(self.fnet(rgbs_), dmaps_, zrange, 0, self.embedConv, freqs)
+                fmaps_ = embed_conv(fnet_of(ind, 0, S), dmaps_, zrange, 0, self.embedConv, freqs)
             else:                                                           # a slide: the old second half, and the new half convolved
                 window = torch.empty_like(fmaps_)
                 window[:half] = fmaps_[half:]
-                embed_conv(self.fnet(rgbs_[half:]), dmaps_, zrange, half, self.embedConv, freqs, out=window[half:])
+                embed_conv(fnet_of(ind, half, S), dmaps_, zrange, half, self.embedConv, freqs, out=window[half:])
                 fmaps_ = window
         elif fmaps_ is None:
-            fmaps_ = self.fnet(rgbs_)
+            fmaps_ = fnet_of(ind, 0, S)
         else:
-            fmaps_ = torch.cat([fmaps_[half:], self.fnet(rgbs_[half:])], dim=0)
+            fmaps_ = torch.cat([fmaps_[half:], fnet_of(ind, half, S)], dim=0)
 
         fmaps = fmaps_[:, :C].reshape(B, S, C, h, w)
         dmaps = dmaps_.reshape(B, S, 1, h, w)
