@@ -8,14 +8,15 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BT_LIB_PATH") or os.path.join(_HERE, "lib", "libbatrack_ba.so")   # BT_LIB_PATH: measurement builds only
-SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "window_fmaps.hip", "conv_stats.hip", "encoder_head.hip", "encoder_trunk.hip", "encoder_stem.hip", "video_prep.hip"]
+SOURCES = ["ba_tile.hip", "ba_pair.hip", "ba_solve.hip", "ba_xchg.hip", "ba_step.cpp", "ba_etile.hip", "ba_stream.hip", "ba_edge2.hip", "ba_edge2u.hip", "ba_dense.hip", "ba_loose.hip", "plan_pack.hip", "plan_device.hip", "ba_plan.cpp", "ba_plan_solver.cpp", "ba_api.cpp", "plan_shift.cpp", "se3_kernels.hip", "patchify_kernels.hip", "projective_kernels.hip", "world_tracks.hip", "ga_kernels.hip", "depth_eval.hip", "depth_align.hip", "mono_align.hip", "corr_lookup.hip", "observe.hip", "keyframe.hip", "patch_gen.hip", "track_iter.hip", "attention.hip", "rows_linear.hip", "window_fmaps.hip", "conv_stats.hip", "encoder_head.hip", "encoder_trunk.hip", "encoder_stem.hip", "video_prep.hip"]
 HEADERS = ["projective_edge.hpp", "ba_kernels.hpp", "ba_wave.hpp", "ba_plan.hpp", "ba_edge.hpp", "ba_update.hpp", "dev_cache.hpp", "plan_host.hpp", "ba_edge2.hpp", "probe.hpp", "radix_select.hpp", "sample_taps.hpp", "ba_solve_update.hpp", "conv_tile.hpp", "minmax_reduce.hpp", os.path.join("..", "..", "include", "batrack_ba.h"),
            os.path.join("..", "..", "include", "batrack_se3.h"), os.path.join("..", "..", "include", "batrack_patchify.h"),
            os.path.join("..", "..", "include", "batrack_projective.h"), os.path.join("..", "..", "include", "batrack_ga.h"),
            os.path.join("..", "..", "include", "batrack_depth.h"), os.path.join("..", "..", "include", "batrack_corr.h"),
            os.path.join("..", "..", "include", "batrack_observe.h"), os.path.join("..", "..", "include", "batrack_keyframe.h"),
            os.path.join("..", "..", "include", "batrack_patches.h"), os.path.join("..", "..", "include", "batrack_track.h"),
-           os.path.join("..", "..", "include", "batrack_attn.h"), os.path.join("..", "..", "include", "batrack_window.h"),
+           os.path.join("..", "..", "include", "batrack_attn.h"), os.path.join("..", "..", "include", "batrack_rows.h"),
+           os.path.join("..", "..", "include", "batrack_window.h"),
            os.path.join("..", "..", "include", "batrack_encoder.h"), os.path.join("..", "..", "include", "batrack_video.h")]
 # -fno-slp-vectorize: packed f32 pairs cost more register moves than the packed instructions save (measured on k_edge, round 4's kernel; k_edge2 writes its packed pairs out by hand)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
@@ -23,6 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 BT_OK, BT_EINVAL, BT_ENOMEM, BT_EHIP, BT_EUNSUPPORTED = 0, -1, -2, -3, -4
 BT_DEPTH_F32, BT_DEPTH_F64 = 0, 1                    # include/batrack_depth.h
 BT_IMAGE_U8, BT_IMAGE_F32 = 0, 1                     # include/batrack_patches.h
+BT_ROWS_PRECISION = {"f16x3": 0, "f16": 1}           # include/batrack_rows.h: BT_ROWS_F16X3, BT_ROWS_F16
 BT_PATCH_ROWS = {"reference": 0, "image": 1}
 ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "HIP runtime error",
           BT_EUNSUPPORTED: "unsupported size (bundle adjustment: n > 2048 free poses, or a track whose edges name more "
@@ -33,6 +35,7 @@ ERRORS = {BT_EINVAL: "invalid argument", BT_ENOMEM: "out of memory", BT_EHIP: "H
                            "window observations: a window of more than 64 frames, 2^24 or more scores, or window buffers of 2^31 or more slots; "
                            "patch generation: more than 1024 candidates per cell (8 * patches per cell), or an image side above 32768; "
                            "tracker iteration: more than 144 flow columns, more than 128 feature channels in the state update, or 2^31 - 16 or more tokens; "
+                           "rows_linear: a size or a row stride above 2^31 - 1, or more than 2^31 - 1 workgroups; "
                            "attention: a head size other than 48, a size, stride or row index above 2^31 - 1, or more than 2^24 - 1 workgroups; "
                            "tracker window: a channel count other than 128, or a size, stride or element count above 2^31 - 1; "
                            "encoder head: channel counts other than 64 / 96 / 128 / 128 -> 256 -> 128, more than 65535 frames, or a size, stride, "
@@ -367,6 +370,8 @@ def lib():
     L.bt_track_apply.argtypes = [vp] * 9 + [i64] * 3 + [f32] * 4 + [i32, vp, vp]
     L.bt_attention.restype = i32
     L.bt_attention.argtypes = [vp, i64, vp, i64] + [i64] * 6 + [f32, vp]
+    L.bt_rows_linear.restype = i32
+    L.bt_rows_linear.argtypes = [vp, i64, vp, vp, f32, vp, vp, i64, vp, i64, i64, i64, i64, i32, f32, i32, i32, vp]
     L.bt_window_workspace_bytes.restype = ctypes.c_size_t
     L.bt_window_workspace_bytes.argtypes = []
     L.bt_depth_range.restype = i32

@@ -54,6 +54,10 @@
 //       bt_attention (include/batrack_attn.h): qkv [rows, >= 3 * heads * 48] with unit last stride (the row stride is read from
 //       the tensor); token i of sequence b is row b * seq_stride + i * tok_stride -> [rows, heads * 48] (rows that no token
 //       addresses are left unwritten)
+//   batrack_hip::rows_linear(Tensor x, Tensor w_hi, Tensor w_lo, float inv_scale, Tensor? bias, float norm_eps, bool gelu,
+//                            Tensor? residual, Tensor(a!) out, int precision) -> ()
+//       bt_rows_linear (include/batrack_rows.h): x [rows, K] and out, residual [rows, Nout] with unit last stride (the row
+//       strides are read from the tensors); w_hi, w_lo [Nout, K] float16 contiguous; norm_eps < 0: no LayerNorm prologue
 //   batrack_hip::depth_range(Tensor depth, bool use_log_depth) -> Tensor
 //       bt_depth_range (include/batrack_window.h): depth [T, H, W], any strides (read in place) -> [2] (min, max) on the device
 //   batrack_hip::window_depth(Tensor depth, int S, int stride, float d_near, float d_range, float dz, bool use_log_depth) -> (Tensor, Tensor)
@@ -92,6 +96,7 @@
 #include "../../include/batrack_encoder.h"
 #include "../../include/batrack_observe.h"
 #include "../../include/batrack_projective.h"
+#include "../../include/batrack_rows.h"
 #include "../../include/batrack_track.h"
 #include "../../include/batrack_video.h"
 #include "../../include/batrack_window.h"
@@ -458,6 +463,47 @@ at::Tensor attention(const at::Tensor &qkv, int64_t heads, int64_t n_seq, int64_
     return out;
 }
 
+void rows_linear(const at::Tensor &x, const at::Tensor &w_hi, const at::Tensor &w_lo, double inv_scale, const c10::optional<at::Tensor> &bias,
+                 double norm_eps, bool gelu, const c10::optional<at::Tensor> &residual, at::Tensor out, int64_t precision) {
+    const char *op = "batrack_hip::rows_linear: ";
+    const float *px = f32(x, "x");
+    float *po = const_cast<float *>(f32(out, "out"));
+    auto rows_of = [&](const at::Tensor &t, int64_t cols, const char *what) {          // [rows, cols] with unit last stride -> row stride
+        TORCH_CHECK(t.dim() == 2 && t.size(0) == x.size(0) && t.size(1) == cols && (cols == 1 || t.stride(1) == 1)
+                    && (t.size(0) <= 1 || t.stride(0) >= cols) && t.device() == x.device(), op, "`", what, "` must be [rows, ", cols,
+                    "] with unit last stride, on the device of x");
+        return t.size(0) > 1 ? t.stride(0) : cols;
+    };
+    TORCH_CHECK(x.dim() == 2, op, "x must be [rows, K]");
+    const int64_t rows = x.size(0), K = x.size(1);
+    TORCH_CHECK(w_hi.is_cuda() && w_lo.is_cuda() && w_hi.scalar_type() == at::kHalf && w_lo.scalar_type() == at::kHalf && w_hi.dim() == 2
+                && w_hi.size(1) == K && w_lo.sizes() == w_hi.sizes() && w_hi.is_contiguous() && w_lo.is_contiguous()
+                && w_hi.device() == x.device() && w_lo.device() == x.device(), op,
+                "w_hi and w_lo must be [Nout, K] float16, contiguous, on the device of x (update_former.pack_linear)");
+    const int64_t Nout = w_hi.size(0);
+    TORCH_CHECK(K >= 8 && K % 8 == 0 && Nout >= 1, op, "K must be a multiple of 8 and Nout positive, got K = ", K, ", Nout = ", Nout);
+    const int64_t ldx = rows_of(x, K, "x"), ldo = rows_of(out, Nout, "out");
+    const float *pb = nullptr, *pr = nullptr;
+    int64_t ldr = 0;
+    if (bias.has_value()) {
+        pb = f32(*bias, "bias");
+        TORCH_CHECK(bias->dim() == 1 && bias->size(0) == Nout && bias->is_contiguous() && bias->device() == x.device(), op,
+                    "bias must be [Nout], contiguous, on the device of x");
+    }
+    if (residual.has_value()) {
+        pr = f32(*residual, "residual");
+        ldr = rows_of(*residual, Nout, "residual");
+    }
+    TORCH_CHECK(precision == BT_ROWS_F16X3 || precision == BT_ROWS_F16, op, "precision must be BT_ROWS_F16X3 or BT_ROWS_F16");
+    if (rows == 0) return;
+    const int rc = bt_rows_linear(px, ldx, w_hi.data_ptr(), w_lo.data_ptr(), (float)inv_scale, pb, pr, ldr, po, ldo, rows, K, Nout,
+                                  norm_eps >= 0 ? BT_ROWS_PRO_LAYERNORM : BT_ROWS_PRO_NONE, norm_eps >= 0 ? (float)norm_eps : 0.f,
+                                  gelu ? BT_ROWS_ACT_GELU_TANH : BT_ROWS_ACT_NONE, (int)precision,
+                                  c10::hip::getCurrentHIPStream(x.device().index()).stream());
+    TORCH_CHECK(rc != BT_EINVAL, op, "bt_rows_linear refused its arguments (out must not overlap x, nor residual unless it is residual)");
+    TORCH_CHECK(rc == BT_OK, op, "bt_rows_linear failed with status ", rc);
+}
+
 at::Tensor window_workspace(const at::Tensor &like) {          // zeroed: the ticket in its last word must be
     return at::zeros({(int64_t)((bt_window_workspace_bytes() + 3) / 4)}, like.options().dtype(at::kInt));
 }
@@ -663,6 +709,8 @@ TORCH_LIBRARY(batrack_hip, m) {
     m.def("track_apply(Tensor delta, Tensor gamma, Tensor beta, Tensor w_u, Tensor b_u, Tensor(a!) state, Tensor(b!) ffeats, "
           "Tensor? total, Tensor? dyn_mask, float stride, float dz, float d_range, float d_near, bool use_log_depth) -> Tensor", &track_apply);
     m.def("attention(Tensor qkv, int heads, int n_seq, int L, int seq_stride, int tok_stride, float scale) -> Tensor", &attention);
+    m.def("rows_linear(Tensor x, Tensor w_hi, Tensor w_lo, float inv_scale, Tensor? bias, float norm_eps, bool gelu, Tensor? residual, "
+          "Tensor(a!) out, int precision) -> ()", &rows_linear);
     m.def("depth_range(Tensor depth, bool use_log_depth) -> Tensor", &depth_range);
     m.def("window_depth(Tensor depth, int S, int stride, float d_near, float d_range, float dz, bool use_log_depth) -> (Tensor, Tensor)",
           &window_depth);

@@ -7,18 +7,35 @@ parts of a block are torch operations on those rows, and only the attention know
     attn_block(x [N S, C], blk, axis, N, S) -> [N S, C]       one AttnBlock; axis "time" or "space"
     forward(self, input_tensor [1, N, T, input_dim]) -> [1, N, T, output_dim]      the reference's signature and return
 
+The opt-in second route puts the row-wise parts on the f16 matrix pipe as well (batrack_amd/csrc/rows_linear.hip through
+include/batrack_rows.h): every Linear with what stands around it is one launch, float32 operands split into f16 pairs.
+
+    pack_linear(weight [Nout, K]) -> (w_hi, w_lo f16, inv_scale)                        the weight split, cached per Linear
+    rows_linear(x [rows, K], lin, *, norm_eps=None, gelu=False, residual=None, out=None, precision="f16x3") -> [rows, Nout]
+                                            residual + act((LayerNorm(x) . W^T) + bias)                          one launch
+    attn_block_rows(x, blk, axis, N, S, precision="f16x3") -> [N S, C]                  five launches
+    forward_rows(self, input_tensor, precision="f16x3") -> [1, N, T, output_dim]        62 launches for 6 + 6 blocks
+
+precision "f16x3" takes three products a K step and stays at float32 accuracy; "f16" takes one and has f16 accuracy.
+
 Inference only (inputs are detached, no autograd through the kernel), GPU tensors only; no CPU fallback.  B = 1, heads of 48.
 What it cannot do raises a RuntimeError that names the reason; there is no route to another path.
 
-`install()` makes the reference's `UpdateFormer` use `forward`; with track_iter.install() the two compose."""
+`install()` makes the reference's `UpdateFormer` use `forward`, `install(precision="f16x3")` makes it use `forward_rows`; with
+track_iter.install() the two compose."""
 import importlib
+import math
+import weakref
 
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from ._conv import cached
 
 HEAD_DIM = 48                # BT_ATTN_HEAD_DIM
+PRECISIONS = tuple(_lib.BT_ROWS_PRECISION)           # "f16x3", "f16"
+_packed = weakref.WeakKeyDictionary()                # Linear -> (key, (w_hi, w_lo, inv_scale, bias))
 
 
 def _gpu(name, t, what="update_former"):
@@ -114,11 +131,174 @@ def forward(self, input_tensor):
         return _linear(x, self.flow_head).reshape(B, N, T, -1)
 
 
-def install(module=None):
+# ------------------------------------------------------------------------------------- the rows on the f16 matrix pipe
+def pack_linear(weight):
+    """weight [Nout, K] -> (w_hi, w_lo, inv_scale): with s = 2^floor(log2(1 / max |W|)) clamped to [2^-14, 2^14] (1 for an
+    all-zero matrix; the maximum is over the finite entries), hi = f16(W s), lo = f16(W s - float(hi)), inv_scale = 1 / s.
+    Torch operations on the weight's device; off the hot path (rows_linear caches the result per Linear)."""
+    w = weight.detach().float()
+    if w.dim() != 2:
+        raise RuntimeError(f"pack_linear: the weight must be [Nout, K], got {tuple(w.shape)}")
+    finite = w[torch.isfinite(w)]
+    m = float(finite.abs().max()) if finite.numel() else 0.0
+    e = 0
+    if m != 0.0:
+        f, p = math.frexp(m)                         # m = f 2^p, 0.5 <= f < 1: floor(log2(1 / m)) without a rounded logarithm
+        e = min(14, max(-14, 1 - p if f == 0.5 else -p))
+    ws = w * 2.0 ** e
+    hi = ws.half()
+    lo = (ws - hi.float()).half()
+    return hi.contiguous(), lo.contiguous(), 2.0 ** -e
+
+
+def _packed_linear(lin):
+    w, b = lin.weight, lin.bias
+    if not w.is_cuda:
+        raise RuntimeError("rows_linear: the Linear must be on the GPU (there is no CPU fallback in batrack_amd)")
+
+    def build():
+        return pack_linear(w) + (None if b is None else b.detach().float().contiguous(),)
+    return cached(_packed, lin, (w,) if b is None else (w, b), build)
+
+
+def _precision(precision, what):
+    if precision not in _lib.BT_ROWS_PRECISION:
+        raise RuntimeError(f"{what}: unknown precision {precision!r}; it is one of {PRECISIONS}")
+    return _lib.BT_ROWS_PRECISION[precision]
+
+
+def _rows(name, t, cols, what):
+    """`t` as [rows, cols] float32 rows that the kernel can read in place (unit last stride), else a contiguous copy."""
+    t = _gpu(name, t, what)
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise RuntimeError(f"{what}: `{name}` must be [rows, {'K' if cols is None else cols}], got {tuple(t.shape)}")
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def rows_linear(x, lin, *, norm_eps=None, gelu=False, residual=None, out=None, precision="f16x3"):
+    """residual + act(LayerNorm(x) . lin.weight^T + lin.bias) on x [rows, K] in one launch (include/batrack_rows.h): the
+    LayerNorm (no affine parameters, eps `norm_eps`) when norm_eps is not None, tanh-GELU when `gelu`.  x, residual and out
+    are read and written in place through their row strides; out may be residual, and must not overlap x.  "In place" needs
+    a unit last stride and rows that do not overlap: an x or a residual laid out otherwise (a transposed view, say) is first
+    copied by torch with `.contiguous()`, one more pass that forward_rows never takes."""
+    what = "rows_linear"
+    prec = _precision(precision, what)
+    x = _rows("x", x, None, what)
+    w_hi, w_lo, inv_scale, bias = _packed_linear(lin)
+    rows, K = x.shape
+    Nout = w_hi.shape[0]
+    if K != w_hi.shape[1]:
+        raise RuntimeError(f"{what}: x has {K} columns, the Linear takes {w_hi.shape[1]}")
+    if K < 8 or K % 8:
+        raise RuntimeError(f"{what}: K = {K} is not a multiple of 8 (the f16 MFMA fragment is 8 consecutive k)")
+    if residual is not None:
+        residual = _rows("residual", residual, Nout, what)
+        if residual.shape[0] != rows:
+            raise RuntimeError(f"{what}: residual has {residual.shape[0]} rows, x has {rows}")
+    if out is None:
+        out = torch.empty(rows, Nout, dtype=torch.float32, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (rows, Nout)
+              and out.device == x.device and (Nout == 1 or out.stride(1) == 1) and (rows <= 1 or out.stride(0) >= Nout)):
+        raise RuntimeError(f"{what}: `out` must be float32 [{rows}, {Nout}] with unit last stride on the device of x")
+    if rows == 0:
+        return out
+    eps = -1.0 if norm_eps is None else float(norm_eps)
+    if norm_eps is not None and not (eps >= 0.0 and math.isfinite(eps)):
+        raise RuntimeError(f"{what}: norm_eps must be finite and not negative, got {norm_eps!r}")
+    span = lambda t: (t.data_ptr(), t.data_ptr() + 4 * ((t.shape[0] - 1) * (t.stride(0) if t.shape[0] > 1 else 0) + t.shape[1]))
+    (xa, xb), (oa, ob) = span(x), span(out)
+    if xa < ob and oa < xb:
+        raise RuntimeError(f"{what}: `out` overlaps `x` (a workgroup would read rows that another has already written)")
+    ops = _lib.torch_ops()
+    if ops is not None:
+        ops.rows_linear(x, w_hi, w_lo, inv_scale, bias, eps, bool(gelu), residual, out, prec)
+        return out
+    ld = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    _lib.check(_lib.lib().bt_rows_linear(x.data_ptr(), ld(x), w_hi.data_ptr(), w_lo.data_ptr(), inv_scale,
+                                         None if bias is None else bias.data_ptr(), None if residual is None else residual.data_ptr(),
+                                         0 if residual is None else ld(residual), out.data_ptr(), ld(out), rows, K, Nout,
+                                         0 if norm_eps is None else 1, max(eps, 0.0), 1 if gelu else 0, prec,
+                                         torch.cuda.current_stream(x.device).cuda_stream), "bt_rows_linear")
+    return out
+
+
+def _check_block_rows(blk, C, training):
+    """What the fused rows add to _check_block's refusals: the LayerNorms carry no affine parameters, the activation is tanh-GELU."""
+    heads = _check_block(blk, C, training)
+    for name in ("norm1", "norm2"):
+        norm = getattr(blk, name)
+        if getattr(norm, "weight", None) is not None or getattr(norm, "bias", None) is not None:
+            raise RuntimeError(f"update_former: {name} has affine parameters; the fused LayerNorm prologue applies none")
+        if tuple(getattr(norm, "normalized_shape", (C,))) != (C,):
+            raise RuntimeError(f"update_former: {name} normalises {tuple(norm.normalized_shape)}, not the {C} columns of a row")
+    act = blk.mlp.act
+    if not isinstance(act, torch.nn.GELU) or getattr(act, "approximate", "none") != "tanh":
+        raise RuntimeError("update_former: mlp.act is not nn.GELU(approximate='tanh'); the fused epilogue has no other activation")
+    return heads
+
+
+def _attn_block_rows(x, blk, axis, N, S, heads, precision):
+    qkv = rows_linear(x, blk.attn.qkv, norm_eps=blk.norm1.eps, precision=precision)
+    scale = float(getattr(blk.attn, "scale", HEAD_DIM ** -0.5))
+    a = attention(qkv, heads, N, S, S, 1, scale) if axis == "time" else attention(qkv, heads, S, N, 1, S, scale)
+    x1 = rows_linear(a, blk.attn.proj, residual=x, precision=precision)
+    h = rows_linear(x1, blk.mlp.fc1, norm_eps=blk.norm2.eps, gelu=True, precision=precision)
+    return rows_linear(h, blk.mlp.fc2, residual=x1, out=x1, precision=precision)
+
+
+def attn_block_rows(x, blk, axis, N, S, precision="f16x3"):
+    """attn_block with every row-wise part in bt_rows_linear: five launches (qkv = LN(x) Wqkv^T + b; the attention;
+    x1 = x + a Wproj^T + b; h = GELU(LN(x1) Wfc1^T + b); x2 = x1 + h Wfc2^T + b).  x is not written."""
+    _precision(precision, "attn_block_rows")
+    x = _gpu("x", x, "attn_block_rows")
+    if axis not in ("time", "space"):
+        raise RuntimeError(f"attn_block_rows: axis must be 'time' or 'space', got {axis!r}")
+    if x.dim() != 2 or x.shape[0] != N * S:
+        raise RuntimeError(f"attn_block_rows: x must be [N * S, C] = [{N * S}, C], got {tuple(x.shape)}")
+    heads = _check_block_rows(blk, x.shape[1], False)
+    with torch.no_grad():
+        return _attn_block_rows(x, blk, axis, N, S, heads, precision)
+
+
+def forward_rows(self, input_tensor, precision="f16x3"):
+    """`forward` with the rows on the f16 matrix pipe: input_transform, five launches a block, flow_head."""
+    _precision(precision, "UpdateFormer.forward_rows")
+    x = _gpu("input_tensor", input_tensor, "UpdateFormer.forward_rows")
+    if x.dim() != 4 or x.shape[0] != 1:
+        raise RuntimeError(f"UpdateFormer.forward_rows: input [B, N, T, C] with B = 1 (B > 1 is not built), got {tuple(x.shape)}")
+    B, N, T, __ = x.shape
+    time_blocks = list(self.time_blocks)
+    space_blocks = list(self.space_blocks) if getattr(self, "add_space_attn", True) else []
+    C = self.input_transform.weight.shape[0]
+    training = bool(getattr(self, "training", False))
+    heads = [_check_block_rows(blk, C, training) for blk in time_blocks + space_blocks]
+    with torch.no_grad():
+        x = rows_linear(x.reshape(N * T, -1), self.input_transform, precision=precision)
+        j = 0
+        for i, blk in enumerate(time_blocks):
+            x = _attn_block_rows(x, blk, "time", N, T, heads[i], precision)
+            if space_blocks and i % (len(time_blocks) // len(space_blocks)) == 0:
+                x = _attn_block_rows(x, space_blocks[j], "space", N, T, heads[len(time_blocks) + j], precision)
+                j += 1
+        return rows_linear(x, self.flow_head, precision=precision).reshape(B, N, T, -1)
+
+
+def install(module=None, precision=None):
     """Set `UpdateFormer.forward` in the reference's `main.frontend.core.cotracker.blocks` (or in the module given) to the
-    function above; returns what was bound before.  Opt-in: nothing in batrack_amd calls it."""
+    `forward` above, or with a `precision` ("f16x3", "f16") to `forward_rows` at that precision; returns what was bound
+    before.  Opt-in: nothing in batrack_amd calls it."""
+    if precision is not None:
+        _precision(precision, "install")
     if module is None:
         module = importlib.import_module("main.frontend.core.cotracker.blocks")
     previous = getattr(module.UpdateFormer, "forward", None)
-    module.UpdateFormer.forward = forward
+    if precision is None:
+        module.UpdateFormer.forward = forward
+    else:
+        def forward_at(self, input_tensor):
+            return forward_rows(self, input_tensor, precision)
+        forward_at.precision = precision
+        module.UpdateFormer.forward = forward_at
     return previous
